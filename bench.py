@@ -14,7 +14,9 @@ independent) and each step ends with the one real exchange of the path: an RCCL 
 of the driver contract and the RCCL id broadcast run over the product's own TCP rendezvous
 (timed_hip/rendezvous.py) on the RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT the launcher sets.
 
-The JSON line carries, besides the contract fields:
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes the
+probabilities of the last timed step as DIR/probs.npy (rank 0's; with N > 1 the gathered matrix).  `--full` adds
+everything that is measured beside the headline, outside the timed region except the roofline's HIP events:
   roofline      the dominant kernel (largest share of device time), timed live with HIP events on the
                 model's stream inside the timed region: algorithmic FLOPs per launch / mean launch
                 duration vs the dense fp32 MFMA peak (157.3 TFLOP/s).  The path is compute-bound
@@ -22,6 +24,9 @@ The JSON line carries, besides the contract fields:
                 whole job is reported beside it in "hbm".
   cpu_baseline  the NumPy/BLAS oracle (a port, not TensorFlow) timed on this host's cores on a bounded
                 sample of the same workload.
+  e2e, sampler, other_configs, pmc
+                host-resident and predict.py legs, the sampler, the other BASELINE topologies and the in-run
+                rocprofv3 --pmc passes (tools/bench_legs.py); --no-* options leave parts of this out.
 """
 from __future__ import annotations
 
@@ -123,6 +128,23 @@ def cpu_baseline(cfg, weights, topology: str, budget_s: float = 15.0, min_s: flo
                        f"the container's CPU quota; fp32, {dt:.1f} s wall")
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """Write every array as <out_dir>/<name>.npy in float32.  When they hold more than `budget` bytes in all, each keeps the
+    same fraction of its rows, a sample drawn with a fixed seed, in row order: two builds run with the same arguments write
+    the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if total > budget:
+            keep = max(1, a.shape[0] * budget // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -134,6 +156,9 @@ def main():
     ap.add_argument("--allow-host-exchange", action="store_true",
                     help="development only: ranks that SHARE a GPU exchange their rows over TCP instead of RCCL (the line says so); "
                          "without it a --gpus N run that is not N RCCL ranks with a verified gather exits with an error")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the probabilities of the last timed step to DIR/probs.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline and per-kernel table, the CPU baseline and the secondary legs (off: headline only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP events (roofline omitted)")
     ap.add_argument("--no-extras", action="store_true", help="skip the e2e / sampler / other-topology legs (N=1 only)")
@@ -144,6 +169,9 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc child passes (roofline.traffic stays null)")
     ap.add_argument("--other-frames", type=int, default=100000, help="frames for the densecpd / timed_rotamer legs (BASELINE config 3: 100 k frames)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    profile = args.full and not args.no_profile
 
     # stdout carries exactly one JSON line: gloo / RCCL banners written to fd 1 by native code go to stderr
     sys.stdout.flush()
@@ -219,15 +247,15 @@ def main():
         elif host_gather is not None:
             host_gather.allgather(d_probs.download((n, model.n_classes), np.float32).tobytes())
 
-    # warm-up steps run with every plan step bracketed by HIP events (the per-layer table); the timed steps
+    # --full: warm-up steps run with every plan step bracketed by HIP events (the per-layer table); the timed steps
     # bracket only the dominant kernel (2 events per chunk), which is what `roofline` is computed from
-    if not args.no_profile:
+    if profile:
         model.profile(1)
     for _ in range(args.warmup):
         step()
     _lib.check(lib.th_dev_sync(device))
-    warm_steps = [s for s in model.steps() if s["launches"]] if not args.no_profile else []
-    if not args.no_profile:
+    warm_steps = [s for s in model.steps() if s["launches"]] if profile else []
+    if profile:
         model.profile(2)
     barrier()
     _lib.check(lib.th_dev_sync(device))
@@ -279,6 +307,12 @@ def main():
         sys.exit(f"[bench] --gpus {world}: not {world} RCCL ranks with a verified gather (rccl_ranks={world if comm else 0}, "
                  f"gather_verified={gather_verified})")
 
+    # what a caller of the timed path receives from its last step: rank 0's rows, or the gathered matrix of every rank
+    if args.dump_outputs and rank == 0:
+        out = d_gather if d_gather is not None else d_probs
+        rows = world * n if d_gather is not None else n
+        dump_outputs(args.dump_outputs, {"probs": out.download((rows, model.n_classes), np.float32)})
+
     if rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_legs
@@ -318,7 +352,7 @@ def main():
             "hbm": {"algo_bytes_per_frame": algo_bytes, "achieved_GBps": fps / world * algo_bytes / 1e9,
                     "frac": fps / world * algo_bytes / 1e9 / PEAK_HBM_GBS},
         }
-        if not args.no_profile:
+        if profile:
             dom = max((s for s in model.steps() if s["launches"]), key=lambda s: s["ms"])   # timed region: dominant step only
             avg_ms = dom["ms"] / dom["launches"]
             frames_per_launch = n * args.steps / dom["launches"]
@@ -342,9 +376,9 @@ def main():
                                     "frac_of_pipe_peak": (bench_legs.step_pipe(s)[2] * n * args.warmup / (s["ms"] * 1e-3) / 1e12 /
                                                           bench_legs.step_pipe(s)[1]) if s["ms"] and s["flops"] else None}
                                    for s in warm_steps]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, weights, f"{model.name}-synth")
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # secondary legs, outside the timed region (tools/bench_legs.py): each is reported, none feeds `value`
             model.profile(0)
             t_legs = time.perf_counter()

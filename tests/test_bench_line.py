@@ -93,3 +93,23 @@ def test_bf16x3_steps_are_priced_on_the_bf16_pipe():
     # 400 k frames/s: the two steps need 0.1167 + 0.0662 of the wall time of their pipes at peak
     f = bench_legs.pipe_time_frac([fp32, split, {"label": "k_wino_in", "flops": 0.0}], 400e3)
     assert abs(f - (400e3 * 45.88e6 / 157.3e12 + 400e3 * 6 * 69.01e6 / 2500e12)) < 1e-12
+
+
+def test_dump_outputs_writes_float32_and_caps_the_total_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: arrays within the budget are written whole; over it, every array keeps the same share of its rows,
+    drawn with a fixed seed, so two runs of two builds write the same rows"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    probs = np.arange(1000 * 20, dtype=np.float64).reshape(1000, 20)
+    bench.dump_outputs(str(tmp_path / "whole"), {"probs": probs})
+    whole = np.load(tmp_path / "whole" / "probs.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, probs.astype(np.float32))
+    budget = 1000 * 20 * 4 // 8
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"probs": probs}, budget=budget)
+    a, b = np.load(tmp_path / "a" / "probs.npy"), np.load(tmp_path / "b" / "probs.npy")
+    assert a.nbytes <= budget and a.shape == (125, 20) and np.array_equal(a, b)
+    rows = a[:, 0] / 20
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, probs[rows.astype(int)].astype(np.float32))
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6

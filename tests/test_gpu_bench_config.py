@@ -115,3 +115,33 @@ def test_two_lanes_give_the_same_bits(gpu, lib, monkeypatch):
         assert np.array_equal(got, ref), f"two lanes (lag {lag}) changed {np.count_nonzero((got != ref).any(1))} rows"
     d_frames.free()
     d_p.free()
+
+
+def test_plain_bench_run_dumps_the_probabilities_of_its_last_step(gpu, tmp_path):
+    """bench.py without --full: the headline line only (no CPU baseline, no roofline, no secondary legs), --steps timed steps, and
+    --dump-outputs writes the last timed step's [frames, classes] probabilities.  The inputs are the same in every run; two
+    processes may differ in the last bit of a few rows (measured: 24 of 100 000 rows by 1 ulp), so they agree to TIGHT"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = CHUNK + 300
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--frames", str(n), "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=300, env=dict(os.environ, TH_BENCH_DETAIL=str(tmp_path / "detail.json")))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append(np.load(out / "probs.npy"))
+    for line in lines:
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["metric"] == "residue_frames_per_sec" and line["unit"] == "frames/s" and line["dtype"] == "f32"
+        for k in ("cpu_baseline", "roofline", "e2e", "sampler", "other_configs"):
+            assert k not in line, k
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (n, 20)
+    np.testing.assert_allclose(a.sum(1), 1.0, atol=1e-5)
+    np.testing.assert_allclose(a, b, atol=TIGHT, rtol=0)

@@ -30,7 +30,7 @@ timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/sampler" -o sampler -- pyt
 cd "$ROOT"
 SM=$(find "$OUT/sampler" -name '*.db' | head -1)
 [ -n "$SM" ] && python tools/rocpd_summary.py --kernel-trace "$SM" > "$OUT/sampler_rocprof.txt" 2>> "$OUT/summary.err"
-# the bench line itself, default settings, outside the profiler
-timeout 600 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+# the bench line itself with every leg (--full), outside the profiler
+timeout 600 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 tail -1 "$OUT/bench_default.json"
 rm -rf "$OUT"/*/*.db "$OUT"/*/*/*.db 2>/dev/null   # databases are large; the summaries are what we keep
