@@ -4,7 +4,9 @@ Every th_model_load checks the plan it built — Cook-Toom / Winograd layers, th
 plan of the same pack on four internally generated frames; logits must agree to 1e-5 x max(1, max |logit|), otherwise fast
 features are dropped until they do.  Why: parity is unpinned against TensorFlow and real `.h5` weights have never been seen
 (reference predict.py:121), so the error figures of the fast forms come from synthetic weights only."""
+import json
 import os
+import re
 
 import numpy as np
 import pytest
@@ -21,7 +23,11 @@ def _labels(model):
 
 
 def _fast(labels):
-    return [l for l in labels if "conv_wino" in l or "conv_wf<" in l or "k_conv_first_w" in l or "k_conv_first_b3" in l]
+    """the steps that run a minimal-filtering or split-operand kernel, judged by the bracketed kernel name that ends each label
+    (a label starts with the user's layer name, which may look like a kernel's)"""
+    kernels = [re.search(r"\[([^\]]+)\]\s*$", l) for l in labels]
+    return [l for l, k in zip(labels, kernels)
+            if k and k.group(1).startswith(("k_wino_", "k_conv_wf", "k_conv_first_w", "k_conv_first_b3"))]
 
 
 def test_guard_passes_on_the_benchmark_topologies(gpu):
@@ -50,6 +56,14 @@ def test_guard_off_and_nothing_to_check(gpu, monkeypatch):
     monkeypatch.setenv("TH_FIRST_WINO", "0")
     model = engine.HipFrameModel.from_keras(cfg, w, device=gpu)            # a direct plan: no fast step, the guard has nothing to do
     assert model.guard()["state"] == 0 and not _fast(_labels(model))
+    model.close()
+    # the same direct plan with a convolution whose name reads like a fast kernel's: layer names do not make a plan "fast"
+    named = json.loads(json.dumps(cfg).replace('"conv3d"', '"k_conv_first5_x"'))
+    wn = {("k_conv_first5_x" if k == "conv3d" else k): v for k, v in w.items()}
+    model = engine.HipFrameModel.from_keras(named, wn, device=gpu)
+    labels = _labels(model)
+    assert any(l.startswith("k_conv_first5_x: ") for l in labels), labels
+    assert model.guard()["state"] == 0 and not _fast(labels)
     model.close()
 
 

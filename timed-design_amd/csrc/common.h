@@ -32,7 +32,7 @@ void th_set_error(const char* fmt, ...);
 
 // ---- A/B and test knobs ---------------------------------------------------------------------
 // Every TH_* environment variable that changes what a MODEL plans or launches is read exactly once, by th_model_load, into the
-// handle (th_knobs_read).  Planners take the snapshot of the load in progress (th_knobs_planning) and leave a pointer to it
+// handle (th_knobs_read).  Planners are handed the snapshot of the load in progress (a `const ThKnobs&`) and leave a pointer to it
 // in their plan structs, launchers read it from there: no getenv in a launch path, no process-wide static caches — two models
 // loaded under different environments keep their own settings, whatever the call order.  `nondefault` lists what was set
 // ("TH_WINOGRAD=0 TH_WF_DBG=3"); th_model_knobs() returns it and bench.py prints it.
@@ -62,8 +62,6 @@ struct ThKnobs {
     std::string nondefault;
 };
 void th_knobs_read(ThKnobs* k);                 // the process environment, now
-const ThKnobs& th_knobs_planning();             // the snapshot of the th_model_load in progress on this thread (defaults outside one)
-void th_knobs_set_planning(const ThKnobs* k);   // runtime.hip, around the planner
 inline const ThKnobs& th_knobs_of(const ThKnobs* k) { static const ThKnobs dflt; return k ? *k : dflt; }
 
 // hipMalloc for every allocator inside the library: when the device is out of memory the blocks parked in the model block
@@ -164,7 +162,8 @@ struct ConvMfmaPlan {
     int FB = 1, ZB = 0, nzb = 1;  // frames / conv z-planes per workgroup, z bricks per frame
     int Zp = 0, Hp = 0, Wp = 0;   // staged (haloed) brick extent
     int rows_pf = 0;              // GEMM rows per frame-brick (multiple of 32)
-    int bres = 0;                 // all taps' weights resident in LDS
+    int bres = 0;                 // all taps' weights resident in LDS (3: the k_conv_n16 weight ring)
+    int ncu = 0;                  // CUs of the model's device: the persistent kernels (k_conv_n16, k_conv_first_b3) size their grid by it
     size_t lds_bytes = 0;
     size_t tab_off = 0;           // byte offset of the row tables inside the LDS allocation
     size_t wpk_floats = 0;        // size of the prepacked weight image
@@ -178,11 +177,11 @@ struct ConvMfmaPlan {
 // choose a tiling for this convolution; returns false when the MFMA kernel does not apply
 // (stride/dilation != 1, nothing fits in LDS, ...)
 bool conv_mfma_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool,
-                    ConvMfmaPlan* plan);
+                    const ThKnobs& kn, ConvMfmaPlan* plan);
 // a narrower instantiation for the last Cout block of a layer planned on 128-column blocks (see conv_mfma.hip); on success
 // the main launch covers output channels [0, *cout_main) and `tail` the rest
 bool conv_mfma_plan_tail(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool,
-                         const ConvMfmaPlan& main, ConvMfmaPlan* tail, int* cout_main);
+                         const ConvMfmaPlan& main, const ThKnobs& kn, ConvMfmaPlan* tail, int* cout_main);
 // host-side weight re-layout: Keras [kd,kh,kw,Cin,Cout] -> [nb][chunk][tap][BN][CS]
 void conv_mfma_pack_weights(const ConvMfmaPlan& p, const ConvGeom& g, int Cin, int Cout, const float* w_keras,
                             float* dst);
@@ -205,7 +204,8 @@ struct ConvWinoPlan {
     std::string label;
 };
 // split: 0 = fp32 MFMA (exact fp32 products), 1 = bf16x3 split operands (see ConvWinoPlan::split)
-bool conv_wino_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int scheme, ConvWinoPlan* plan, int split = 0);
+bool conv_wino_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int scheme, int split, const ThKnobs& kn,
+                    ConvWinoPlan* plan);
 void conv_wino_pack_weights(const ConvWinoPlan& p, const float* w_keras, float* dst);
 // V, M: scratch for ceil(n / 64) * 64 frames (v_fpf / m_fpf floats each).  Three launches = three plan steps.
 int launch_wino_in(hipStream_t s, int64_t n, const ConvWinoPlan& p, TView in, float* V, PreOp pre);
@@ -223,10 +223,11 @@ struct ConvWfPlan {
     size_t wpk_floats = 0, lds_bytes = 0;
     double own_flops = 0;            // the algorithm's multiply-adds x 2 per frame (16 positions x 3 z taps per 2 x 2 tile)
     double exec_flops = 0;           // MFMA FLOPs issued per frame
+    int ncu = 0;                     // CUs of the model's device (one persistent workgroup each)
     const ThKnobs* knobs = nullptr;
     std::string label;
 };
-bool conv_wf_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, ConvWfPlan* plan);
+bool conv_wf_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvWfPlan* plan);
 bool conv_wf_view_ok(const TView& in);      // 16-byte aligned channel slices
 int conv_wf_pre_kind(const PreOp& pre);
 std::string conv_wf_label(const ConvWfPlan& p, const PreOp& pre);    // the plan's label with the kernel's full template argument list
@@ -241,10 +242,11 @@ struct ConvWfsPlan {
     int Cin = 0, Cout = 0, nkh = 0, ncp = 0;       // nkh: phases of 16 input channels, ncp: passes of 64 output channels
     size_t wpk_floats = 0, lds_bytes = 0;
     double own_flops = 0, exec_flops = 0;
+    int ncu = 0;                                   // CUs of the model's device (one persistent workgroup each)
     const ThKnobs* knobs = nullptr;
     std::string label;
 };
-bool conv_wfs_plan(const ConvWfPlan& base, const TView& in, const PreOp& pre, ConvWfsPlan* plan);
+bool conv_wfs_plan(const ConvWfPlan& base, const TView& in, const PreOp& pre, const ThKnobs& kn, ConvWfsPlan* plan);
 void conv_wfs_pack_weights(const ConvWfsPlan& p, const float* w_keras, float* dst);
 int launch_conv_wfs(hipStream_t s, int64_t n, const ConvWfsPlan& p, TView in, TView out, const float* wpk, const float* bias, PostOps post);
 
@@ -254,7 +256,7 @@ int launch_sparse_expand(hipStream_t s, int64_t n, const uint32_t* bits, const u
 // ---- first-layer convolution (conv_first.hip): Cin <= 8, Cout <= 32, 3x3x3, reads the caller's frames ----
 std::string conv_first_label(const ConvMfmaPlan& p, int Cin, const PostOps& post);
 bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& out_conv, const ConvGeom& g, int Cout, int pool,
-                     ConvMfmaPlan* plan);
+                     const ThKnobs& kn, ConvMfmaPlan* plan);
 void conv_first_pack_weights(int Cin, int Cout, const float* w_keras, float* dst);
 void conv_first_w_pack_weights(int Cin, int Cout, const float* w_keras, float* dst);    // plans with first_wino set
 int launch_conv_first(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const void* frames, int dtype, int Din, int Hin,
@@ -269,16 +271,16 @@ int launch_conv_first_b3(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const 
                          const float* wpk, const float* bias, PostOps post);
 
 // 5x5x5 'same' convolution on the model input, <= 8 channels -> <= 16 filters, 2^3 max-pool behind it (conv_first5.hip): ProDCoNN's stem
-bool conv_first5_ok(int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, int pool);
+bool conv_first5_ok(int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, int pool, const ThKnobs& kn);
 size_t conv_first5_wpk_floats();
 double conv_first5_exec_flops();
 std::string conv_first5_label();
 void conv_first5_pack_weights(int Cin, int Cout, const float* w_keras, float* dst);
-int launch_conv_first5(hipStream_t s, int64_t n, const ThKnobs* knobs, const void* frames, int dtype, int Cin, TView out, int Cout,
+int launch_conv_first5(hipStream_t s, int64_t n, const ThKnobs* knobs, int ncu, const void* frames, int dtype, int Cin, TView out, int Cout,
                        const float* wpk, const float* bias, PostOps post);
 
 // ---- pointwise (1x1x1) streaming convolution (conv_pointwise.hip); plan.cfg in [300, 309) ----
-bool conv_pw_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, ConvMfmaPlan* plan);
+bool conv_pw_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvMfmaPlan* plan);
 void conv_pw_pack_weights(const ConvMfmaPlan& p, int Cin, int Cout, const float* w_keras, float* dst);
 std::string conv_pw_label(const ConvMfmaPlan& p, bool out_blk, const PostOps& post);
 int launch_conv_pw(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, TView out, int Cin, int Cout, const float* wpk,

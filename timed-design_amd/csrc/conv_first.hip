@@ -575,7 +575,7 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 }  // namespace
 
 bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& oc, const ConvGeom& g, int Cout, int pool,
-                     ConvMfmaPlan* p) {
+                     const ThKnobs& kn, ConvMfmaPlan* p) {
     if (g.kd != 3 || g.kh != 3 || g.kw != 3) return false;
     if (g.sd != 1 || g.sh != 1 || g.sw != 1 || g.dd != 1 || g.dh != 1 || g.dw != 1) return false;
     // the kernel holds the weights of 32 output channels in registers; a wider first layer (33 .. 128 filters) runs it once per
@@ -591,7 +591,6 @@ bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& oc, const 
     p->Hp = p->Hc + 2;
     p->Wp = p->Wc + 2;
     // F(2,3) along x (k_conv_first_w): 'same' padding, an even number of computed columns; rows are x pairs
-    const ThKnobs& kn = th_knobs_planning();
     p->knobs = &kn;
     const bool no_wino = !kn.first_wino;
     const bool wino = !no_wino && g.pz == 1 && g.py == 1 && g.px == 1 && p->Wc % 2 == 0 && p->Wc >= 2;

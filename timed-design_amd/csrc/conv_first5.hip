@@ -311,8 +311,7 @@ inline double f5_bf16_val(uint16_t b) {
 }  // namespace
 
 // does the kernel serve this layer?  (asked by the planner before anything is packed)
-bool conv_first5_ok(int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, int pool) {
-    const ThKnobs& kn = th_knobs_planning();
+bool conv_first5_ok(int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, int pool, const ThKnobs& kn) {
     if (!kn.first_split || kn.no_pool_first) return false;
     if (Din != kF5D || Hin != kF5D || Win != kF5D || Cin < 1 || Cin > 8 || Cout < 1 || Cout > 16) return false;
     if (g.kd != 5 || g.kh != 5 || g.kw != 5 || g.sd != 1 || g.sh != 1 || g.sw != 1 || g.dd != 1 || g.dh != 1 || g.dw != 1) return false;
@@ -357,7 +356,7 @@ void conv_first5_pack_weights(int Cin, int Cout, const float* w, float* dst_f) {
             }
 }
 
-int launch_conv_first5(hipStream_t s, int64_t n, const ThKnobs* knobs, const void* frames, int dtype, int Cin, TView out, int Cout,
+int launch_conv_first5(hipStream_t s, int64_t n, const ThKnobs* knobs, int ncu, const void* frames, int dtype, int Cin, TView out, int Cout,
                        const float* wpk, const float* bias, PostOps post) {
     if (n <= 0) return TH_OK;
     if (out.D != 10 || out.H != 10 || out.W != 10) TH_FAIL(TH_EINVAL, "conv_first5: the pooled output is not 10^3");
@@ -369,12 +368,6 @@ int launch_conv_first5(hipStream_t s, int64_t n, const ThKnobs* knobs, const voi
     a.Cout = Cout; a.bias = bias; a.post = post;
     a.out = out.p; a.out_fs = out.fs; a.out_cs = out.cs; a.out_coff = out.coff; a.Ho = out.H; a.Wo = out.W;
     a.nframes = n;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const ThKnobs& kn = th_knobs_of(knobs);
     int64_t resident = ncu;
     if (kn.wf_resident) resident = std::max(1, kn.wf_resident);       // tests: several frames per workgroup on small batches

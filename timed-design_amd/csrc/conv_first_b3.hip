@@ -574,14 +574,8 @@ int launch_conv_first_b3(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const 
         a.out_blk_stride = out.D * out.H * out.W * 4;
     }
     a.nframes = n;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const ThKnobs& kn = th_knobs_of(p.knobs);
-    int64_t resident = ncu;                              // one 8-wave workgroup per CU (139 KB of LDS)
+    int64_t resident = p.ncu;                            // one 8-wave workgroup per CU (139 KB of LDS)
     if (kn.wf_resident) resident = std::max(1, kn.wf_resident);       // tests: force multi-frame workgroups on small batches
     // equal trips: every workgroup streams ceil(n / grid) or one frame fewer
     const int64_t trips = (n + resident - 1) / resident;

@@ -1309,9 +1309,9 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 }  // namespace
 
 static bool plan_with_cfg(int cfg, size_t lds_limit, bool whole_frames_only, const TView& in, const TView& oc,
-                          const ConvGeom& g, int Cin, int Cout, int pool, ConvMfmaPlan* p) {
+                          const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvMfmaPlan* p) {
     const CfgDesc& c = kCfgs[cfg];
-    p->knobs = &th_knobs_planning();
+    p->knobs = &kn;
     p->cfg = cfg;
     p->CI = c.CI;
     p->CS = c.CI == 8 ? 8 : c.CI + 4;  // CI=8: unpadded (2-way ds_read_b128 conflict, but the brick fits)
@@ -1388,7 +1388,7 @@ static bool plan_with_cfg(int cfg, size_t lds_limit, bool whole_frames_only, con
     }
     if ((int64_t)FB * oc.fs > 0x7fffffffLL || (int64_t)FB * in.D * in.H * in.W * std::max(in.cs, in.C) > 0x7fffffffLL) return false;
     p->geo = 0;
-    if (g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && p->Hp == p->Wp && p->CS == 20 && !th_knobs_planning().conv_nogeo)
+    if (g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && p->Hp == p->Wp && p->CS == 20 && !kn.conv_nogeo)
         for (const MfmaGeo& ge : kMfmaGeo)
             if (ge.cfg == cfg && ge.pool == pool && ge.geo == p->Hp) p->geo = ge.geo;
     char buf[224], geo[16];
@@ -1422,9 +1422,9 @@ const ConvKernelN16 kN16Kernels[kNumN16][3] = {
     {k_conv_n16<4, 4, 0, 4>, nullptr, nullptr},
 };
 bool plan_n16(int variant, size_t lds_limit, const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool,
-              ConvMfmaPlan* p) {
+              const ThKnobs& kn, ConvMfmaPlan* p) {
     const N16Cfg& c = kN16[variant];
-    p->knobs = &th_knobs_planning();
+    p->knobs = &kn;
     p->cfg = 200 + variant;
     p->CI = 16; p->CS = 20; p->BN = 16; p->nnb = 1; p->nchunks = (Cin + 15) / 16; p->pool = pool; p->bres = 3;
     p->Dc = pool ? (oc.D / 2) * 2 : oc.D;
@@ -1453,7 +1453,7 @@ bool plan_n16(int variant, size_t lds_limit, const TView& in, const TView& oc, c
     p->exec_flops = 2.0 * (double)p->rows_pf * p->nzb * 16.0 * (double)(p->nchunks * 16) * 27;   // MFMA only
     if ((int64_t)FB * oc.fs > 0x7fffffffLL || (int64_t)FB * in.D * in.H * in.W * std::max(in.cs, in.C) > 0x7fffffffLL) return false;
     p->geo = 0;
-    if (pool == 0 && p->Hp == p->Wp && !th_knobs_planning().n16_nogeo)
+    if (pool == 0 && p->Hp == p->Wp && !kn.n16_nogeo)
         for (const N16Geo& ge : kN16Geo)
             if (ge.variant == variant && ge.geo == p->Hp) p->geo = ge.geo;
     char buf[224], geo[24];
@@ -1466,7 +1466,7 @@ bool plan_n16(int variant, size_t lds_limit, const TView& in, const TView& oc, c
 }
 }  // namespace
 
-bool conv_mfma_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, ConvMfmaPlan* p) {
+bool conv_mfma_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvMfmaPlan* p) {
     if (g.dd != 1 || g.dh != 1 || g.dw != 1) return false;
     const bool strided = g.sd != 1 || g.sh != 1 || g.sw != 1;
     if (strided && pool) return false;   // strided convolutions run on the brick kernel (row table carries the stride), unpooled
@@ -1477,26 +1477,25 @@ bool conv_mfma_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin
     // TH_CONV_BMODE=dbuf keeps the LDS double-buffered weight slabs, =stream8 the 8-wave streamed kernels
     // (A/B comparisons); default: weights streamed L2 -> registers, two 4-wave workgroups per CU when whole
     // frames fit in half the LDS
-    const ThKnobs& kn = th_knobs_planning();
     p->knobs = &kn;
     const bool dbuf = kn.conv_bmode == 1, stream8 = kn.conv_bmode == 2, no16 = kn.conv_bmode == 3;
     if (!dbuf && !stream8 && !strided && Cout <= 16 && Cin > 8 && g.kd == 3 && g.kh == 3 && g.kw == 3 && !no16) {
-        if (plan_n16(1, kLdsLimit / 2, in, oc, g, Cin, Cout, pool, p)) return true;   // two 4-wave workgroups per CU
-        if (plan_n16(0, kLdsLimit, in, oc, g, Cin, Cout, pool, p)) return true;       // one 8-wave workgroup
+        if (plan_n16(1, kLdsLimit / 2, in, oc, g, Cin, Cout, pool, kn, p)) return true;   // two 4-wave workgroups per CU
+        if (plan_n16(0, kLdsLimit, in, oc, g, Cin, Cout, pool, kn, p)) return true;       // one 8-wave workgroup
     }
     // Cout 17..20 (a 20-class head): 16 channels on the matrix pipe + up to 4 on the VALU pipe underneath,
     // instead of a 32-wide tile with 12 zero columns
     if (!dbuf && !stream8 && !strided && Cout > 16 && Cout <= 20 && Cin > 8 && pool == 0 && g.kd == 3 && g.kh == 3 && g.kw == 3 && !no16 &&
         !kn.conv_noxc) {
-        if (plan_n16(2, kLdsLimit / 2, in, oc, g, Cin, Cout, pool, p)) return true;
+        if (plan_n16(2, kLdsLimit / 2, in, oc, g, Cin, Cout, pool, kn, p)) return true;
     }
     if (!dbuf && cfg >= 1 && cfg <= 3) {
-        if (!stream8 && plan_with_cfg(cfg + 7, kLdsLimit / 2, true, in, oc, g, Cin, Cout, pool, p)) return true;
+        if (!stream8 && plan_with_cfg(cfg + 7, kLdsLimit / 2, true, in, oc, g, Cin, Cout, pool, kn, p)) return true;
         cfg += 4;
     }
-    if (plan_with_cfg(cfg, kLdsLimit, false, in, oc, g, Cin, Cout, pool, p)) return true;
+    if (plan_with_cfg(cfg, kLdsLimit, false, in, oc, g, Cin, Cout, pool, kn, p)) return true;
     // Cin <= 8 with a kernel too large for LDS-resident weights: stream them
-    if (cfg == 0 || cfg == 4) return plan_with_cfg(cfg == 0 ? 11 : 12, kLdsLimit, false, in, oc, g, Cin, Cout, pool, p);
+    if (cfg == 0 || cfg == 4) return plan_with_cfg(cfg == 0 ? 11 : 12, kLdsLimit, false, in, oc, g, Cin, Cout, pool, kn, p);
     return false;
 }
 
@@ -1506,13 +1505,13 @@ bool conv_mfma_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin
 // is a workgroup), so unlike a split over different kernels nothing is staged more often than before.  TIMED-rotamer's
 // head (256 -> 338 at 5^3, half of that model's time): 128 + 128 + 96 = 352 columns instead of 3 x 128 = 384.
 bool conv_mfma_plan_tail(const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, const ConvMfmaPlan& main,
-                         ConvMfmaPlan* tail, int* cout_main) {
-    const bool off = th_knobs_planning().conv_notail != 0;     // A/B comparisons and tests
+                         const ThKnobs& kn, ConvMfmaPlan* tail, int* cout_main) {
+    const bool off = kn.conv_notail != 0;     // A/B comparisons and tests
     if (off || main.cfg != 9 || main.nnb < 2) return false;
     const int done = (main.nnb - 1) * main.BN, rest = Cout - done;
     if (rest <= 0 || rest > 96) return false;
     const int cfg = rest <= 32 ? 10 : (rest <= 64 ? 8 : 13);
-    if (!plan_with_cfg(cfg, kLdsLimit / 2, true, in, oc, g, Cin, rest, pool, tail)) return false;
+    if (!plan_with_cfg(cfg, kLdsLimit / 2, true, in, oc, g, Cin, rest, pool, kn, tail)) return false;
     if (tail->nnb != 1) return false;
     *cout_main = done;
     return true;
@@ -1611,13 +1610,7 @@ int launch_conv_mfma(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, 
     const int64_t groups = (n + p.FB - 1) / p.FB;
     int64_t grid = groups * p.nzb * p.nnb;
     if (n16) {  // persistent workgroups: one resident set, each walks groups blockIdx.x, +gridDim.x, ...
-        static int ncu = 0;
-        if (!ncu) {
-            int dev = 0;
-            HIP_TRY(hipGetDevice(&dev));
-            HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        }
-        int64_t resident = (int64_t)ncu * (c.WAVES == 4 ? 2 : 1);
+        int64_t resident = (int64_t)p.ncu * (c.WAVES == 4 ? 2 : 1);
         if (kn.n16_resident) resident = std::max(1, kn.n16_resident);   // tests: force multi-trip workgroups
         // units = (frame group, slab); equal trip counts: ceil(units / ceil(units / resident)) workgroups, and a
         // workgroup keeps its slab: the stride is a multiple of nzb

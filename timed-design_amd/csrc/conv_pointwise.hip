@@ -60,8 +60,7 @@ constexpr size_t kPwLdsLimit = 64 * 1024;
 }  // namespace
 
 // plan encoding (ConvMfmaPlan): cfg = 300 + 3*kmax_index + nt_index, CI = 8*K8 (padded Cin), BN = 32*NT, bres = 4
-bool conv_pw_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, ConvMfmaPlan* p) {
-    const ThKnobs& kn = th_knobs_planning();
+bool conv_pw_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvMfmaPlan* p) {
     if (kn.conv_nopw) return false;                             // A/B comparisons against conv_mfma
     p->knobs = &kn;
     if (g.kd != 1 || g.kh != 1 || g.kw != 1) return false;

@@ -547,8 +547,7 @@ size_t wfs_lds_bytes(int D, int H, int W) {
 // `base` is the layer's conv_wfused plan (geometry and padding already checked there); the split form serves it when the knobs
 // allow, the layer has no input prologue (the slice goes from HBM to LDS without passing through registers), Cin is a multiple
 // of 16 (one k-step per phase) and more than 32 output channels exist (a pass multiplies two 32-column tiles)
-bool conv_wfs_plan(const ConvWfPlan& base, const TView& in, const PreOp& pre, ConvWfsPlan* p) {
-    const ThKnobs& kn = th_knobs_planning();
+bool conv_wfs_plan(const ConvWfPlan& base, const TView& in, const PreOp& pre, const ThKnobs& kn, ConvWfsPlan* p) {
     if (!kn.wf_split || base.geo < 0) return false;
     if (conv_wf_pre_kind(pre) != 0) return false;
     if (base.Cin % 16 != 0 || base.Cin < 16 || base.Cout <= 32) return false;
@@ -629,14 +628,8 @@ int launch_conv_wfs(hipStream_t s, int64_t n, const ConvWfsPlan& p, TView in, TV
     const int64_t nslots = (n + 7) / 8 * 8 * p.ncp;
     if (nslots > 0x7fffffffLL) TH_FAIL(TH_EINVAL, "conv_wfs: too many frames per launch");
     a.nslots = (unsigned)nslots;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const ThKnobs& kn = th_knobs_of(p.knobs);
-    int64_t resident = ncu;                              // one 8-wave workgroup per CU
+    int64_t resident = p.ncu;                            // one 8-wave workgroup per CU
     if (kn.wf_resident) resident = std::max(1, kn.wf_resident);
     const int64_t trips = (nslots + resident - 1) / resident;
     int64_t grid = (nslots + trips - 1) / trips;

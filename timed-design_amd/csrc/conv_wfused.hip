@@ -487,7 +487,7 @@ const WfDbg kWfDbg[] = {WF_DBG(1), WF_DBG(2), WF_DBG(3), WF_DBG(4), WF_DBG(7), W
 }  // namespace
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-bool conv_wf_plan(const TView& in, const TView& out, const ConvGeom& g, int Cin, int Cout, int pool, ConvWfPlan* p) {
+bool conv_wf_plan(const TView& in, const TView& out, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvWfPlan* p) {
     if (g.kd != 3 || g.kh != 3 || g.kw != 3 || g.sd != 1 || g.sh != 1 || g.sw != 1 || g.dd != 1 || g.dh != 1 || g.dw != 1) return false;
     if (g.pz != 1 || g.py != 1 || g.px != 1) return false;                              // 'same'
     if (in.D != out.D || in.H != out.H || in.W != out.W) return false;
@@ -499,7 +499,7 @@ bool conv_wf_plan(const TView& in, const TView& out, const ConvGeom& g, int Cin,
     if (geo < 0) return false;
     const int NT = (in.H / 2) * (in.W / 2);
     p->geo = geo; p->pool = pool;
-    p->knobs = &th_knobs_planning();
+    p->knobs = &kn;
     p->Cin = Cin; p->Cout = Cout;
     p->ncb = (Cout + 15) / 16;
     p->nchunks = Cin / 4;
@@ -569,13 +569,7 @@ int launch_conv_wf(hipStream_t s, int64_t n, const ConvWfPlan& p, TView in, TVie
     const int64_t nslots = (n + 7) / 8 * 8 * p.ncb;
     if (nslots > 0x7fffffffLL) TH_FAIL(TH_EINVAL, "conv_wf: too many frames per launch");
     a.nslots = (unsigned)nslots;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    int64_t resident = ncu;                              // one 8-wave workgroup per CU (154 KB of LDS)
+    int64_t resident = p.ncu;                            // one 8-wave workgroup per CU (154 KB of LDS)
     const ThKnobs& kn = th_knobs_of(p.knobs);
     if (kn.wf_resident) resident = std::max(1, kn.wf_resident);       // tests: force multi-trip workgroups
     const int64_t trips = (nslots + resident - 1) / resident;

@@ -40,9 +40,6 @@ void th_set_error(const char* fmt, ...) {
 }
 
 // ---- A/B and test knobs (ThKnobs, common.h) ---------------------------------------------------------------------------------
-static thread_local const ThKnobs* g_planning_knobs = nullptr;
-const ThKnobs& th_knobs_planning() { return th_knobs_of(g_planning_knobs); }
-void th_knobs_set_planning(const ThKnobs* k) { g_planning_knobs = k; }
 void th_knobs_read(ThKnobs* k) {
     *k = ThKnobs();
     std::string& nd = k->nondefault;
@@ -294,6 +291,7 @@ struct Step {
     int64_t launches = 0;
     int out_node = -1;
     bool is_final_softmax = false;
+    bool fast = false;            // a minimal-filtering or split-operand form (fast_form): what the load-time guard checks
 };
 
 // a remark in a step label, in front of the trailing " [kernel]" that tools/ parse
@@ -314,6 +312,7 @@ inline void keras_same_pad(int n, int k, int s, int d, int* before) {
 
 struct th_model {
     int device = 0;
+    int ncu = 0;                  // CUs of `device`: the persistent kernels size their grids by it
     unsigned flags = 0;
     hipStream_t stream = nullptr;
     std::vector<Node> nodes;
@@ -324,12 +323,6 @@ struct th_model {
     std::vector<Buffer> bufs;
     std::vector<Step> steps;
     int wino_v_buf = -1, wino_m_buf = -1;   // scratch arenas of the Winograd layers (shared: the layers run one after the other)
-    int wfused = 1;                         // eligible 3x3x3 'same' layers on 10^3 volumes run on conv_wfused.hip (TH_WFUSED=0: direct kernels)
-    int winograd = 1;                       // eligible 3x3x3 'same' layers on 5^3 volumes run on conv_wino.hip: 1 = F(3,3)+F(2,3) in-plane
-                                            // (default, as accurate as the direct form), 2 = F(5,3) (1.65x fewer products, ~4x the rounding
-                                            // error; opt-in), 0 = direct kernels (TH_WINOGRAD)
-    int wino_split = 1;                     // the Winograd GEMMs run on bf16 MFMA with exactly split operands (conv_wino.hip, k_wino_gemm_b3;
-                                            // TH_WINO_SPLIT=0: fp32-input MFMA)
     ThKnobs knobs;                          // the TH_* knobs as th_model_load found them (plans and launchers point here)
     // load-time guard (guard_check): 0 not run (TH_GUARD=0, or no fast plan to check), 1 passed, 2 tripped (fast features dropped)
     int guard_state = 0;
@@ -507,28 +500,75 @@ int bn_affine(th_model* m, const Node& bn, const float** scale, const float** sh
     return TH_OK;
 }
 
+// the activation `act` (slope `alpha`) at the end of an epilogue chain that has room for it
+void add_act(PostOps* po, int act, float alpha) {
+    const int i = po->n++;
+    if (i == 0) po->monotone = 1;
+    po->type[i] = POP_ACT;
+    po->act[i] = act;
+    po->alpha[i] = alpha;
+    const bool mono = act == ACT_LINEAR || act == ACT_RELU || act == ACT_SIGMOID || act == ACT_TANH ||
+                      ((act == ACT_ELU || act == ACT_LEAKY) && alpha >= 0.f);
+    if (!mono) po->monotone = 0;
+}
+
 int add_post(th_model* m, PostOps* po, const Node& n) {
     if (po->n >= TH_MAX_POST) return 1;
+    if (n.op != OP_BN) { add_act(po, n.ip[0], n.fp[0]); return TH_OK; }
     const int i = po->n;
     if (i == 0) po->monotone = 1;
-    if (n.op == OP_BN) {
-        po->type[i] = POP_AFFINE;
-        int rc = bn_affine(m, n, &po->scale[i], &po->shift[i]);
-        if (rc) return rc;
-        // scale = gamma * rsqrt(var + eps): its sign is gamma's
-        const float* g = n.w[0] >= 0 ? m->blob_host[n.w[0]] : nullptr;
-        for (int c = 0; g && c < n.ip[0]; ++c) if (!(g[c] >= 0.f)) po->monotone = 0;
-    } else {
-        po->type[i] = POP_ACT;
-        po->act[i] = n.ip[0];
-        po->alpha[i] = n.fp[0];
-        const int a = po->act[i];
-        const bool mono = a == ACT_LINEAR || a == ACT_RELU || a == ACT_SIGMOID || a == ACT_TANH ||
-                          ((a == ACT_ELU || a == ACT_LEAKY) && po->alpha[i] >= 0.f);
-        if (!mono) po->monotone = 0;
-    }
+    po->type[i] = POP_AFFINE;
+    if (int rc = bn_affine(m, n, &po->scale[i], &po->shift[i])) return rc;
+    // scale = gamma * rsqrt(var + eps): its sign is gamma's
+    const float* g = n.w[0] >= 0 ? m->blob_host[n.w[0]] : nullptr;
+    for (int c = 0; g && c < n.ip[0]; ++c) if (!(g[c] >= 0.f)) po->monotone = 0;
     po->n++;
     return TH_OK;
+}
+
+// the epilogue of output channels [c0, ...): its per-channel scale / shift vectors start at channel c0
+PostOps post_from(PostOps po, int c0) {
+    for (int k = 0; k < po.n; ++k) {
+        if (po.scale[k]) po.scale[k] += c0;
+        if (po.shift[k]) po.shift[k] += c0;
+    }
+    return po;
+}
+
+// a weight image of `floats` floats (zeroed), filled on the host by `pack`, then uploaded
+template <class Pack>
+int upload_packed(th_model* m, size_t floats, Pack pack, float** out) {
+    std::vector<float> h(floats);
+    pack(h.data());
+    return upload(m, h.data(), h.size(), out);
+}
+
+// output channels [c0, c0 + cn) of Keras weights with `ktaps` rows of Cout
+std::vector<float> weight_columns(const float* w, size_t ktaps, int Cout, int c0, int cn) {
+    std::vector<float> out(ktaps * cn);
+    for (size_t r = 0; r < ktaps; ++r) std::memcpy(&out[r * cn], w + r * Cout + c0, (size_t)cn * sizeof(float));
+    return out;
+}
+
+// node n's shape as a dense channels-last view without storage: what the kernel planners size their tiles by
+TView shape_of(const Node& n) {
+    TView v;
+    v.D = n.D; v.H = n.H; v.W = n.W; v.C = n.C;
+    v.fs = (int64_t)n.D * n.H * n.W * n.C;
+    return v;
+}
+
+ConvGeom conv_geom(const Node& c, const Node& in) {
+    ConvGeom g{};
+    g.kd = c.ip[0]; g.kh = c.ip[1]; g.kw = c.ip[2]; g.sd = c.ip[3]; g.sh = c.ip[4]; g.sw = c.ip[5];
+    g.dd = c.ip[6]; g.dh = c.ip[7]; g.dw = c.ip[8];
+    g.pz = g.py = g.px = 0;
+    if (c.ip[9]) {
+        keras_same_pad(in.D, g.kd, g.sd, g.dd, &g.pz);
+        keras_same_pad(in.H, g.kh, g.sh, g.dh, &g.py);
+        keras_same_pad(in.W, g.kw, g.sw, g.dw, &g.px);
+    }
+    return g;
 }
 
 struct ConvFusion {
@@ -539,152 +579,193 @@ struct ConvFusion {
     int last = -1;           // node whose tensor the step produces
 };
 
-int plan(th_model* m) {
-    std::vector<Node>& N = m->nodes;
-    const bool fuse = !(m->flags & (TH_LOAD_NO_FUSE | TH_LOAD_KEEP_ALL));
-    const bool use_mfma = !(m->flags & TH_LOAD_NO_MFMA);
-    const int nn = (int)N.size();
+// the kernel family that runs a Conv3D / Dense layer
+enum class Kern { None, Wino, WfSplit, Wf, First5, First, Pointwise, Gl, Mfma, Direct, DenseGemm, Dense };
 
-    // ---------------- pass 1: fusion decisions (symbolic) ----------------------------------------
-    std::map<int, ConvFusion> fus;
-    std::map<int, ConvMfmaPlan> mplans;
-    auto geom_of = [&](const Node& c, const Node& in) {
-        ConvGeom g{};
-        g.kd = c.ip[0]; g.kh = c.ip[1]; g.kw = c.ip[2]; g.sd = c.ip[3]; g.sh = c.ip[4]; g.sw = c.ip[5];
-        g.dd = c.ip[6]; g.dh = c.ip[7]; g.dw = c.ip[8];
-        g.pz = g.py = g.px = 0;
-        if (c.ip[9]) {
-            keras_same_pad(in.D, g.kd, g.sd, g.dd, &g.pz);
-            keras_same_pad(in.H, g.kh, g.sh, g.dh, &g.py);
-            keras_same_pad(in.W, g.kw, g.sw, g.dw, &g.px);
+// one Conv3D / Dense step: what it absorbs, and the kernel that runs it — decided once, read by every pass after the decision
+struct LayerPlan {
+    ConvFusion f;
+    ConvGeom g{};                 // Conv3D: the geometry on the input it reads (f.src)
+    Kern family = Kern::None;     // fusion pass: First5 / First / Pointwise / Mfma with `mp` (None: no MFMA-family plan)
+    ConvMfmaPlan mp;
+    bool wf = false;              // conv_wfused serves the layer, with `wfp`
+    ConvWfPlan wfp;
+    Kern kind = Kern::None;       // what runs it (choose_kernel)
+    ConvWinoPlan wp;              // Wino
+    ConvWfsPlan sp;               // WfSplit
+    bool b3 = false;              // First: on the bf16 pipe with split operands (conv_first_b3.hip)
+    bool tailed = false;          // Mfma: the last Cout block, from channel `cout_main` on, runs on the narrower `tp`
+    ConvMfmaPlan tp;
+    int cout_main = 0;
+    PostOps po;                   // the layer's own activation + the absorbed elementwise chain
+    PreOp pre;                    // the absorbed BN -> activation in front of a convolution
+    bool split_softmax = false;   // activation='softmax': a softmax step of its own after the layer
+};
+
+// the minimal-filtering and split-operand forms: what the load-time guard checks against a direct plan
+bool fast_form(const LayerPlan& L) {
+    return L.kind == Kern::Wino || L.kind == Kern::Wf || L.kind == Kern::WfSplit || L.kind == Kern::First5 ||
+           (L.kind == Kern::First && (L.mp.first_wino || L.b3));
+}
+
+struct Planner {
+    th_model* m;
+    std::vector<Node>& N;
+    const ThKnobs& kn;
+    const bool fuse, use_mfma;
+    std::map<int, LayerPlan> layers;   // by Conv3D / Dense node
+    std::vector<char> concat_copy;     // [i * kMaxIn + k]: input k of concat i needs an explicit copy
+    int fused_tail = -1;               // the final Softmax node when it was folded into the GlobalAveragePooling3D step
+    std::set<int> wino_in_done;        // Winograd convolutions whose input transform was fused into the previous layer's output transform
+    std::set<int> gap_done;            // GlobalAveragePooling3D nodes already computed by the output transform of the Winograd layer in front
+    std::set<int> tail_done;           // nodes computed by a k_tail_dense step ([BN / act]* -> GAP -> Dense -> Softmax in one launch)
+    explicit Planner(th_model* model)
+        : m(model), N(model->nodes), kn(model->knobs), fuse(!(model->flags & (TH_LOAD_NO_FUSE | TH_LOAD_KEEP_ALL))),
+          use_mfma(!(model->flags & TH_LOAD_NO_MFMA)), concat_copy(model->nodes.size() * kMaxIn, 0) {}
+    int pool_mode(const ConvFusion& f) const { return f.pool < 0 ? 0 : N[f.pool].op == OP_MAXPOOL ? 1 : 2; }   // 0 none, 1 max, 2 avg
+    void add_step(Step s) { m->steps.push_back(std::move(s)); }
+    int new_buffer(int64_t floats_per_frame) {
+        m->bufs.push_back(Buffer());
+        m->bufs.back().floats_per_frame = floats_per_frame;
+        return (int)m->bufs.size() - 1;
+    }
+    Step& add_step(int out_node, std::string label, double bytes, std::function<int(hipStream_t, int64_t)> run) {
+        Step s;
+        s.out_node = out_node; s.label = std::move(label); s.bytes = bytes; s.run = std::move(run);
+        m->steps.push_back(std::move(s));
+        return m->steps.back();
+    }
+};
+
+// ---------------- pass 1: fusion decisions (symbolic) ----------------------------------------------------------------------
+ConvFusion fuse_chain(const Planner& P, int i) {
+    const std::vector<Node>& N = P.N;
+    const Node& n = N[i];
+    ConvFusion f;
+    f.src = n.in[0];
+    f.last = i;
+    if (!P.fuse) return f;
+    if (n.op == OP_CONV3D) {
+        // prologue: [BN] -> [act] directly in front, each consumed only by this chain
+        int x = f.src;
+        std::vector<int> pre;
+        if (N[x].absorbed_by < 0 && N[x].op == OP_ACT && N[x].ip[0] != ACT_SOFTMAX && N[x].consumers.size() == 1) {
+            pre.push_back(x);
+            x = N[x].in[0];
         }
-        return g;
-    };
-    for (int i = 0; i < nn; ++i) {
+        if (N[x].absorbed_by < 0 && N[x].op == OP_BN && N[x].consumers.size() == 1 && (pre.empty() || N[pre.back()].in[0] == x)) {
+            pre.push_back(x);
+            x = N[x].in[0];
+        }
+        if (!pre.empty()) {
+            std::reverse(pre.begin(), pre.end());
+            f.pre = pre;
+            f.src = x;
+        }
+    }
+    // epilogue: elementwise chain with single consumers
+    int cur = i;
+    int npost = (n.op == OP_CONV3D ? n.ip[13] : n.ip[3]) != ACT_LINEAR ? 1 : 0;
+    while (N[cur].consumers.size() == 1 && cur != P.m->output_node) {
+        const int nx = N[cur].consumers[0];
+        if (!is_elementwise(N[nx]) || npost >= TH_MAX_POST) break;
+        f.post.push_back(nx);
+        ++npost;
+        cur = nx;
+    }
+    f.last = cur;
+    if (n.op == OP_CONV3D && N[cur].consumers.size() == 1 && cur != P.m->output_node) {
+        const Node& pl = N[N[cur].consumers[0]];
+        if ((pl.op == OP_MAXPOOL || pl.op == OP_AVGPOOL) && pl.ip[0] == 2 && pl.ip[1] == 2 && pl.ip[2] == 2 &&
+            pl.ip[3] == 2 && pl.ip[4] == 2 && pl.ip[5] == 2 && pl.ip[6] == 0)
+            f.pool = N[cur].consumers[0];
+    }
+    return f;
+}
+
+// the MFMA family of convolution i, in this order: first5 -> first -> pointwise -> mfma.  The fused pool is dropped when the
+// kernel that takes the layer cannot pool it.
+void choose_family(const Planner& P, int i, LayerPlan& L) {
+    ConvFusion& f = L.f;
+    const Node& n = P.N[i];
+    const Node& src = P.N[f.src];
+    const ConvGeom& g = L.g;
+    const TView iv = shape_of(src), ov = shape_of(n);
+    const int pool = P.pool_mode(f);
+    const bool stem = P.use_mfma && P.fuse && f.src == P.m->input_node && f.pre.empty();
+    ConvMfmaPlan& mp = L.mp;
+    Kern& k = L.family;
+    if (stem && pool == 1 && conv_first5_ok(src.D, src.H, src.W, src.C, n.C, g, 1, P.kn)) {
+        // ProDCoNN's 5x5x5 stem: direct form on the bf16 pipe, input split once at staging (conv_first5.hip)
+        mp = ConvMfmaPlan();
+        mp.pool = 1; mp.nnb = 1;
+        mp.knobs = &P.kn;
+        mp.exec_flops = conv_first5_exec_flops();
+        mp.label = conv_first5_label();
+        k = Kern::First5;
+    }
+    if (k == Kern::None && stem && conv_first_plan(src.D, src.H, src.W, src.C, ov, g, n.C, pool, P.kn, &mp)) k = Kern::First;
+    if (k == Kern::None && P.use_mfma && g.kd * g.kh * g.kw == 1 && conv_pw_plan(iv, ov, g, src.C, n.C, pool, P.kn, &mp))
+        k = Kern::Pointwise;
+    if (k == Kern::None && P.use_mfma) {
+        if (f.pool >= 0 && conv_mfma_plan(iv, ov, g, src.C, n.C, pool, P.kn, &mp)) k = Kern::Mfma;
+        else if (conv_mfma_plan(iv, ov, g, src.C, n.C, 0, P.kn, &mp)) { k = Kern::Mfma; f.pool = -1; }
+    }
+    if (k == Kern::None) f.pool = -1;
+}
+
+void fusion_pass(Planner& P) {
+    std::vector<Node>& N = P.N;
+    th_model* m = P.m;
+    for (int i = 0; i < (int)N.size(); ++i) {
         Node& n = N[i];
-        if (n.absorbed_by >= 0) continue;
-        if (n.op != OP_CONV3D && n.op != OP_DENSE) continue;
-        ConvFusion f;
-        f.src = n.in[0];
-        f.last = i;
-        if (fuse) {
-            if (n.op == OP_CONV3D) {
-                // prologue: [BN] -> [act] directly in front, each consumed only by this chain
-                int x = f.src;
-                std::vector<int> pre;
-                if (N[x].absorbed_by < 0 && N[x].op == OP_ACT && N[x].ip[0] != ACT_SOFTMAX && N[x].consumers.size() == 1) {
-                    pre.push_back(x);
-                    x = N[x].in[0];
-                }
-                if (N[x].absorbed_by < 0 && N[x].op == OP_BN && N[x].consumers.size() == 1 &&
-                    (pre.empty() || N[pre.back()].in[0] == x)) {
-                    pre.push_back(x);
-                    x = N[x].in[0];
-                }
-                if (!pre.empty()) {
-                    std::reverse(pre.begin(), pre.end());
-                    f.pre = pre;
-                    f.src = x;
-                }
-            }
-            // epilogue: elementwise chain with single consumers
-            int cur = i;
-            int npost = (n.op == OP_CONV3D ? n.ip[13] : n.ip[3]) != ACT_LINEAR ? 1 : 0;
-            while (N[cur].consumers.size() == 1 && cur != m->output_node) {
-                const int nx = N[cur].consumers[0];
-                if (!is_elementwise(N[nx]) || npost >= TH_MAX_POST) break;
-                f.post.push_back(nx);
-                ++npost;
-                cur = nx;
-            }
-            f.last = cur;
-            if (n.op == OP_CONV3D && N[cur].consumers.size() == 1 && cur != m->output_node) {
-                const Node& pl = N[N[cur].consumers[0]];
-                if ((pl.op == OP_MAXPOOL || pl.op == OP_AVGPOOL) && pl.ip[0] == 2 && pl.ip[1] == 2 && pl.ip[2] == 2 &&
-                    pl.ip[3] == 2 && pl.ip[4] == 2 && pl.ip[5] == 2 && pl.ip[6] == 0)
-                    f.pool = N[cur].consumers[0];
-            }
-        }
+        if (n.absorbed_by >= 0 || (n.op != OP_CONV3D && n.op != OP_DENSE)) continue;
+        LayerPlan& L = P.layers[i];
+        L.f = fuse_chain(P, i);
         if (n.op == OP_CONV3D) {
-            const Node& src = N[f.src];
-            ConvGeom g = geom_of(n, src);
-            TView iv; iv.D = src.D; iv.H = src.H; iv.W = src.W; iv.C = src.C;
-            TView ov; ov.D = n.D; ov.H = n.H; ov.W = n.W; ov.C = n.C; ov.fs = (int64_t)n.D * n.H * n.W * n.C;
-            ConvMfmaPlan mp;
-            bool ok = false;
-            if (use_mfma && fuse && f.src == m->input_node && f.pre.empty() && f.pool >= 0 && N[f.pool].op == OP_MAXPOOL &&
-                conv_first5_ok(src.D, src.H, src.W, src.C, n.C, g, 1)) {
-                // ProDCoNN's 5x5x5 stem: direct form on the bf16 pipe, input split once at staging (conv_first5.hip); cfg 101
-                mp = ConvMfmaPlan();
-                mp.cfg = 101; mp.pool = 1; mp.nnb = 1;
-                mp.knobs = &th_knobs_planning();
-                mp.exec_flops = conv_first5_exec_flops();
-                mp.label = conv_first5_label();
-                ok = true;
-            }
-            if (!ok && use_mfma && fuse && f.src == m->input_node && f.pre.empty()) {
-                if (f.pool >= 0) ok = conv_first_plan(src.D, src.H, src.W, src.C, ov, g, n.C, N[f.pool].op == OP_MAXPOOL ? 1 : 2, &mp);
-                if (!ok && f.pool < 0) ok = conv_first_plan(src.D, src.H, src.W, src.C, ov, g, n.C, 0, &mp);
-            }
-            if (!ok && use_mfma && g.kd * g.kh * g.kw == 1) {
-                if (f.pool >= 0) ok = conv_pw_plan(iv, ov, g, src.C, n.C, N[f.pool].op == OP_MAXPOOL ? 1 : 2, &mp);
-                if (!ok && f.pool < 0) ok = conv_pw_plan(iv, ov, g, src.C, n.C, 0, &mp);
-            }
-            if (!ok && use_mfma) {
-                if (f.pool >= 0) {
-                    ok = conv_mfma_plan(iv, ov, g, src.C, n.C, N[f.pool].op == OP_MAXPOOL ? 1 : 2, &mp);
-                    if (!ok) f.pool = -1;
-                }
-                if (!ok) ok = conv_mfma_plan(iv, ov, g, src.C, n.C, 0, &mp);
-            } else if (!ok) {
-                f.pool = -1;
-            }
-            if (ok) mplans[i] = mp;
-            else f.pool = -1;
+            L.g = conv_geom(n, N[L.f.src]);
+            choose_family(P, i, L);
         }
+        ConvFusion& f = L.f;
         if (f.pool >= 0) f.last = f.pool;
         for (int x : f.pre) N[x].absorbed_by = i;
         for (int x : f.post) N[x].absorbed_by = i;
         if (f.pool >= 0) N[f.pool].absorbed_by = i;
         if (f.last != i) n.absorbed_by = i;  // the conv's own raw output is never materialised
-        fus[i] = f;
     }
-    // does anything still need the converted fp32 copy of the input?
-    m->need_convert = false;
+    // does anything still need the converted fp32 copy of the input?  (the first-layer kernels read the caller's frames)
+    m->need_convert = m->output_node == m->input_node;
     for (int c : N[m->input_node].consumers) {
-        bool direct = false;
-        for (auto& kv : fus) if (kv.second.src == m->input_node && (kv.first == c) && mplans.count(kv.first) && (mplans[kv.first].cfg == 100 || mplans[kv.first].cfg == 101)) direct = true;
-        if (!direct) m->need_convert = true;
+        const auto it = P.layers.find(c);
+        if (it == P.layers.end() || it->second.f.src != m->input_node ||
+            (it->second.family != Kern::First && it->second.family != Kern::First5))
+            m->need_convert = true;
     }
-    if (m->output_node == m->input_node) m->need_convert = true;
     // which node outputs exist in memory
-    for (int i = 0; i < nn; ++i) N[i].materialised = N[i].absorbed_by < 0;
-    for (auto& kv : fus) N[kv.second.last].materialised = true;
+    for (Node& n : N) n.materialised = n.absorbed_by < 0;
+    for (auto& kv : P.layers) N[kv.second.f.last].materialised = true;
+}
 
-    // ---------------- pass 2: storage (zero-copy concat, flatten aliasing) -----------------------
-    auto new_buffer = [&](int64_t fpf) {
-        Buffer b;
-        b.floats_per_frame = fpf;
-        m->bufs.push_back(b);
-        return (int)m->bufs.size() - 1;
-    };
-    std::vector<char> concat_copy(nn * kMaxIn, 0);  // input k of concat i needs an explicit copy
+// ---------------- pass 2: storage (zero-copy concat, flatten aliasing) -------------------------------------------------------
+void storage_pass(Planner& P) {
+    std::vector<Node>& N = P.N;
+    const int nn = (int)N.size();
     for (int i = nn - 1; i >= 0; --i) {
         Node& n = N[i];
         if (n.op != OP_CONCAT) continue;
         if (n.buf < 0) {
             n.cs = n.C; n.coff = 0;
-            n.buf = new_buffer((int64_t)n.D * n.H * n.W * n.cs);
+            n.buf = P.new_buffer((int64_t)n.D * n.H * n.W * n.cs);
         }
         int off = 0;
         for (size_t k = 0; k < n.in.size(); ++k) {
             Node& a = N[n.in[k]];
-            const bool can_alias = fuse && a.buf < 0 && a.materialised && a.op != OP_INPUT && a.op != OP_FLATTEN &&
+            const bool can_alias = P.fuse && a.buf < 0 && a.materialised && a.op != OP_INPUT && a.op != OP_FLATTEN &&
                                    a.op != OP_IDENTITY;
             if (can_alias) {
                 a.buf = n.buf; a.cs = n.cs; a.coff = n.coff + off;
             } else {
-                concat_copy[i * kMaxIn + k] = 1;
+                P.concat_copy[i * kMaxIn + k] = 1;
             }
             off += a.C;
         }
@@ -704,628 +785,657 @@ int plan(th_model* m) {
         if (n.op == OP_INPUT) {
             bool all_conv = !n.consumers.empty();
             for (int c : n.consumers) if (N[c].op != OP_CONV3D) all_conv = false;
-            if (all_conv && fuse) n.cs = (n.C + 3) / 4 * 4;  // 16-byte voxel rows for the conv staging loads
+            if (all_conv && P.fuse) n.cs = (n.C + 3) / 4 * 4;  // 16-byte voxel rows for the conv staging loads
         }
-        n.buf = new_buffer((int64_t)n.D * n.H * n.W * n.cs);
+        n.buf = P.new_buffer((int64_t)n.D * n.H * n.W * n.cs);
     }
+}
 
-    // ---------------- pass 3: emit steps ----------------------------------------------------------
-    auto V = [&](int node) { return m->view(node); };  // NOTE: device pointers are bound at run time
-    auto add_step = [&](Step s) { m->steps.push_back(std::move(s)); };
-    th_model* M = m;
-    int fused_tail = -1;     // the final Softmax node when it was folded into the GlobalAveragePooling3D step
-    std::set<int> wino_in_done;   // Winograd convolutions whose input transform was fused into the previous layer's output transform
-    std::set<int> gap_done;       // GlobalAveragePooling3D nodes already computed by the output transform of the Winograd layer in front
-    std::set<int> tail_done;      // nodes computed by a k_tail_dense step ([BN / act]* -> GAP -> Dense -> Softmax in one launch)
-    // does convolution i run on conv_wfused.hip?  (asked twice: by the layout pre-pass below and when its step is emitted)
-    auto wf_plan_for = [&](int i, ConvWfPlan* fp) -> bool {
-        const Node& n = N[i];
-        if (n.op != OP_CONV3D || !fus.count(i) || !(M->wfused && use_mfma && fuse) || n.ip[13] == ACT_SOFTMAX) return false;
-        const ConvFusion& f = fus[i];
-        const Node& sn = N[f.src];
-        const ConvGeom g = geom_of(n, sn);
-        TView iv; iv.D = sn.D; iv.H = sn.H; iv.W = sn.W; iv.C = sn.C; iv.cs = sn.cs; iv.coff = sn.coff;
-        TView ov; ov.D = n.D; ov.H = n.H; ov.W = n.W; ov.C = n.C;
-        if (!conv_wf_view_ok(iv)) return false;
-        return conv_wf_plan(iv, ov, g, sn.C, n.C, f.pool >= 0 ? (N[f.pool].op == OP_MAXPOOL ? 1 : 2) : 0, fp);
+// ---------------- does conv_wfused serve the convolution?  (reads the storage of its input) ----------------------------------
+void wf_pass(Planner& P) {
+    if (!(P.kn.wfused && P.use_mfma && P.fuse)) return;
+    for (auto& [i, L] : P.layers) {
+        const Node& n = P.N[i];
+        if (n.op != OP_CONV3D || n.ip[13] == ACT_SOFTMAX) continue;
+        const Node& sn = P.N[L.f.src];
+        TView iv = shape_of(sn);
+        iv.cs = sn.cs; iv.coff = sn.coff;
+        L.wf = conv_wf_view_ok(iv) && conv_wf_plan(iv, shape_of(n), L.g, sn.C, n.C, P.pool_mode(L.f), P.kn, &L.wfp);
+    }
+}
+
+// ---------------- chunk-blocked layout ---------------------------------------------------------------------------------------
+// chunk-blocked storage (TView::blk) for a tensor that is written by ONE pointwise / first-layer step and read by ONE
+// conv_wfused step and by nothing else: that kernel reads 4-channel slices of whole frames, which are 16 bytes out of
+// every voxel's channel row in the channels-last form (measured: 3.8x the tensor's bytes fetched from HBM) and one
+// contiguous 16 KB run in the blocked form
+void blocked_pass(Planner& P) {
+    if (P.kn.wf_noblk) return;
+    std::vector<Node>& N = P.N;
+    for (auto& [i, L] : P.layers) {
+        if (!L.wf) continue;
+        const ConvFusion& f = L.f;
+        const int src = f.src;
+        Node& sn = N[src];
+        if (src == P.m->input_node || src == P.m->output_node || !sn.materialised || sn.buf < 0) continue;
+        if (sn.consumers.size() != 1 || sn.consumers[0] != (f.pre.empty() ? i : f.pre[0])) continue;
+        if (sn.cs != sn.C || sn.coff != 0 || sn.C % 4) continue;
+        int prod = -1, nprod = 0;
+        for (auto& kv : P.layers) if (kv.second.f.last == src) { prod = kv.first; ++nprod; }
+        if (nprod != 1) continue;
+        const LayerPlan& pp = P.layers.at(prod);
+        if (pp.wf) continue;                                        // (the producer itself runs on conv_wfused: channels-last stores only)
+        if (!((pp.family == Kern::Pointwise && pp.mp.pool == 0) || (pp.family == Kern::First && pp.mp.nnb == 1))) continue;
+        bool shared = false;                                        // nobody else may alias the buffer (Flatten / Identity views)
+        for (int k = 0; k < (int)N.size(); ++k) if (k != src && N[k].buf == sn.buf && N[k].materialised) shared = true;
+        if (shared) continue;
+        sn.blk = 4;
+    }
+}
+
+// ---------------- the kernel of every layer ----------------------------------------------------------------------------------
+// the epilogue (own activation + absorbed elementwise chain) and the prologue of layer i
+int build_epilogue(Planner& P, int i, LayerPlan& L) {
+    const Node& n = P.N[i];
+    const int own_act = n.op == OP_CONV3D ? n.ip[13] : n.ip[3];
+    int rc;
+    if (own_act == ACT_SOFTMAX) L.split_softmax = true;
+    else if (own_act != ACT_LINEAR) add_act(&L.po, own_act, n.fp[0]);
+    for (int x : L.f.post) if ((rc = add_post(P.m, &L.po, P.N[x]))) return rc < 0 ? rc : TH_EUNSUP;
+    if (P.kn.no_pool_first) L.po.monotone = 0;   // A/B comparisons and tests: keep act/BN before the max-pool
+    for (int x : L.f.pre) {
+        const Node& pn = P.N[x];
+        if (pn.op == OP_BN) { if ((rc = bn_affine(P.m, pn, &L.pre.scale, &L.pre.shift))) return rc; }
+        else { L.pre.act = pn.ip[0]; L.pre.alpha = pn.fp[0]; }
+    }
+    return TH_OK;
+}
+
+// in this order: wino -> wfs -> wf -> first5 -> first -> pointwise -> gl -> mfma -> direct.  After the chunk-blocked pass: the
+// wfs and gl kernels read `blk`.
+int choose_kernel(Planner& P, int i, LayerPlan& L) {
+    th_model* m = P.m;
+    if (int rc = build_epilogue(P, i, L)) return rc;
+    const Node& n = P.N[i];
+    const Node& sn = P.N[L.f.src];
+    if (n.op == OP_DENSE) {
+        if (sn.cs != sn.C || sn.coff != 0 || sn.D * sn.H * sn.W != 1) TH_FAIL(TH_EUNSUP, "%s: Dense needs a contiguous vector input", n.name.c_str());
+        L.kind = P.kn.dense_gemm && dense_gemm_ok(sn.C, n.C, m->bufs[sn.buf].floats_per_frame) ? Kern::DenseGemm : Kern::Dense;
+        return TH_OK;
+    }
+    const ConvGeom& g = L.g;
+    const TView iv = shape_of(sn), ov = shape_of(n);
+    const int Cin = sn.C, Cout = n.C;
+    if (P.kn.winograd && P.use_mfma && P.fuse && L.f.pool < 0 && !L.split_softmax &&
+        conv_wino_plan(iv, ov, g, Cin, Cout, P.kn.winograd == 2 ? 7 : 9, P.kn.wino_split, P.kn, &L.wp))
+        L.kind = Kern::Wino;
+    else if (L.wf && conv_wfs_plan(L.wfp, m->view(L.f.src), L.pre, P.kn, &L.sp)) L.kind = Kern::WfSplit;
+    else if (L.wf) L.kind = Kern::Wf;
+    else if (L.family == Kern::First5 || L.family == Kern::First || L.family == Kern::Pointwise) L.kind = L.family;
+    else if (conv_gl_wanted(P.kn.conv_gl, g, n.D * n.H * n.W) && L.f.pool < 0 && !sn.blk && !P.N[L.f.last].blk &&
+             (L.family == Kern::None || L.mp.bres != 3) &&          // (the 16-wide kernel keeps its layers: 42 against 62 us on DenseCPD's 2^3 ones)
+             conv_gl_ok(Cin, Cout, sn.cs, sn.coff, (int64_t)m->bufs[sn.buf].floats_per_frame))
+        L.kind = Kern::Gl;
+    else if (L.family == Kern::Mfma) {
+        L.kind = Kern::Mfma;
+        // heterogeneous Cout blocks: the last, mostly empty 128-column block on a narrower instantiation
+        L.tailed = conv_mfma_plan_tail(iv, ov, g, Cin, Cout, L.mp.pool, L.mp, P.kn, &L.tp, &L.cout_main);
+    } else L.kind = Kern::Direct;
+    // the aposteriori case (21^3 frames, pool before a monotone chain) runs on the bf16 pipe with split operands
+    if (L.kind == Kern::First) L.b3 = conv_first_b3_ok(L.mp, sn.D, sn.H, sn.W, Cin, std::min(Cout, 32), g, L.po);
+    L.mp.ncu = L.tp.ncu = L.wfp.ncu = L.sp.ncu = m->ncu;
+    return TH_OK;
+}
+
+// ---------------- emission: one emitter per kernel family --------------------------------------------------------------------
+// what a convolution's launch needs besides its plan: values only, so a step's run() may keep a copy (the device pointers of the
+// tensors are bound at run time, th_model::view)
+struct ConvArgs {
+    th_model* M;
+    int i, src, dst, Cin, Cout;
+    ConvGeom g;
+    const float* hw;       // Keras weights [kd][kh][kw][Cin][Cout], host
+    const float* bias;     // device, or nullptr
+    PreOp pre;
+    PostOps po;
+    TView in() const { return M->view(src); }
+    TView out() const { return M->view(dst); }
+    const Node& node(int k) const { return M->nodes[k]; }
+};
+
+// three or four steps, one kernel each.  `direct_flops` (the SURVEY §8d count of the direct form) stays with the GEMM step for
+// the model total; the per-step `flops` are what the kernels really compute: the GEMM's own multiply-adds, nothing for the
+// bandwidth-bound transforms (their bytes are V / M traffic)
+int emit_wino(Planner& P, const ConvArgs& c, const LayerPlan& L, Step st) {
+    th_model* M = c.M;
+    std::vector<Node>& N = P.N;
+    const ConvWinoPlan wp = L.wp;
+    float* dw;
+    if (int rc = upload_packed(M, wp.wpk_floats, [&](float* d) { conv_wino_pack_weights(wp, c.hw, d); }, &dw)) return rc;
+    if (M->wino_v_buf < 0) { M->wino_v_buf = P.new_buffer(0); M->wino_m_buf = P.new_buffer(0); }
+    int64_t& v_fpf = M->bufs[M->wino_v_buf].floats_per_frame;
+    v_fpf = std::max(v_fpf, wp.v_fpf);
+    M->bufs[M->wino_m_buf].floats_per_frame = std::max(M->bufs[M->wino_m_buf].floats_per_frame, wp.m_fpf);
+    const Node& sn = N[c.src];
+    const double direct = st.flops, act_bytes = st.bytes, in_floats = (double)sn.D * sn.H * sn.W * c.Cin, mf = (double)wp.m_fpf;
+    const std::string name = N[c.i].name, pts = std::to_string(wp.P * wp.P);
+    auto Vp = [M]() { const Buffer& b = M->bufs[M->wino_v_buf]; return b.dev + M->lane_off * b.floats_per_frame; };
+    auto Mp = [M]() { const Buffer& b = M->bufs[M->wino_m_buf]; return b.dev + M->lane_off * b.floats_per_frame; };
+    if (!P.wino_in_done.count(c.i))
+        P.add_step(st.out_node, name + ": wino_in (25 voxels -> " + pts + " points per plane) [k_wino_in]", 4.0 * (in_floats + (double)wp.v_fpf),
+                   [=](hipStream_t s, int64_t cnt) { return launch_wino_in(s, cnt, wp, c.in(), Vp(), c.pre); });
+    st.flops = wp.gemm_flops;
+    st.direct_flops = direct;
+    // split GEMM: six bf16 piece products per fp32 multiply-add — what the bf16 matrix pipe issues
+    st.exec_flops = wp.split ? 6.0 * wp.exec_flops : wp.exec_flops;
+    st.bytes = 4.0 * ((double)wp.v_fpf + mf);
+    st.label = name + ": " + wp.label + (wp.narrow ? " [k_wino_gemm_n32]" : wp.split ? " [k_wino_gemm_b3]" : " [k_wino_gemm]");
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_wino_gemm(s, cnt, wp, Vp(), Mp(), dw); };
+    P.add_step(st);
+    const int dst = c.dst, Cout = c.Cout;
+    // two Winograd layers in a row and nobody else reads the tensor between them: this layer's output transform feeds the
+    // next layer's V directly (k_wino_mid) and the 5^3 activation is never written
+    if (!P.kn.wino_nomid && dst != M->output_node && N[dst].consumers.size() == 1) {
+        const int next = N[dst].consumers[0];
+        const auto it = P.layers.find(next);
+        const LayerPlan* nl = it == P.layers.end() ? nullptr : &it->second;
+        if (nl && nl->kind == Kern::Wino && nl->f.src == dst && nl->f.pre.empty() && nl->wp.Cin == Cout) {
+            v_fpf = std::max(v_fpf, nl->wp.v_fpf);
+            P.add_step(st.out_node, name + ": wino_mid (" + pts + " points -> bias + epilogue -> " + pts + " points of " + N[next].name + ") [k_wino_mid]",
+                       4.0 * (mf / wp.Coutp * Cout + (double)nl->wp.v_fpf),
+                       [=](hipStream_t s, int64_t cnt) { return launch_wino_mid(s, cnt, wp, Mp(), Vp(), c.bias, c.po); });
+            P.wino_in_done.insert(next);
+            N[dst].materialised = false;        // th_model_fetch refuses it ("fused away")
+            return TH_OK;
+        }
+    }
+    // the layer's only reader is a GlobalAveragePooling3D (TIMED's 338-class head): the output transform pools
+    // (k_wino_out<P, true>), neither the 5^3 activation nor the pooling kernel's pass over it exist
+    int gp = -1;
+    if (!P.kn.no_tail_fuse && dst != M->output_node) {
+        int cur = dst;
+        while (N[cur].consumers.size() == 1 && N[N[cur].consumers[0]].op == OP_IDENTITY && N[cur].consumers[0] != M->output_node)
+            cur = N[cur].consumers[0];
+        if (N[cur].consumers.size() == 1 && N[N[cur].consumers[0]].op == OP_GAP && N[N[cur].consumers[0]].materialised &&
+            N[N[cur].consumers[0]].absorbed_by < 0) {
+            bool single = true;          // every node of the chain has exactly one reader
+            for (int k = dst; k != cur; k = N[k].consumers[0]) if (N[k].consumers.size() != 1) single = false;
+            if (single) gp = N[cur].consumers[0];
+        }
+    }
+    if (gp >= 0) {
+        P.add_step(gp, name + ": wino_out + global_avg_pool (" + pts + " points -> bias + epilogue -> mean of the 125 voxels) [k_wino_out]",
+                   4.0 * (mf / wp.Coutp * Cout + Cout),
+                   [=](hipStream_t s, int64_t cnt) { return launch_wino_out(s, cnt, wp, Mp(), M->view(gp), c.bias, c.po, true); });
+        for (int k = dst; ; k = N[k].consumers[0]) { N[k].materialised = false; if (N[k].consumers[0] == gp) break; }
+        P.gap_done.insert(gp);
+        return TH_OK;
+    }
+    P.add_step(st.out_node, name + ": wino_out (" + pts + " points -> 25 voxels per plane, bias + epilogue) [k_wino_out]",
+               4.0 * (mf / wp.Coutp * Cout + (act_bytes / 4.0 - in_floats)),
+               [=](hipStream_t s, int64_t cnt) { return launch_wino_out(s, cnt, wp, Mp(), c.out(), c.bias, c.po); });
+    return TH_OK;
+}
+
+// the step's label: the layer's name, then the kernel's, with a remark when a tensor of the step is chunk-blocked
+std::string conv_label(const ConvArgs& c, const std::string& kernel, bool in_blk, bool out_blk) {
+    const std::string l = c.node(c.i).name + ": " + kernel;
+    return in_blk ? label_note(l, " (input chunk-blocked)") : out_blk ? label_note(l, " (output chunk-blocked)") : l;
+}
+
+// the same algorithm as conv_wf on the bf16 pipe: both operands split exactly into three bf16 pieces (conv_wfsplit.hip)
+int emit_wfs(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    const ConvWfsPlan sp = L.sp;
+    float* dw;
+    if (int rc = upload_packed(c.M, sp.wpk_floats, [&](float* d) { conv_wfs_pack_weights(sp, c.hw, d); }, &dw)) return rc;
+    st.direct_flops = st.flops;
+    st.flops = sp.own_flops;
+    st.exec_flops = sp.exec_flops;
+    st.label = conv_label(c, sp.label, c.node(c.src).blk, false);
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_wfs(s, cnt, sp, c.in(), c.out(), dw, c.bias, c.po); };
+    return TH_OK;
+}
+
+// F(2,3)^2 in-plane with the whole transform domain in LDS: one step, one kernel (conv_wfused.hip)
+int emit_wf(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    const ConvWfPlan fp = L.wfp;
+    float* dw;
+    if (int rc = upload_packed(c.M, fp.wpk_floats, [&](float* d) { conv_wf_pack_weights(fp, c.hw, d); }, &dw)) return rc;
+    st.direct_flops = st.flops;
+    st.flops = fp.own_flops;
+    st.exec_flops = fp.exec_flops;
+    st.label = conv_label(c, conv_wf_label(fp, c.pre), c.node(c.src).blk, false);
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_wf(s, cnt, fp, c.in(), c.out(), dw, c.bias, c.pre, c.po); };
+    return TH_OK;
+}
+
+int emit_first5(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    float* dw;
+    if (int rc = upload_packed(c.M, conv_first5_wpk_floats(), [&](float* d) { conv_first5_pack_weights(c.Cin, c.Cout, c.hw, d); }, &dw))
+        return rc;
+    st.exec_flops = L.mp.exec_flops;
+    st.label = conv_label(c, L.mp.label, false, false);
+    const ThKnobs* kn = L.mp.knobs;
+    st.run = [=](hipStream_t s, int64_t cnt) {
+        return launch_conv_first5(s, cnt, kn, c.M->ncu, c.M->cur_in, c.M->cur_dtype, c.Cin, c.out(), c.Cout, dw, c.bias, c.po);
     };
-    // chunk-blocked storage (TView::blk) for a tensor that is written by ONE pointwise / first-layer step and read by ONE
-    // conv_wfused step and by nothing else: that kernel reads 4-channel slices of whole frames, which are 16 bytes out of
-    // every voxel's channel row in the channels-last form (measured: 3.8x the tensor's bytes fetched from HBM) and one
-    // contiguous 16 KB run in the blocked form
-    if (!M->knobs.wf_noblk)
-        for (int i = 0; i < nn; ++i) {
-            ConvWfPlan fp;
-            if (!(fus.count(i) || N[i].absorbed_by < 0) || !wf_plan_for(i, &fp)) continue;
-            const ConvFusion& f = fus[i];
-            const int src = f.src;
-            Node& sn = N[src];
-            if (src == M->input_node || src == M->output_node || !sn.materialised || sn.buf < 0) continue;
-            if (sn.consumers.size() != 1 || sn.consumers[0] != (f.pre.empty() ? i : f.pre[0])) continue;
-            if (sn.cs != sn.C || sn.coff != 0 || sn.C % 4) continue;
-            int prod = -1, nprod = 0;
-            for (auto& kv : fus) if (kv.second.last == src) { prod = kv.first; ++nprod; }
-            if (nprod != 1 || N[prod].op != OP_CONV3D || !mplans.count(prod)) continue;
-            const ConvMfmaPlan& pp = mplans[prod];
-            ConvWfPlan dummy;
-            if (wf_plan_for(prod, &dummy)) continue;                    // (the producer itself runs on conv_wfused: channels-last stores only)
-            if (!((pp.cfg >= 300 && pp.pool == 0) || (pp.cfg == 100 && pp.nnb == 1))) continue;
-            bool shared = false;                                        // nobody else may alias the buffer (Flatten / Identity views)
-            for (int k = 0; k < nn; ++k) if (k != src && N[k].buf == sn.buf && N[k].materialised) shared = true;
-            if (shared) continue;
-            sn.blk = 4;
+    return TH_OK;
+}
+
+// the first layer on the caller's frames (conv_first.hip, conv_first_b3.hip): one launch per block of 32 output channels, each
+// with its own weight columns, bias and per-channel epilogue vectors
+int emit_first(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    const ConvMfmaPlan mp = L.mp;
+    const bool b3 = L.b3;
+    if (mp.first_wino) {
+        st.direct_flops = st.flops;
+        st.flops = mp.own_flops;
+    }
+    st.exec_flops = b3 ? conv_first_b3_exec_flops() * mp.nnb : mp.exec_flops;
+    st.label = conv_label(c, b3 ? conv_first_b3_label(mp.nnb) : conv_first_label(mp, c.Cin, c.po), false, c.node(c.dst).blk);
+    if (mp.nnb > 1) st.label = label_note(st.label, (" x" + std::to_string(mp.nnb) + " passes of 32 columns").c_str());
+    struct Pass { int c0, cn; float* dw; const float* bias; PostOps po; };
+    std::vector<Pass> passes;
+    const size_t ktaps = (size_t)c.g.kd * c.g.kh * c.g.kw * c.Cin;
+    for (int c0 = 0; c0 < c.Cout; c0 += 32) {
+        Pass ps{c0, std::min(32, c.Cout - c0), nullptr, c.bias ? c.bias + c0 : nullptr, post_from(c.po, c0)};
+        const std::vector<float> wcol = weight_columns(c.hw, ktaps, c.Cout, c0, ps.cn);
+        const int rc = upload_packed(c.M, b3 ? conv_first_b3_wpk_floats() : mp.wpk_floats, [&](float* d) {
+            if (b3) conv_first_b3_pack_weights(c.Cin, ps.cn, wcol.data(), d);
+            else if (mp.first_wino) conv_first_w_pack_weights(c.Cin, ps.cn, wcol.data(), d);
+            else conv_first_pack_weights(c.Cin, ps.cn, wcol.data(), d);
+        }, &ps.dw);
+        if (rc) return rc;
+        passes.push_back(ps);
+    }
+    const Node& sn = c.node(c.src);
+    const int iD = sn.D, iH = sn.H, iW = sn.W;
+    st.run = [=](hipStream_t s, int64_t cnt) {
+        for (const Pass& ps : passes) {
+            TView ov = c.out();
+            if (passes.size() > 1) { ov.coff += ps.c0; ov.C = ps.cn; }
+            th_model* M = c.M;
+            const int r = b3 ? launch_conv_first_b3(s, cnt, mp, M->cur_in, M->cur_dtype, c.Cin, ov, ps.cn, ps.dw, ps.bias, ps.po)
+                             : launch_conv_first(s, cnt, mp, M->cur_in, M->cur_dtype, iD, iH, iW, c.Cin, ov, c.g, ps.cn, ps.dw, ps.bias, ps.po);
+            if (r) return r;
         }
-    // DenseCPD's tail [BatchNormalization / activation]* -> GlobalAveragePooling3D -> Dense -> Softmax (the model output) as ONE
-    // launch, one wavefront per frame (k_tail_dense).  Called at the first node of the chain; fills *st and returns 1 when the
-    // pattern holds (0: no, < 0: error).  The pooled vector and the logits are still written to their nodes' buffers; the
-    // elementwise nodes in front of the pooling are fused away.
-    auto try_dense_tail = [&](int first, Step* st) -> int {
-        if (!fuse || M->knobs.no_tail_fuse) return 0;
-        std::vector<int> chain;
-        int j = first;
-        while ((N[j].op == OP_BN || (N[j].op == OP_ACT && N[j].ip[0] != ACT_SOFTMAX)) && (int)chain.size() < TH_MAX_POST) {
-            if (N[j].absorbed_by >= 0 || !N[j].materialised || N[j].consumers.size() != 1 || j == M->output_node) return 0;
-            chain.push_back(j);
-            j = N[j].consumers[0];
-        }
-        const int gp = j;
-        if (N[gp].op != OP_GAP || gap_done.count(gp) || N[gp].absorbed_by >= 0 || !N[gp].materialised || N[gp].consumers.size() != 1 ||
-            gp == M->output_node || N[gp].C > 2048)
-            return 0;
-        const int dn = N[gp].consumers[0];
-        if (N[dn].op != OP_DENSE || !fus.count(dn) || N[dn].C > 512 || N[dn].w[0] < 0) return 0;
-        const ConvFusion& f = fus[dn];
-        if (f.src != gp || !f.pre.empty() || !f.post.empty() || f.pool >= 0 || f.last != dn || !N[dn].materialised) return 0;
-        const int own_act = N[dn].ip[3];
-        int sm = -1;                                         // node that holds the probabilities
-        // (Dense(activation='softmax') keeps its two steps: logits and probabilities share the node there, and a TH_PREDICT_LOGITS
-        // call drops the in-place softmax step)
-        if (own_act == ACT_LINEAR) {
-            if (dn == M->output_node || N[dn].consumers.size() != 1) return 0;
-            sm = N[dn].consumers[0];
-            if (!(N[sm].op == OP_ACT && N[sm].ip[0] == ACT_SOFTMAX && sm == M->output_node && N[sm].absorbed_by < 0 && N[sm].materialised)) return 0;
-        } else return 0;
-        const int src = N[chain.empty() ? gp : chain[0]].in[0];
-        if (N[src].blk || !N[src].materialised || N[src].buf < 0) return 0;
-        const Node& gn = N[gp];
-        if (gn.cs != gn.C || gn.coff != 0) return 0;         // k_dense's contract: a contiguous feature vector
-        PostOps pre, post;
-        int rc;
-        for (int x : chain) if ((rc = add_post(M, &pre, N[x]))) return rc < 0 ? rc : 0;
-        const int F = gn.C, O = N[dn].C;
-        if (M->blob_count[N[dn].w[0]] != (size_t)F * O) return 0;   // (the Dense case reports the mismatch)
-        float *dw = nullptr, *dbias = nullptr;
-        if ((rc = upload(M, M->blob_host[N[dn].w[0]], (size_t)F * O, &dw))) return rc;
-        if (N[dn].ip[2]) {
-            if (N[dn].w[1] < 0) return 0;
-            if ((rc = upload(M, M->blob_host[N[dn].w[1]], M->blob_count[N[dn].w[1]], &dbias))) return rc;
-        }
-        const int V = N[src].D * N[src].H * N[src].W;
-        st->out_node = sm;
-        st->flops = st->exec_flops = 2.0 * F * O;
-        st->bytes = 4.0 * ((double)V * N[src].C + F + 2.0 * O);
-        st->label = N[first].name + ": " + (chain.empty() ? "" : std::to_string(chain.size()) + " elementwise + ") +
-                    "global_avg_pool + dense + softmax [k_tail_dense]";
-        st->run = [=](hipStream_t s, int64_t cnt) {
-            return launch_tail_dense(s, cnt, M->view(src), pre, M->view(gp), M->view(dn), M->view(sm), dw, dbias, post, 1);
-        };
-        M->logits_node = dn;
-        for (int x : chain) { tail_done.insert(x); N[x].materialised = false; }   // th_model_fetch refuses them ("fused away")
-        tail_done.insert(gp); tail_done.insert(dn); tail_done.insert(sm);
-        tail_done.erase(first);
-        return 1;
+        return (int)TH_OK;
     };
-    for (int i = 0; i < nn; ++i) {
-        Node& n = N[i];
-        const bool emits = fus.count(i) || n.absorbed_by < 0;
-        if (!emits) continue;
-        if (tail_done.count(i)) continue;
-        Step st;
-        st.out_node = i;
-        switch (n.op) {
-            case OP_INPUT: {
-                // the convert step is issued by predict() itself (it needs the caller's pointer/dtype)
-                continue;
-            }
-            case OP_CONV3D:
-            case OP_DENSE: {
-                const ConvFusion& f = fus[i];
-                st.out_node = f.last;
+    return TH_OK;
+}
+
+int emit_pointwise(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    const ConvMfmaPlan mp = L.mp;
+    float* dw;
+    if (int rc = upload_packed(c.M, mp.wpk_floats, [&](float* d) { conv_pw_pack_weights(mp, c.Cin, c.Cout, c.hw, d); }, &dw)) return rc;
+    const bool blk = c.node(c.dst).blk != 0;
+    st.exec_flops = mp.exec_flops;
+    st.label = conv_label(c, conv_pw_label(mp, blk, c.po), false, blk);
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_pw(s, cnt, mp, c.in(), c.out(), c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
+    return TH_OK;
+}
+
+// strided / few-outputs-per-frame layers: implicit GEMM with rows across the batch, operands from L2 (conv_gl.hip)
+int emit_gl(const ConvArgs& c, Step& st) {
+    float* dw;
+    const size_t floats = conv_gl_wpk_floats(c.g, c.Cin, c.Cout);
+    if (int rc = upload_packed(c.M, floats, [&](float* d) { conv_gl_pack_weights(c.g, c.Cin, c.Cout, c.hw, d); }, &dw)) return rc;
+    const Node& n = c.node(c.i);
+    st.exec_flops = conv_gl_exec_flops(c.g, c.Cin, c.Cout, n.D * n.H * n.W);
+    st.label = conv_label(c, conv_gl_label(c.Cout), false, false);
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_gl(s, cnt, c.in(), c.out(), c.g, c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
+    return TH_OK;
+}
+
+int emit_mfma(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    ConvMfmaPlan mp = L.mp;
+    float *dw, *dwt;
+    int rc;
+    if (!L.tailed) {
+        if ((rc = upload_packed(c.M, mp.wpk_floats, [&](float* d) { conv_mfma_pack_weights(mp, c.g, c.Cin, c.Cout, c.hw, d); }, &dw))) return rc;
+        st.exec_flops = mp.exec_flops;
+        st.label = conv_label(c, mp.label, false, false);
+        st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_mfma(s, cnt, mp, c.in(), c.out(), c.g, c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
+        return TH_OK;
+    }
+    // the last Cout block on the narrower `tp`: output channels [cout_main, Cout)
+    const ConvMfmaPlan tp = L.tp;
+    const int cout_main = L.cout_main, cout_tail = c.Cout - cout_main;
+    const size_t ktaps = (size_t)c.g.kd * c.g.kh * c.g.kw * c.Cin;
+    const std::vector<float> wm = weight_columns(c.hw, ktaps, c.Cout, 0, cout_main), wt = weight_columns(c.hw, ktaps, c.Cout, cout_main, cout_tail);
+    mp.nnb -= 1;
+    mp.exec_flops *= (double)mp.nnb / (mp.nnb + 1);
+    mp.wpk_floats = mp.wpk_floats / (mp.nnb + 1) * mp.nnb;
+    if ((rc = upload_packed(c.M, mp.wpk_floats, [&](float* d) { conv_mfma_pack_weights(mp, c.g, c.Cin, cout_main, wm.data(), d); }, &dw)) ||
+        (rc = upload_packed(c.M, tp.wpk_floats, [&](float* d) { conv_mfma_pack_weights(tp, c.g, c.Cin, cout_tail, wt.data(), d); }, &dwt)))
+        return rc;
+    const PostOps pot = post_from(c.po, cout_main);
+    const float* bias_t = c.bias ? c.bias + cout_main : nullptr;
+    st.exec_flops = mp.exec_flops + tp.exec_flops;
+    st.label = conv_label(c, mp.label + " x" + std::to_string(mp.nnb) + " + " + tp.label, false, false);
+    st.run = [=](hipStream_t s, int64_t cnt) {
+        int r1 = launch_conv_mfma(s, cnt, mp, c.in(), c.out(), c.g, c.Cin, cout_main, dw, c.bias, c.pre, c.po);
+        if (r1) return r1;
+        TView ot = c.out();
+        ot.coff += cout_main;
+        return launch_conv_mfma(s, cnt, tp, c.in(), ot, c.g, c.Cin, cout_tail, dwt, bias_t, c.pre, pot);
+    };
+    return TH_OK;
+}
+
+int emit_direct(const ConvArgs& c, Step& st) {
+    float* dw;
+    if (int rc = upload(c.M, c.hw, (size_t)c.g.kd * c.g.kh * c.g.kw * c.Cin * c.Cout, &dw)) return rc;
+    st.exec_flops = st.flops;
+    st.label = conv_label(c, "conv3d_direct", false, false);
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv3d_direct(s, cnt, c.in(), c.out(), c.g, dw, c.bias, c.pre, c.po); };
+    return TH_OK;
+}
+
+int emit_dense(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    const int F = c.Cin, O = c.Cout;
+    if (c.M->blob_count[c.node(c.i).w[0]] != (size_t)F * O) TH_FAIL(TH_EIO, "%s: kernel size mismatch", c.node(c.i).name.c_str());
+    float* dw;
+    if (int rc = upload(c.M, c.hw, (size_t)F * O, &dw)) return rc;
+    st.flops = st.exec_flops = 2.0 * F * O;
+    st.bytes = 4.0 * (F + O);
+    if (L.kind == Kern::DenseGemm) {
+        st.label = conv_label(c, "dense as a batch GEMM, 16 frames x all outputs per workgroup, F in four quarters (16x16x4 fp32 MFMA) [k_dense_gemm]",
+                              false, false);
+        st.run = [=](hipStream_t s, int64_t cnt) { return launch_dense_gemm(s, cnt, c.in(), c.out(), dw, c.bias, c.po); };
+    } else {
+        st.label = conv_label(c, "dense", false, false);
+        st.run = [=](hipStream_t s, int64_t cnt) { return launch_dense(s, cnt, c.in(), c.out(), dw, c.bias, c.po); };
+    }
+    return TH_OK;
+}
+
+// a 3x3x3 stride-1 layer that stays on a direct kernel says why no minimal-filtering form took it (tools/plan_report.py)
+void note_direct_form(const Planner& P, const ConvArgs& c, const LayerPlan& L, Step& st) {
+    const ConvGeom& g = c.g;
+    const Node& sn = c.node(c.src);
+    const bool k333 = g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.dd == 1 && g.dh == 1 && g.dw == 1;
+    if (!k333 || fast_form(L)) return;
+    std::string why;
+    const bool same = g.pz == 1 && g.py == 1 && g.px == 1;
+    if (!P.use_mfma || !P.fuse) why = "load flags select the direct kernels";
+    else if (!same) why = "'valid' padding (the Cook-Toom forms are built for 'same')";
+    else if (c.src == P.m->input_node && sn.C <= 8 && c.Cout <= 32) why = P.kn.first_wino ? "odd computed width" : "TH_FIRST_WINO=0";
+    else if (sn.D == 5 && sn.H == 5 && sn.W == 5) {
+        if (!P.kn.winograd) why = "TH_WINOGRAD=0";
+        else if (L.f.pool >= 0) why = "a pooling layer is fused behind it";
+        else if (sn.C < 32) why = "Cin < 32";
+        else if (c.Cout < 64) why = "Cout < 64 (a 128-column GEMM block would run mostly empty)";
+        else why = "softmax fused into the layer";
+    } else if (sn.H % 2 == 0 && sn.W % 2 == 0 && sn.D * (sn.H / 2) * (sn.W / 2) <= 250) {
+        if (!P.kn.wfused) why = "TH_WFUSED=0";
+        else if (sn.C < 16 || sn.C % 4) why = "Cin < 16 or not a multiple of 4";
+        else if (!(sn.D == 10 && sn.H == 10 && sn.W == 10)) why = "conv_wf is instantiated for 10^3 volumes only";
+        else why = "input view is not 16-byte aligned";
+    } else why = "no minimal-filtering kernel for a " + std::to_string(sn.D) + "x" + std::to_string(sn.H) + "x" + std::to_string(sn.W) +
+                 " volume (conv_wf: 10^3, conv_wino: 5^3)";
+    st.label = label_note(st.label, (" (direct form: " + why + ")").c_str());
+}
+
+// the step(s) of Conv3D / Dense layer i
+int emit_layer(Planner& P, int i) {
+    th_model* M = P.m;
+    const Node& n = P.N[i];
+    const LayerPlan& L = P.layers.at(i);
+    const Node& sn = P.N[L.f.src];
+    const Node& dn = P.N[L.f.last];
+    const float* hw = n.w[0] >= 0 ? M->blob_host[n.w[0]] : nullptr;
+    if (!hw) TH_FAIL(TH_EIO, "%s: missing kernel", n.name.c_str());
+    float* bias = nullptr;
+    int rc = TH_OK;
+    if ((n.op == OP_CONV3D ? n.ip[12] : n.ip[2]) != 0) {
+        if (n.w[1] < 0) TH_FAIL(TH_EIO, "%s: missing bias", n.name.c_str());
+        if ((rc = upload(M, M->blob_host[n.w[1]], M->blob_count[n.w[1]], &bias))) return rc;
+    }
+    const ConvGeom& g = L.g;
+    const ConvArgs c{M, i, L.f.src, L.f.last, sn.C, n.C, g, hw, bias, L.pre, L.po};
+    Step st;
+    st.out_node = c.dst;
+    st.fast = fast_form(L);
+    if (n.op == OP_CONV3D) {
+        if (M->blob_count[n.w[0]] != (size_t)g.kd * g.kh * g.kw * c.Cin * c.Cout) TH_FAIL(TH_EIO, "%s: kernel size mismatch", n.name.c_str());
+        st.flops = 2.0 * n.D * n.H * n.W * (double)g.kd * g.kh * g.kw * c.Cin * c.Cout;
+        st.bytes = 4.0 * ((double)sn.D * sn.H * sn.W * c.Cin + (double)dn.D * dn.H * dn.W * dn.C);
+    }
+    switch (L.kind) {
+        case Kern::Wino: return emit_wino(P, c, L, st);
+        case Kern::WfSplit: rc = emit_wfs(c, L, st); break;
+        case Kern::Wf: rc = emit_wf(c, L, st); break;
+        case Kern::First5: rc = emit_first5(c, L, st); break;
+        case Kern::First: rc = emit_first(c, L, st); break;
+        case Kern::Pointwise: rc = emit_pointwise(c, L, st); break;
+        case Kern::Gl: rc = emit_gl(c, st); break;
+        case Kern::Mfma: rc = emit_mfma(c, L, st); break;
+        case Kern::DenseGemm: case Kern::Dense: rc = emit_dense(c, L, st); break;
+        default: rc = emit_direct(c, st); break;
+    }
+    if (rc) return rc;
+    if (n.op == OP_CONV3D) note_direct_form(P, c, L, st);
+    P.add_step(st);
+    if (L.split_softmax) {
+        const bool final_softmax = c.dst == M->output_node;
+        P.add_step(c.dst, n.name + ": softmax (layer activation)", 0,
+                   [=](hipStream_t s, int64_t cnt) { return launch_softmax(s, cnt, c.out(), c.out()); }).is_final_softmax = final_softmax;
+        if (final_softmax) M->logits_node = c.dst;
+    }
+    return TH_OK;
+}
+
+// DenseCPD's tail [BatchNormalization / activation]* -> GlobalAveragePooling3D -> Dense -> Softmax (the model output) as ONE
+// launch, one wavefront per frame (k_tail_dense).  Called at the first node of the chain; fills *st and returns 1 when the
+// pattern holds (0: no, < 0: error).  The pooled vector and the logits are still written to their nodes' buffers; the
+// elementwise nodes in front of the pooling are fused away.
+int try_dense_tail(Planner& P, int first, Step* st) {
+    th_model* M = P.m;
+    std::vector<Node>& N = P.N;
+    if (!P.fuse || P.kn.no_tail_fuse) return 0;
+    std::vector<int> chain;
+    int j = first;
+    while ((N[j].op == OP_BN || (N[j].op == OP_ACT && N[j].ip[0] != ACT_SOFTMAX)) && (int)chain.size() < TH_MAX_POST) {
+        if (N[j].absorbed_by >= 0 || !N[j].materialised || N[j].consumers.size() != 1 || j == M->output_node) return 0;
+        chain.push_back(j);
+        j = N[j].consumers[0];
+    }
+    const int gp = j;
+    if (N[gp].op != OP_GAP || P.gap_done.count(gp) || N[gp].absorbed_by >= 0 || !N[gp].materialised || N[gp].consumers.size() != 1 ||
+        gp == M->output_node || N[gp].C > 2048)
+        return 0;
+    const int dn = N[gp].consumers[0];
+    if (N[dn].op != OP_DENSE || !P.layers.count(dn) || N[dn].C > 512 || N[dn].w[0] < 0) return 0;
+    const ConvFusion& f = P.layers.at(dn).f;
+    if (f.src != gp || !f.pre.empty() || !f.post.empty() || f.pool >= 0 || f.last != dn || !N[dn].materialised) return 0;
+    // (Dense(activation='softmax') keeps its two steps: logits and probabilities share the node there, and a TH_PREDICT_LOGITS
+    // call drops the in-place softmax step)
+    if (N[dn].ip[3] != ACT_LINEAR || dn == M->output_node || N[dn].consumers.size() != 1) return 0;
+    const int sm = N[dn].consumers[0];                  // node that holds the probabilities
+    if (!(N[sm].op == OP_ACT && N[sm].ip[0] == ACT_SOFTMAX && sm == M->output_node && N[sm].absorbed_by < 0 && N[sm].materialised)) return 0;
+    const int src = N[chain.empty() ? gp : chain[0]].in[0];
+    if (N[src].blk || !N[src].materialised || N[src].buf < 0) return 0;
+    const Node& gn = N[gp];
+    if (gn.cs != gn.C || gn.coff != 0) return 0;         // k_dense's contract: a contiguous feature vector
+    PostOps pre, post;
+    int rc;
+    for (int x : chain) if ((rc = add_post(M, &pre, N[x]))) return rc < 0 ? rc : 0;
+    const int F = gn.C, O = N[dn].C;
+    if (M->blob_count[N[dn].w[0]] != (size_t)F * O) return 0;   // (the Dense case reports the mismatch)
+    float *dw = nullptr, *dbias = nullptr;
+    if ((rc = upload(M, M->blob_host[N[dn].w[0]], (size_t)F * O, &dw))) return rc;
+    if (N[dn].ip[2]) {
+        if (N[dn].w[1] < 0) return 0;
+        if ((rc = upload(M, M->blob_host[N[dn].w[1]], M->blob_count[N[dn].w[1]], &dbias))) return rc;
+    }
+    const int V = N[src].D * N[src].H * N[src].W;
+    st->out_node = sm;
+    st->flops = st->exec_flops = 2.0 * F * O;
+    st->bytes = 4.0 * ((double)V * N[src].C + F + 2.0 * O);
+    st->label = N[first].name + ": " + (chain.empty() ? "" : std::to_string(chain.size()) + " elementwise + ") +
+                "global_avg_pool + dense + softmax [k_tail_dense]";
+    st->run = [=](hipStream_t s, int64_t cnt) {
+        return launch_tail_dense(s, cnt, M->view(src), pre, M->view(gp), M->view(dn), M->view(sm), dw, dbias, post, 1);
+    };
+    M->logits_node = dn;
+    for (int x : chain) { P.tail_done.insert(x); N[x].materialised = false; }   // th_model_fetch refuses them ("fused away")
+    P.tail_done.insert(gp); P.tail_done.insert(dn); P.tail_done.insert(sm);
+    P.tail_done.erase(first);
+    return 1;
+}
+
+// GlobalAveragePooling3D / GlobalMaxPooling3D node i, with the tails fused into it
+int emit_global_pool(Planner& P, int i) {
+    th_model* M = P.m;
+    std::vector<Node>& N = P.N;
+    const Node& n = N[i];
+    const int src = n.in[0];
+    const int is_max = n.op == OP_GMP;
+    // the model's final softmax right behind the pooling, when it is nothing else's input
+    const int sm = n.consumers.size() == 1 ? n.consumers[0] : -1;
+    const bool softmax_out = sm >= 0 && N[sm].op == OP_ACT && N[sm].ip[0] == ACT_SOFTMAX && sm == M->output_node && N[sm].absorbed_by < 0 &&
+                             N[sm].materialised;
+    Step st;
+    st.out_node = i;
+    if (P.gap_done.count(i)) {
+        // pooled by k_wino_out<P, true>; what is left of the tail is the softmax over the pooled logits
+        if (!softmax_out) return TH_OK;
+        st.out_node = sm;
+        st.label = N[sm].name + ": softmax (logits pooled by the output transform) [k_softmax]";
+        st.is_final_softmax = true;
+        st.bytes = 8.0 * n.C;
+        st.run = [=](hipStream_t s, int64_t cnt) { return launch_softmax(s, cnt, M->view(i), M->view(sm)); };
+        M->logits_node = i;
+        P.fused_tail = sm;
+    } else if (int rc = is_max ? 0 : try_dense_tail(P, i, &st)) {
+        if (rc < 0) return rc;
+    } else if (!is_max && P.fuse && softmax_out && n.C <= 512 && !P.kn.no_tail_fuse && n.materialised) {
+        // TIMED's tail GlobalAveragePooling3D -> Softmax (the model output): one launch, one wavefront per frame
+        st.label = n.name + ": global_avg_pool + softmax [k_gap_softmax]";
+        st.bytes = 4.0 * ((double)N[src].D * N[src].H * N[src].W * N[src].C + 2.0 * n.C);
+        st.run = [=](hipStream_t s, int64_t cnt) { return launch_gap_softmax(s, cnt, M->view(src), M->view(i), M->view(sm)); };
+        M->logits_node = i;
+        P.fused_tail = sm;
+    } else {
+        st.label = n.name + (is_max ? ": global_max_pool" : ": global_avg_pool");
+        st.bytes = 4.0 * N[src].D * N[src].H * N[src].W * N[src].C;
+        st.run = [=](hipStream_t s, int64_t cnt) { return launch_global_pool(s, cnt, M->view(src), M->view(i), is_max); };
+    }
+    P.add_step(st);
+    return TH_OK;
+}
+
+// the step(s) of node i that is not a Conv3D / Dense layer
+int emit_node(Planner& P, int i) {
+    th_model* M = P.m;
+    std::vector<Node>& N = P.N;
+    const Node& n = N[i];
+    Step st;
+    st.out_node = i;
+    switch (n.op) {
+        case OP_INPUT: return TH_OK;          // the convert step is issued by predict() itself (it needs the caller's pointer/dtype)
+        case OP_BN:
+        case OP_ACT: {
+            const int src = n.in[0];
+            if (i == P.fused_tail) return TH_OK;      // computed by the k_gap_softmax step of its input
+            if (int rc = try_dense_tail(P, i, &st)) { if (rc < 0) return rc; break; }
+            if (n.op == OP_ACT && n.ip[0] == ACT_SOFTMAX) {
+                st.label = n.name + ": softmax";
+                st.is_final_softmax = i == M->output_node;
+                if (st.is_final_softmax) M->logits_node = src;
+                st.run = [=](hipStream_t s, int64_t cnt) { return launch_softmax(s, cnt, M->view(src), M->view(i)); };
+            } else {
                 PostOps po;
-                PreOp pre;
-                int rc;
-                const int own_act = n.op == OP_CONV3D ? n.ip[13] : n.ip[3];
-                bool split_softmax = false;
-                if (own_act == ACT_SOFTMAX) split_softmax = true;
-                else if (own_act != ACT_LINEAR) {
-                    po.type[0] = POP_ACT; po.act[0] = own_act; po.alpha[0] = n.fp[0]; po.n = 1;
-                    po.monotone = (own_act == ACT_RELU || own_act == ACT_SIGMOID || own_act == ACT_TANH ||
-                                   ((own_act == ACT_ELU || own_act == ACT_LEAKY) && n.fp[0] >= 0.f)) ? 1 : 0;
-                }
-                for (int x : f.post) if ((rc = add_post(M, &po, N[x]))) return rc < 0 ? rc : TH_EUNSUP;
-                if (M->knobs.no_pool_first) po.monotone = 0;   // A/B comparisons and tests: keep act/BN before the max-pool
-                for (int x : f.pre) {
-                    if (N[x].op == OP_BN) { if ((rc = bn_affine(M, N[x], &pre.scale, &pre.shift))) return rc; }
-                    else { pre.act = N[x].ip[0]; pre.alpha = N[x].fp[0]; }
-                }
-                const float* hw = n.w[0] >= 0 ? M->blob_host[n.w[0]] : nullptr;
-                if (!hw) TH_FAIL(TH_EIO, "%s: missing kernel", n.name.c_str());
-                float* dbias = nullptr;
-                const bool use_bias = (n.op == OP_CONV3D ? n.ip[12] : n.ip[2]) != 0;
-                if (use_bias) {
-                    if (n.w[1] < 0) TH_FAIL(TH_EIO, "%s: missing bias", n.name.c_str());
-                    if ((rc = upload(M, M->blob_host[n.w[1]], M->blob_count[n.w[1]], &dbias))) return rc;
-                }
-                const int src = f.src, dst = f.last;
-                if (n.op == OP_CONV3D) {
-                    const Node& sn = N[src];
-                    const ConvGeom g = geom_of(n, sn);
-                    const int Cin = sn.C, Cout = n.C;
-                    const size_t wcount = (size_t)g.kd * g.kh * g.kw * Cin * Cout;
-                    if (M->blob_count[n.w[0]] != wcount) TH_FAIL(TH_EIO, "%s: kernel size mismatch", n.name.c_str());
-                    st.flops = 2.0 * n.D * n.H * n.W * (double)g.kd * g.kh * g.kw * Cin * Cout;
-                    st.bytes = 4.0 * ((double)sn.D * sn.H * sn.W * Cin + (double)N[dst].D * N[dst].H * N[dst].W * N[dst].C);
-                    ConvWinoPlan wp;
-                    TView wiv; wiv.D = sn.D; wiv.H = sn.H; wiv.W = sn.W; wiv.C = sn.C;
-                    TView wov; wov.D = n.D; wov.H = n.H; wov.W = n.W; wov.C = n.C;
-                    if (M->winograd && use_mfma && fuse && f.pool < 0 && !split_softmax && conv_wino_plan(wiv, wov, g, Cin, Cout, M->winograd == 2 ? 7 : 9, &wp, M->wino_split)) {
-                        std::vector<float> packed(wp.wpk_floats);
-                        conv_wino_pack_weights(wp, hw, packed.data());
-                        float* dw;
-                        if ((rc = upload(M, packed.data(), packed.size(), &dw))) return rc;
-                        if (M->wino_v_buf < 0) {
-                            Buffer b;
-                            M->bufs.push_back(b); M->wino_v_buf = (int)M->bufs.size() - 1;
-                            M->bufs.push_back(b); M->wino_m_buf = (int)M->bufs.size() - 1;
-                        }
-                        M->bufs[M->wino_v_buf].floats_per_frame = std::max(M->bufs[M->wino_v_buf].floats_per_frame, wp.v_fpf);
-                        M->bufs[M->wino_m_buf].floats_per_frame = std::max(M->bufs[M->wino_m_buf].floats_per_frame, wp.m_fpf);
-                        // three steps, one kernel each.  `direct_flops` (the SURVEY §8d count of the direct form) stays with the
-                        // GEMM step for the model total; the per-step `flops` are what the kernels really compute: the GEMM's own
-                        // multiply-adds, nothing for the two bandwidth-bound transforms (their bytes are V / M traffic)
-                        const double direct = st.flops, act_bytes = st.bytes;
-                        const int64_t vf = wp.v_fpf, mf = wp.m_fpf;
-                        auto Vp = [=]() { const Buffer& b = M->bufs[M->wino_v_buf]; return b.dev + M->lane_off * b.floats_per_frame; };
-                        auto Mp = [=]() { const Buffer& b = M->bufs[M->wino_m_buf]; return b.dev + M->lane_off * b.floats_per_frame; };
-                        if (!wino_in_done.count(i)) {
-                            Step a;
-                            a.out_node = st.out_node;
-                            a.label = n.name + ": wino_in (25 voxels -> " + std::to_string(wp.P * wp.P) + " points per plane) [k_wino_in]";
-                            a.bytes = 4.0 * ((double)sn.D * sn.H * sn.W * Cin + (double)vf);
-                            a.run = [=](hipStream_t s, int64_t cnt) { return launch_wino_in(s, cnt, wp, M->view(src), Vp(), pre); };
-                            add_step(a);
-                        }
-                        st.flops = wp.gemm_flops;
-                        st.direct_flops = direct;
-                        // split GEMM: six bf16 piece products per fp32 multiply-add — what the bf16 matrix pipe issues
-                        st.exec_flops = wp.split ? 6.0 * wp.exec_flops : wp.exec_flops;
-                        st.bytes = 4.0 * ((double)vf + (double)mf);
-                        st.label = n.name + ": " + wp.label + (wp.narrow ? " [k_wino_gemm_n32]" : wp.split ? " [k_wino_gemm_b3]" : " [k_wino_gemm]");
-                        st.run = [=](hipStream_t s, int64_t cnt) { return launch_wino_gemm(s, cnt, wp, Vp(), Mp(), dw); };
-                        add_step(st);
-                        // two Winograd layers in a row and nobody else reads the tensor between them: this layer's output transform
-                        // feeds the next layer's V directly (k_wino_mid) and the 5^3 activation is never written
-                        int next = -1;
-                        ConvWinoPlan np;
-                        if (!M->knobs.wino_nomid && dst != M->output_node && N[dst].consumers.size() == 1) {
-                            const int c2 = N[dst].consumers[0];
-                            const Node& nx = N[c2];
-                            if (nx.op == OP_CONV3D && fus.count(c2) && fus[c2].src == dst && fus[c2].pre.empty() && fus[c2].pool < 0 &&
-                                nx.ip[13] != ACT_SOFTMAX) {
-                                const ConvGeom g2 = geom_of(nx, N[dst]);
-                                TView i2; i2.D = N[dst].D; i2.H = N[dst].H; i2.W = N[dst].W; i2.C = N[dst].C;
-                                TView o2; o2.D = nx.D; o2.H = nx.H; o2.W = nx.W; o2.C = nx.C;
-                                if (conv_wino_plan(i2, o2, g2, N[dst].C, nx.C, wp.P, &np, M->wino_split) && np.Cin == Cout) next = c2;
-                            }
-                        }
-                        if (next >= 0) {
-                            M->bufs[M->wino_v_buf].floats_per_frame = std::max(M->bufs[M->wino_v_buf].floats_per_frame, np.v_fpf);
-                            Step o;
-                            o.out_node = st.out_node;
-                            o.label = n.name + ": wino_mid (" + std::to_string(wp.P * wp.P) + " points -> bias + epilogue -> " + std::to_string(wp.P * wp.P) +
-                                      " points of " + N[next].name + ") [k_wino_mid]";
-                            o.bytes = 4.0 * ((double)mf / wp.Coutp * Cout + (double)np.v_fpf);
-                            o.run = [=](hipStream_t s, int64_t cnt) { return launch_wino_mid(s, cnt, wp, Mp(), Vp(), dbias, po); };
-                            add_step(o);
-                            wino_in_done.insert(next);
-                            N[dst].materialised = false;        // th_model_fetch refuses it ("fused away")
-                            continue;
-                        }
-                        // the layer's only reader is a GlobalAveragePooling3D (TIMED's 338-class head): the output transform pools
-                        // (k_wino_out<P, true>), neither the 5^3 activation nor the pooling kernel's pass over it exist
-                        int gp = -1;
-                        if (!M->knobs.no_tail_fuse && dst != M->output_node) {
-                            int cur = dst;
-                            while (N[cur].consumers.size() == 1 && N[N[cur].consumers[0]].op == OP_IDENTITY && N[cur].consumers[0] != M->output_node)
-                                cur = N[cur].consumers[0];
-                            if (N[cur].consumers.size() == 1 && N[N[cur].consumers[0]].op == OP_GAP && N[N[cur].consumers[0]].materialised &&
-                                N[N[cur].consumers[0]].absorbed_by < 0) {
-                                bool single = true;          // every node of the chain has exactly one reader
-                                for (int k = dst; k != cur; k = N[k].consumers[0]) if (N[k].consumers.size() != 1) single = false;
-                                if (single) gp = N[cur].consumers[0];
-                            }
-                        }
-                        if (gp >= 0) {
-                            Step o;
-                            o.out_node = gp;
-                            o.label = n.name + ": wino_out + global_avg_pool (" + std::to_string(wp.P * wp.P) + " points -> bias + epilogue -> mean of the 125 voxels) [k_wino_out]";
-                            o.bytes = 4.0 * ((double)mf / wp.Coutp * Cout + Cout);
-                            o.run = [=](hipStream_t s, int64_t cnt) { return launch_wino_out(s, cnt, wp, Mp(), M->view(gp), dbias, po, true); };
-                            add_step(o);
-                            for (int k = dst; ; k = N[k].consumers[0]) { N[k].materialised = false; if (N[k].consumers[0] == gp) break; }
-                            gap_done.insert(gp);
-                            continue;
-                        }
-                        Step o;
-                        o.out_node = st.out_node;
-                        o.label = n.name + ": wino_out (" + std::to_string(wp.P * wp.P) + " points -> 25 voxels per plane, bias + epilogue) [k_wino_out]";
-                        o.bytes = 4.0 * ((double)mf / wp.Coutp * Cout + (act_bytes / 4.0 - (double)sn.D * sn.H * sn.W * Cin));
-                        o.run = [=](hipStream_t s, int64_t cnt) { return launch_wino_out(s, cnt, wp, Mp(), M->view(dst), dbias, po); };
-                        add_step(o);
-                        continue;
-                    }
-                    ConvWfPlan fp;
-                    ConvWfsPlan sp;
-                    if (wf_plan_for(i, &fp) && conv_wfs_plan(fp, M->view(src), pre, &sp)) {
-                        // the same algorithm on the bf16 pipe: both operands split exactly into three bf16 pieces (conv_wfsplit.hip)
-                        std::vector<float> packed(sp.wpk_floats);
-                        conv_wfs_pack_weights(sp, hw, packed.data());
-                        float* dw;
-                        if ((rc = upload(M, packed.data(), packed.size(), &dw))) return rc;
-                        st.direct_flops = st.flops;
-                        st.flops = sp.own_flops;
-                        st.exec_flops = sp.exec_flops;
-                        st.label = n.name + ": " + (sn.blk ? label_note(sp.label, " (input chunk-blocked)") : sp.label);
-                        st.run = [=](hipStream_t s, int64_t cnt) {
-                            return launch_conv_wfs(s, cnt, sp, M->view(src), M->view(dst), dw, dbias, po);
-                        };
-                    } else if (wf_plan_for(i, &fp)) {
-                        // F(2,3)^2 in-plane with the whole transform domain in LDS: one step, one kernel
-                        std::vector<float> packed(fp.wpk_floats);
-                        conv_wf_pack_weights(fp, hw, packed.data());
-                        float* dw;
-                        if ((rc = upload(M, packed.data(), packed.size(), &dw))) return rc;
-                        st.direct_flops = st.flops;
-                        st.flops = fp.own_flops;
-                        st.exec_flops = fp.exec_flops;
-                        st.label = n.name + ": " + (sn.blk ? label_note(conv_wf_label(fp, pre), " (input chunk-blocked)") : conv_wf_label(fp, pre));
-                        st.run = [=](hipStream_t s, int64_t cnt) {
-                            return launch_conv_wf(s, cnt, fp, M->view(src), M->view(dst), dw, dbias, pre, po);
-                        };
-                    } else if (mplans.count(i) && mplans[i].cfg == 101) {
-                        const ConvMfmaPlan mp = mplans[i];
-                        std::vector<float> packed(conv_first5_wpk_floats());
-                        conv_first5_pack_weights(Cin, Cout, hw, packed.data());
-                        float* dw;
-                        if ((rc = upload(M, packed.data(), packed.size(), &dw))) return rc;
-                        st.exec_flops = mp.exec_flops;
-                        st.label = n.name + ": " + mp.label;
-                        const ThKnobs* kn = mp.knobs;
-                        st.run = [=](hipStream_t s, int64_t cnt) {
-                            return launch_conv_first5(s, cnt, kn, M->cur_in, M->cur_dtype, Cin, M->view(dst), Cout, dw, dbias, po);
-                        };
-                    } else if (mplans.count(i) && mplans[i].cfg == 100) {
-                        const ConvMfmaPlan mp = mplans[i];
-                        if (mp.first_wino) {
-                            st.direct_flops = st.flops;
-                            st.flops = mp.own_flops;
-                        }
-                        st.exec_flops = mp.exec_flops;
-                        const int iD = sn.D, iH = sn.H, iW = sn.W;
-                        // the aposteriori case (21^3 frames, pool before a monotone chain) runs on the bf16 pipe with split operands
-                        const bool b3 = conv_first_b3_ok(mp, iD, iH, iW, Cin, std::min(Cout, 32), g, po);
-                        const std::string flabel = b3 ? conv_first_b3_label(mp.nnb) : conv_first_label(mp, Cin, po);
-                        if (b3) st.exec_flops = conv_first_b3_exec_flops() * mp.nnb;
-                        st.label = n.name + ": " + (N[dst].blk ? label_note(flabel, " (output chunk-blocked)") : flabel);
-                        if (mp.nnb > 1) st.label = label_note(st.label, (" x" + std::to_string(mp.nnb) + " passes of 32 columns").c_str());
-                        // one launch per block of 32 output channels: its own weight columns, bias and per-channel epilogue vectors
-                        struct Pass { int c0, cn; float* dw; const float* bias; PostOps po; };
-                        std::vector<Pass> passes;
-                        const size_t ktaps = (size_t)g.kd * g.kh * g.kw * Cin;
-                        for (int c0 = 0; c0 < Cout; c0 += 32) {
-                            Pass ps;
-                            ps.c0 = c0; ps.cn = std::min(32, Cout - c0);
-                            std::vector<float> wcol(ktaps * ps.cn), packed(b3 ? conv_first_b3_wpk_floats() : mp.wpk_floats);
-                            for (size_t r = 0; r < ktaps; ++r) std::memcpy(&wcol[r * ps.cn], hw + r * Cout + c0, (size_t)ps.cn * sizeof(float));
-                            if (b3) conv_first_b3_pack_weights(Cin, ps.cn, wcol.data(), packed.data());
-                            else if (mp.first_wino) conv_first_w_pack_weights(Cin, ps.cn, wcol.data(), packed.data());
-                            else conv_first_pack_weights(Cin, ps.cn, wcol.data(), packed.data());
-                            if ((rc = upload(M, packed.data(), packed.size(), &ps.dw))) return rc;
-                            ps.bias = dbias ? dbias + c0 : nullptr;
-                            ps.po = po;
-                            for (int k = 0; k < ps.po.n; ++k) {
-                                if (ps.po.scale[k]) ps.po.scale[k] += c0;
-                                if (ps.po.shift[k]) ps.po.shift[k] += c0;
-                            }
-                            passes.push_back(ps);
-                        }
-                        st.run = [=](hipStream_t s, int64_t cnt) {
-                            for (const Pass& ps : passes) {
-                                TView ov = M->view(dst);
-                                if (passes.size() > 1) { ov.coff += ps.c0; ov.C = ps.cn; }
-                                const int r = b3 ? launch_conv_first_b3(s, cnt, mp, M->cur_in, M->cur_dtype, Cin, ov, ps.cn, ps.dw, ps.bias, ps.po)
-                                                 : launch_conv_first(s, cnt, mp, M->cur_in, M->cur_dtype, iD, iH, iW, Cin, ov, g, ps.cn, ps.dw, ps.bias, ps.po);
-                                if (r) return r;
-                            }
-                            return (int)TH_OK;
-                        };
-                    } else if (mplans.count(i) && mplans[i].cfg >= 300) {
-                        const ConvMfmaPlan mp = mplans[i];
-                        std::vector<float> packed(mp.wpk_floats);
-                        conv_pw_pack_weights(mp, Cin, Cout, hw, packed.data());
-                        float* dw;
-                        if ((rc = upload(M, packed.data(), packed.size(), &dw))) return rc;
-                        st.exec_flops = mp.exec_flops;
-                        st.label = n.name + ": " + conv_pw_label(mp, N[dst].blk != 0, po);
-                        if (N[dst].blk) st.label = label_note(st.label, " (output chunk-blocked)");
-                        st.run = [=](hipStream_t s, int64_t cnt) {
-                            return launch_conv_pw(s, cnt, mp, M->view(src), M->view(dst), Cin, Cout, dw, dbias, pre, po);
-                        };
-                    } else if (conv_gl_wanted(M->knobs.conv_gl, g, n.D * n.H * n.W) && f.pool < 0 && !sn.blk && !N[dst].blk &&
-                               (!mplans.count(i) || mplans[i].cfg < 100) &&             // (the 16-wide kernel keeps its layers: 42 against 62 us on DenseCPD's 2^3 ones)
-                               conv_gl_ok(Cin, Cout, sn.cs, sn.coff, (int64_t)M->bufs[sn.buf].floats_per_frame)) {
-                        // strided / few-outputs-per-frame layers: implicit GEMM with rows across the batch, operands from L2 (conv_gl.hip)
-                        std::vector<float> packed(conv_gl_wpk_floats(g, Cin, Cout));
-                        conv_gl_pack_weights(g, Cin, Cout, hw, packed.data());
-                        float* dw;
-                        if ((rc = upload(M, packed.data(), packed.size(), &dw))) return rc;
-                        st.exec_flops = conv_gl_exec_flops(g, Cin, Cout, n.D * n.H * n.W);
-                        st.label = n.name + ": " + conv_gl_label(Cout);
-                        st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_gl(s, cnt, M->view(src), M->view(dst), g, Cin, Cout, dw, dbias, pre, po); };
-                    } else if (mplans.count(i)) {
-                        ConvMfmaPlan mp = mplans[i];
-                        // heterogeneous Cout blocks: the last, mostly empty 128-column block on a narrower instantiation
-                        ConvMfmaPlan tp;
-                        int cout_main = Cout;
-                        TView ivp; ivp.D = sn.D; ivp.H = sn.H; ivp.W = sn.W; ivp.C = sn.C;
-                        TView ovp; ovp.D = n.D; ovp.H = n.H; ovp.W = n.W; ovp.C = n.C; ovp.fs = (int64_t)n.D * n.H * n.W * n.C;
-                        const bool tailed = conv_mfma_plan_tail(ivp, ovp, g, Cin, Cout, mp.pool, mp, &tp, &cout_main);
-                        float *dw, *dwt = nullptr;
-                        if (tailed) {
-                            const int cout_tail = Cout - cout_main;
-                            const size_t ktaps = (size_t)g.kd * g.kh * g.kw * Cin;
-                            std::vector<float> wm(ktaps * cout_main), wt(ktaps * cout_tail);
-                            for (size_t r = 0; r < ktaps; ++r) {
-                                std::memcpy(&wm[r * cout_main], hw + r * Cout, (size_t)cout_main * sizeof(float));
-                                std::memcpy(&wt[r * cout_tail], hw + r * Cout + cout_main, (size_t)cout_tail * sizeof(float));
-                            }
-                            mp.nnb -= 1;
-                            mp.exec_flops *= (double)mp.nnb / (mp.nnb + 1);
-                            mp.wpk_floats = mp.wpk_floats / (mp.nnb + 1) * mp.nnb;
-                            std::vector<float> packed(mp.wpk_floats), packed_t(tp.wpk_floats);
-                            conv_mfma_pack_weights(mp, g, Cin, cout_main, wm.data(), packed.data());
-                            conv_mfma_pack_weights(tp, g, Cin, cout_tail, wt.data(), packed_t.data());
-                            if ((rc = upload(M, packed.data(), packed.size(), &dw)) || (rc = upload(M, packed_t.data(), packed_t.size(), &dwt))) return rc;
-                            PostOps pot = po;        // per-channel vectors of the tail block start at its first channel
-                            for (int k = 0; k < pot.n; ++k) {
-                                if (pot.scale[k]) pot.scale[k] += cout_main;
-                                if (pot.shift[k]) pot.shift[k] += cout_main;
-                            }
-                            const float* dbias_t = dbias ? dbias + cout_main : nullptr;
-                            st.exec_flops = mp.exec_flops + tp.exec_flops;
-                            st.label = n.name + ": " + mp.label + " x" + std::to_string(mp.nnb) + " + " + tp.label;
-                            st.run = [=](hipStream_t s, int64_t cnt) {
-                                int r1 = launch_conv_mfma(s, cnt, mp, M->view(src), M->view(dst), g, Cin, cout_main, dw, dbias, pre, po);
-                                if (r1) return r1;
-                                TView ot = M->view(dst);
-                                ot.coff += cout_main;
-                                return launch_conv_mfma(s, cnt, tp, M->view(src), ot, g, Cin, cout_tail, dwt, dbias_t, pre, pot);
-                            };
-                        } else {
-                            std::vector<float> packed(mp.wpk_floats);
-                            conv_mfma_pack_weights(mp, g, Cin, Cout, hw, packed.data());
-                            if ((rc = upload(M, packed.data(), packed.size(), &dw))) return rc;
-                            st.exec_flops = mp.exec_flops;
-                            st.label = n.name + ": " + mp.label;
-                            st.run = [=](hipStream_t s, int64_t cnt) {
-                                return launch_conv_mfma(s, cnt, mp, M->view(src), M->view(dst), g, Cin, Cout, dw, dbias, pre, po);
-                            };
-                        }
-                    } else {
-                        float* dw;
-                        if ((rc = upload(M, hw, wcount, &dw))) return rc;
-                        st.exec_flops = st.flops;
-                        st.label = n.name + ": conv3d_direct";
-                        st.run = [=](hipStream_t s, int64_t cnt) {
-                            TView iv = M->view(src);
-                            return launch_conv3d_direct(s, cnt, iv, M->view(dst), g, dw, dbias, pre, po);
-                        };
-                    }
-                } else {
-                    const Node& sn = N[src];
-                    if (sn.cs != sn.C || sn.coff != 0 || sn.D * sn.H * sn.W != 1)
-                        TH_FAIL(TH_EUNSUP, "%s: Dense needs a contiguous vector input", n.name.c_str());
-                    const int F = sn.C, O = n.C;
-                    if (M->blob_count[n.w[0]] != (size_t)F * O) TH_FAIL(TH_EIO, "%s: kernel size mismatch", n.name.c_str());
-                    float* dw;
-                    if ((rc = upload(M, hw, (size_t)F * O, &dw))) return rc;
-                    st.flops = st.exec_flops = 2.0 * F * O;
-                    st.bytes = 4.0 * (F + O);
-                    if (th_knobs_planning().dense_gemm && dense_gemm_ok(F, O, (int64_t)M->bufs[sn.buf].floats_per_frame)) {
-                        st.label = n.name + ": dense as a batch GEMM, 16 frames x all outputs per workgroup, F in four quarters (16x16x4 fp32 MFMA) [k_dense_gemm]";
-                        st.run = [=](hipStream_t s, int64_t cnt) { return launch_dense_gemm(s, cnt, M->view(src), M->view(dst), dw, dbias, po); };
-                    } else {
-                        st.label = n.name + ": dense";
-                        st.run = [=](hipStream_t s, int64_t cnt) { return launch_dense(s, cnt, M->view(src), M->view(dst), dw, dbias, po); };
-                    }
-                }
-                if (n.op == OP_CONV3D) {
-                    // a 3x3x3 stride-1 layer that stays on a direct kernel says why no minimal-filtering form took it (tools/plan_report.py)
-                    const Node& sn = N[src];
-                    const ConvGeom g = geom_of(n, sn);
-                    const bool k333 = g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.dd == 1 && g.dh == 1 && g.dw == 1;
-                    const bool fast = st.label.find("conv_wf<") != std::string::npos || st.label.find("conv_first_w<") != std::string::npos ||
-                                      st.label.find("conv_first_b3<") != std::string::npos;
-                    if (k333 && !fast) {
-                        std::string why;
-                        const bool same = g.pz == 1 && g.py == 1 && g.px == 1;
-                        const bool first = src == M->input_node;
-                        if (!use_mfma || !fuse) why = "load flags select the direct kernels";
-                        else if (!same) why = "'valid' padding (the Cook-Toom forms are built for 'same')";
-                        else if (first && sn.C <= 8 && n.C <= 32) why = M->knobs.first_wino ? "odd computed width" : "TH_FIRST_WINO=0";
-                        else if (sn.D == 5 && sn.H == 5 && sn.W == 5) {
-                            if (!M->winograd) why = "TH_WINOGRAD=0";
-                            else if (f.pool >= 0) why = "a pooling layer is fused behind it";
-                            else if (sn.C < 32) why = "Cin < 32";
-                            else if (n.C < 64) why = "Cout < 64 (a 128-column GEMM block would run mostly empty)";
-                            else why = "softmax fused into the layer";
-                        } else if (sn.H % 2 == 0 && sn.W % 2 == 0 && sn.D * (sn.H / 2) * (sn.W / 2) <= 250) {
-                            if (!M->wfused) why = "TH_WFUSED=0";
-                            else if (sn.C < 16 || sn.C % 4) why = "Cin < 16 or not a multiple of 4";
-                            else if (!(sn.D == 10 && sn.H == 10 && sn.W == 10)) why = "conv_wf is instantiated for 10^3 volumes only";
-                            else why = "input view is not 16-byte aligned";
-                        } else why = "no minimal-filtering kernel for a " + std::to_string(sn.D) + "x" + std::to_string(sn.H) + "x" + std::to_string(sn.W) +
-                                     " volume (conv_wf: 10^3, conv_wino: 5^3)";
-                        st.label = label_note(st.label, (" (direct form: " + why + ")").c_str());
-                    }
-                }
-                add_step(st);
-                if (split_softmax) {
-                    Step sm;
-                    sm.out_node = dst;
-                    sm.label = n.name + ": softmax (layer activation)";
-                    sm.is_final_softmax = dst == M->output_node;
-                    sm.run = [=](hipStream_t s, int64_t cnt) { return launch_softmax(s, cnt, M->view(dst), M->view(dst)); };
-                    add_step(sm);
-                    if (sm.is_final_softmax) M->logits_node = dst;
-                }
-                continue;
+                int rc = add_post(M, &po, n);
+                if (rc) return rc < 0 ? rc : TH_EUNSUP;
+                st.label = n.name + (n.op == OP_BN ? ": batchnorm" : ": activation");
+                st.run = [=](hipStream_t s, int64_t cnt) { return launch_eltwise(s, cnt, M->view(src), M->view(i), po); };
             }
-            case OP_BN:
-            case OP_ACT: {
-                const int src = n.in[0];
-                if (i == fused_tail) continue;                 // computed by the k_gap_softmax step of its input
-                if (int rc = try_dense_tail(i, &st)) { if (rc < 0) return rc; break; }
-                if (n.op == OP_ACT && n.ip[0] == ACT_SOFTMAX) {
-                    st.label = n.name + ": softmax";
-                    st.is_final_softmax = i == M->output_node;
-                    if (st.is_final_softmax) M->logits_node = src;
-                    st.run = [=](hipStream_t s, int64_t cnt) { return launch_softmax(s, cnt, M->view(src), M->view(i)); };
-                } else {
-                    PostOps po;
-                    int rc = add_post(M, &po, n);
-                    if (rc) return rc < 0 ? rc : TH_EUNSUP;
-                    st.label = n.name + (n.op == OP_BN ? ": batchnorm" : ": activation");
-                    st.run = [=](hipStream_t s, int64_t cnt) { return launch_eltwise(s, cnt, M->view(src), M->view(i), po); };
-                }
-                st.bytes = 8.0 * n.D * n.H * n.W * n.C;
-                break;
-            }
-            case OP_MAXPOOL:
-            case OP_AVGPOOL: {
-                const int src = n.in[0];
-                const Node& sn = N[src];
-                ConvGeom g{};
-                g.kd = n.ip[0]; g.kh = n.ip[1]; g.kw = n.ip[2]; g.sd = n.ip[3]; g.sh = n.ip[4]; g.sw = n.ip[5];
-                g.dd = g.dh = g.dw = 1;
-                if (n.ip[6]) {
-                    keras_same_pad(sn.D, g.kd, g.sd, 1, &g.pz);
-                    keras_same_pad(sn.H, g.kh, g.sh, 1, &g.py);
-                    keras_same_pad(sn.W, g.kw, g.sw, 1, &g.px);
-                }
-                const int is_max = n.op == OP_MAXPOOL;
-                st.label = n.name + (is_max ? ": maxpool3d" : ": avgpool3d");
-                st.bytes = 4.0 * ((double)sn.D * sn.H * sn.W * sn.C + (double)n.D * n.H * n.W * n.C);
-                st.run = [=](hipStream_t s, int64_t cnt) { return launch_pool3d(s, cnt, M->view(src), M->view(i), g, is_max); };
-                break;
-            }
-            case OP_GAP:
-            case OP_GMP: {
-                const int src = n.in[0];
-                const int is_max = n.op == OP_GMP;
-                if (gap_done.count(i)) {
-                    // pooled by k_wino_out<P, true>; what is left of the tail is the softmax over the pooled logits
-                    if (n.consumers.size() == 1) {
-                        const int sm = n.consumers[0];
-                        if (N[sm].op == OP_ACT && N[sm].ip[0] == ACT_SOFTMAX && sm == M->output_node && N[sm].absorbed_by < 0 && N[sm].materialised) {
-                            st.out_node = sm;
-                            st.label = N[sm].name + ": softmax (logits pooled by the output transform) [k_softmax]";
-                            st.is_final_softmax = true;
-                            st.bytes = 8.0 * n.C;
-                            st.run = [=](hipStream_t s, int64_t cnt) { return launch_softmax(s, cnt, M->view(i), M->view(sm)); };
-                            M->logits_node = i;
-                            fused_tail = sm;
-                            break;
-                        }
-                    }
-                    continue;
-                }
-                if (!is_max) if (int rc = try_dense_tail(i, &st)) { if (rc < 0) return rc; break; }
-                // TIMED's tail GlobalAveragePooling3D -> Softmax (the model output): one launch, one wavefront per frame
-                if (!is_max && fuse && n.consumers.size() == 1 && n.C <= 512 && !M->knobs.no_tail_fuse) {
-                    const int sm = n.consumers[0];
-                    if (N[sm].op == OP_ACT && N[sm].ip[0] == ACT_SOFTMAX && sm == M->output_node && N[sm].absorbed_by < 0 &&
-                        N[sm].materialised && n.materialised) {
-                        st.label = n.name + ": global_avg_pool + softmax [k_gap_softmax]";
-                        st.bytes = 4.0 * ((double)N[src].D * N[src].H * N[src].W * N[src].C + 2.0 * n.C);
-                        st.run = [=](hipStream_t s, int64_t cnt) { return launch_gap_softmax(s, cnt, M->view(src), M->view(i), M->view(sm)); };
-                        M->logits_node = i;
-                        fused_tail = sm;
-                        break;
-                    }
-                }
-                st.label = n.name + (is_max ? ": global_max_pool" : ": global_avg_pool");
-                st.bytes = 4.0 * N[src].D * N[src].H * N[src].W * N[src].C;
-                st.run = [=](hipStream_t s, int64_t cnt) { return launch_global_pool(s, cnt, M->view(src), M->view(i), is_max); };
-                break;
-            }
-            case OP_FLATTEN:
-            case OP_IDENTITY: {
-                const int src = n.in[0];
-                if (n.buf == N[src].buf && n.coff == 0) continue;  // alias, nothing to do
-                // gather a channel-sliced tensor into a dense [V*C] vector
-                st.label = n.name + ": flatten(copy)";
-                st.run = [=](hipStream_t s, int64_t cnt) {
-                    TView o = M->view(src);  // same shape, destination is dense
-                    o.p = M->bufs[M->nodes[i].buf].dev; o.cs = o.C; o.coff = 0; o.fs = M->bufs[M->nodes[i].buf].floats_per_frame;
-                    return launch_copy(s, cnt, M->view(src), o);
-                };
-                break;
-            }
-            case OP_CONCAT: {
-                int off = 0;
-                bool any = false;
-                for (size_t k = 0; k < n.in.size(); ++k) {
-                    const int src = n.in[k];
-                    const int o = off;
-                    off += N[src].C;
-                    if (!concat_copy[i * kMaxIn + k]) continue;
-                    any = true;
-                    Step cs;
-                    cs.out_node = i;
-                    cs.label = n.name + ": concat(copy " + N[src].name + ")";
-                    cs.bytes = 8.0 * N[src].D * N[src].H * N[src].W * N[src].C;
-                    cs.run = [=](hipStream_t s, int64_t cnt) {
-                        TView d = M->view(i);
-                        d.coff += o;
-                        d.C = M->nodes[src].C;
-                        return launch_copy(s, cnt, M->view(src), d);
-                    };
-                    add_step(cs);
-                }
-                (void)any;
-                continue;
-            }
-            case OP_ADD: {
-                if (n.in.size() < 2) TH_FAIL(TH_EUNSUP, "%s: Add needs >= 2 inputs", n.name.c_str());
-                for (size_t k = 1; k < n.in.size(); ++k) {
-                    Step as;
-                    as.out_node = i;
-                    as.label = n.name + ": add";
-                    const int a = k == 1 ? n.in[0] : i, b = n.in[k];
-                    as.bytes = 12.0 * n.D * n.H * n.W * n.C;
-                    as.run = [=](hipStream_t s, int64_t cnt) { return launch_add(s, cnt, M->view(a), M->view(b), M->view(i)); };
-                    add_step(as);
-                }
-                continue;
-            }
-            default:
-                TH_FAIL(TH_EUNSUP, "node %s: op %d not supported", n.name.c_str(), n.op);
+            st.bytes = 8.0 * n.D * n.H * n.W * n.C;
+            break;
         }
-        add_step(st);
+        case OP_MAXPOOL:
+        case OP_AVGPOOL: {
+            const int src = n.in[0];
+            const Node& sn = N[src];
+            ConvGeom g{};
+            g.kd = n.ip[0]; g.kh = n.ip[1]; g.kw = n.ip[2]; g.sd = n.ip[3]; g.sh = n.ip[4]; g.sw = n.ip[5];
+            g.dd = g.dh = g.dw = 1;
+            if (n.ip[6]) {
+                keras_same_pad(sn.D, g.kd, g.sd, 1, &g.pz);
+                keras_same_pad(sn.H, g.kh, g.sh, 1, &g.py);
+                keras_same_pad(sn.W, g.kw, g.sw, 1, &g.px);
+            }
+            const int is_max = n.op == OP_MAXPOOL;
+            st.label = n.name + (is_max ? ": maxpool3d" : ": avgpool3d");
+            st.bytes = 4.0 * ((double)sn.D * sn.H * sn.W * sn.C + (double)n.D * n.H * n.W * n.C);
+            st.run = [=](hipStream_t s, int64_t cnt) { return launch_pool3d(s, cnt, M->view(src), M->view(i), g, is_max); };
+            break;
+        }
+        case OP_GAP:
+        case OP_GMP: return emit_global_pool(P, i);
+        case OP_FLATTEN:
+        case OP_IDENTITY: {
+            const int src = n.in[0];
+            if (n.buf == N[src].buf && n.coff == 0) return TH_OK;  // alias, nothing to do
+            // gather a channel-sliced tensor into a dense [V*C] vector
+            st.label = n.name + ": flatten(copy)";
+            st.run = [=](hipStream_t s, int64_t cnt) {
+                TView o = M->view(src);  // same shape, destination is dense
+                o.p = M->bufs[M->nodes[i].buf].dev; o.cs = o.C; o.coff = 0; o.fs = M->bufs[M->nodes[i].buf].floats_per_frame;
+                return launch_copy(s, cnt, M->view(src), o);
+            };
+            break;
+        }
+        case OP_CONCAT: {
+            int off = 0;
+            for (size_t k = 0; k < n.in.size(); ++k) {
+                const int src = n.in[k];
+                const int o = off;
+                off += N[src].C;
+                if (!P.concat_copy[i * kMaxIn + k]) continue;
+                P.add_step(i, n.name + ": concat(copy " + N[src].name + ")", 8.0 * N[src].D * N[src].H * N[src].W * N[src].C,
+                           [=](hipStream_t s, int64_t cnt) {
+                               TView d = M->view(i);
+                               d.coff += o;
+                               d.C = M->nodes[src].C;
+                               return launch_copy(s, cnt, M->view(src), d);
+                           });
+            }
+            return TH_OK;
+        }
+        case OP_ADD: {
+            if (n.in.size() < 2) TH_FAIL(TH_EUNSUP, "%s: Add needs >= 2 inputs", n.name.c_str());
+            for (size_t k = 1; k < n.in.size(); ++k) {
+                const int a = k == 1 ? n.in[0] : i, b = n.in[k];
+                P.add_step(i, n.name + ": add", 12.0 * n.D * n.H * n.W * n.C,
+                           [=](hipStream_t s, int64_t cnt) { return launch_add(s, cnt, M->view(a), M->view(b), M->view(i)); });
+            }
+            return TH_OK;
+        }
+        default:
+            TH_FAIL(TH_EUNSUP, "node %s: op %d not supported", n.name.c_str(), n.op);
+    }
+    P.add_step(st);
+    return TH_OK;
+}
+
+// the load-time planner: the model's graph -> m->steps, a short list of launches
+int plan(th_model* m) {
+    Planner P(m);
+    fusion_pass(P);
+    storage_pass(P);
+    wf_pass(P);
+    blocked_pass(P);
+    for (auto& [i, L] : P.layers)
+        if (int rc = choose_kernel(P, i, L)) return rc;
+    for (int i = 0; i < (int)P.N.size(); ++i) {
+        if (!(P.layers.count(i) || P.N[i].absorbed_by < 0) || P.tail_done.count(i)) continue;
+        const int rc = P.layers.count(i) ? emit_layer(P, i) : emit_node(P, i);
+        if (rc) return rc;
     }
     for (const Step& s : m->steps) { m->algo_flops += s.direct_flops >= 0 ? s.direct_flops : s.flops; m->exec_flops += s.exec_flops; }
-    (void)V;
     return TH_OK;
 }
 
@@ -1462,6 +1572,7 @@ int run_device(th_model* m, const void* d_frames, int dtype, int64_t n, float* d
 
 int load_common(th_model* m, const ThKnobs* forced = nullptr) {
     HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipDeviceGetAttribute(&m->ncu, hipDeviceAttributeMultiprocessorCount, m->device));
     HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&m->d2h_stream, hipStreamNonBlocking));
@@ -1472,7 +1583,6 @@ int load_common(th_model* m, const ThKnobs* forced = nullptr) {
     if (forced) m->knobs = *forced;             // (the load-time guard's reference / fallback plans)
     else th_knobs_read(&m->knobs);
     m->lanes = m->knobs.lanes; m->lane_lag = m->knobs.lane_lag;
-    m->winograd = m->knobs.winograd; m->wfused = m->knobs.wfused; m->wino_split = m->knobs.wino_split;
     for (int r = 0; r < th_model::kRing; ++r) {
         HIP_TRY(hipEventCreateWithFlags(&m->ev_h2d[r], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&m->ev_free[r], hipEventDisableTiming));
@@ -1483,10 +1593,7 @@ int load_common(th_model* m, const ThKnobs* forced = nullptr) {
     }
     int rc = parse_pack(m);
     if (rc) return rc;
-    th_knobs_set_planning(&m->knobs);
-    rc = plan(m);
-    th_knobs_set_planning(nullptr);
-    return rc;
+    return plan(m);
 }
 
 
@@ -1503,12 +1610,7 @@ constexpr int kGuardFrames = 4;
 constexpr double kGuardTol = 1e-5;
 
 bool has_fast_steps(const th_model* m) {
-    for (const Step& s : m->steps)
-        if (s.label.find("conv_wino") != std::string::npos || s.label.find("conv_wf<") != std::string::npos ||
-            s.label.find("k_conv_first_w") != std::string::npos || s.label.find("k_conv_first_b3") != std::string::npos ||
-            s.label.find("k_conv_first5") != std::string::npos)
-            return true;
-    return false;
+    return std::any_of(m->steps.begin(), m->steps.end(), [](const Step& s) { return s.fast; });
 }
 
 // deterministic frames of any shape: the first half sparse in [0, 1] (about one voxel-channel in five non-zero, like
