@@ -280,6 +280,30 @@ int th_csv_fill(const char* text, int64_t len, char delim, int64_t rows, int col
 int th_argmax_letters(const void* matrix, int dtype, int64_t n, int64_t k, const char* col_letters, char* letters_out,
                       int32_t* idx_out);
 
+/* ---- evaluation: predict.py --output_analysis — what the reference computes with sklearn / scipy in
+ * design_utils/analyse_utils.py (calculate_metrics :628-728, calculate_prediction_entropy :294-310) and ui.py:55-59 (BLOSUM62
+ * similarity), in one pass over the prediction matrix on the GPU.  Residues are indices 0..19 in the order ACDEFGHIKLMNPQRSTVWY.
+ * matrix: host [n, k] of TH_F16 or TH_F32, 1 <= k <= 1024; col_res: host int8[k], the residue that owns each column (the identity
+ * for k = 20, the rotamer codec's owner for k = 338; any order); true_res: host int8[n], 0..19 or -1 (unlabelled).  Per row:
+ *   pred_out[i]    = col_res[argmax_i] under th_argmax_letters' rules (first maximum, first NaN) — the FASTA letter;
+ *   rank_out[i]    = rank of the true residue t: with s_r = max of residue r's columns and c_r the first column reaching it,
+ *                    #{r : s_r > s_t or (s_r == s_t and c_r < c_t)}; 20 ("never a hit") when t owns no column; a row holding a NaN
+ *                    or an infinity ranks 0 if pred == t, else 20; -1 for an unlabelled row;
+ *   entropy_out[i] = Shannon entropy in bits of the row normalised by its sum (scipy.stats.entropy(row, base=2)), float64; NaN when
+ *                    the sum is 0 or the row holds a NaN, an infinity or a negative value (scipy gives -inf for the last).
+ * Each output may be NULL.  Totals over the whole matrix (labelled rows only, but n_nonfinite counts every row) are 64-bit integers,
+ * independent of arrival order: two calls give the same bytes.  similar = BLOSUM62(true, pred) > 0.  The host rows are staged to
+ * `device` in blocks of up to 262 144 rows (at most 256 MB; TH_ANALYSIS_BLOCK_ROWS overrides the row count, results unchanged),
+ * copies overlapping the kernel of the previous block.  TH_EINVAL: dtype, k, or a col_res / true_res value out of range.  n = 0
+ * returns zero totals. */
+typedef struct th_analysis_totals {
+    int64_t confusion[20][20];    /* [true][predicted]                               */
+    int64_t rank_hist[21];        /* rank of the true residue; bucket 20: never a hit */
+    int64_t n_labelled, n_nonfinite, n_similar;
+} th_analysis_totals;
+int th_analyse_probs(int device, const void* matrix, int dtype, int64_t n, int64_t k, const int8_t* col_res, const int8_t* true_res,
+                     int8_t* pred_out, int8_t* rank_out, double* entropy_out, th_analysis_totals* totals);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

@@ -106,3 +106,30 @@ def calculate_seq_metrics(seq: str) -> t.Tuple[float, float, float, float]:
     """reference analyse_utils.py:351-371 -> (charge, iso_ph, mw, me)."""
     c, p, m, e = seq_metrics_batch([seq])[0]
     return float(c), float(p), float(m), int(e) if float(e).is_integer() else float(e)
+
+
+# ---- prediction entropy (predict.py --output_analysis; computed on the GPU by timed_hip.analysis) -----------------------------
+def calculate_prediction_entropy(residue_predictions) -> np.ndarray:
+    """reference analyse_utils.py:294-310: Shannon entropy in bits of every row of an (n, k) probability matrix —
+    ``scipy.stats.entropy(residue_predictions, base=2, axis=1)`` — computed by th_analyse_probs.  Differs from scipy for a row
+    with a negative entry (NaN here, -inf there); float64 rows are narrowed as timed_hip.analysis.entropy says."""
+    from timed_hip import analysis
+    return analysis.entropy(np.asarray(residue_predictions))
+
+
+def extract_prediction_entropy_to_dict(model_pred_path, model_map_path, rotamer_mode: bool = False, is_old: bool = False) -> dict:
+    """reference analyse_utils.py:237-291: {key: entropy of each of its rows} for a prediction CSV and its dataset map (key and
+    row order as extract_sequence_from_pred_matrix gives them).  ``rotamer_mode`` names a 338-column matrix (``<model>_rot.csv``);
+    the entropy is over all of its columns either way."""
+    from pathlib import Path
+
+    from . import utils
+    model_pred_path, model_map_path = Path(model_pred_path), Path(model_map_path)
+    assert model_pred_path.exists(), f"Model path {model_pred_path} does not exists."
+    assert model_map_path.exists(), f"Model path {model_map_path} does not exists."
+    prediction_matrix = np.atleast_2d(np.loadtxt(model_pred_path, delimiter=",", dtype=np.float64))
+    if rotamer_mode and prediction_matrix.shape[1] != 338:
+        raise ValueError(f"rotamer_mode expects 338 columns, {model_pred_path} has {prediction_matrix.shape[1]}")
+    plan = utils.SequencePlan(utils.load_datasetmap(model_map_path, is_old=is_old))
+    entropy = calculate_prediction_entropy(prediction_matrix)
+    return {key: entropy[plan.rows(key)] for key in plan.keys}

@@ -454,6 +454,7 @@ def load_dataset_and_predict(
     devices=None,
     model_loader=None,
     gather=None,
+    output_analysis: bool = False,
 ) -> (np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray):
     """reference predict.py:28-194 — same leading parameters and return tuple (flat_dataset_map, pdb_to_sequence,
     pdb_to_probability, pdb_to_real_sequence, pdb_to_consensus, pdb_to_consensus_prob).  ``start_batch`` keeps the
@@ -461,7 +462,9 @@ def load_dataset_and_predict(
 
     Opt-in extras: ``device`` / ``devices`` (HIP device indices for this process), ``frames_per_call`` (frames handed to
     a GPU per call), ``model_loader(path, device=...)`` (default ``timed_hip.engine.load_model``) and ``gather`` (a
-    row-gather transport from ``timed_hip.distributed``; default: RCCL when WORLD_SIZE > 1)."""
+    row-gather transport from ``timed_hip.distributed``; default: RCCL when WORLD_SIZE > 1) and ``output_analysis``
+    (after each model's FASTA, rank 0 writes <model>_analysis.json, <model>_entropy.csv and <model>_per_structure.csv — see
+    _write_analysis)."""
     path_to_output = Path(path_to_output)
     n_classes = N_ROTAMER_CLASSES if predict_rotamers else N_RESIDUE_CLASSES
     rank, world, local_rank, gather = _distributed_context(gather)
@@ -542,8 +545,9 @@ def load_dataset_and_predict(
                     h.close()
                 if srb is not None:
                     srb.result()
+            matrix = files.prediction_matrix()
             outputs = du.extract_sequence_from_pred_matrix(
-                flat_dataset_map, files.prediction_matrix(), rotamers_categories=flat_categories if predict_rotamers else None,
+                flat_dataset_map, matrix, rotamers_categories=flat_categories if predict_rotamers else None,
                 old_datasetmap=old_datasetmap, is_consensus=is_consensus, plan=plan.result())
             pdb_to_sequence, _prob, pdb_to_real_sequence, pdb_to_consensus, pdb_to_consensus_prob = outputs
             du.save_dict_to_fasta(pdb_to_sequence, model_name, path_to_output)
@@ -551,6 +555,9 @@ def load_dataset_and_predict(
             if pdb_to_consensus:
                 du.save_dict_to_fasta(pdb_to_consensus, model_name + "_consensus", path_to_output)
                 du.save_consensus_probs(pdb_to_consensus_prob, model_name, path_to_output)
+            if output_analysis:
+                _write_analysis(matrix, flat_dataset_map, plan.result(), model_name, path_to_output, predict_rotamers,
+                                flat_categories, device_ids[0])
     finally:
         if pending_handles is not None:          # a model that was prefetched but never used (an error above)
             try:
@@ -560,6 +567,67 @@ def load_dataset_and_predict(
                 pass
         side.shutdown(wait=True)
     return (flat_dataset_map, *outputs)
+
+
+def _write_analysis(matrix, flat_dataset_map, plan, model_name, path_to_output, predict_rotamers, flat_categories, device):
+    """--output_analysis for one model: the float16 matrix the FASTA was read off (so resumed and sharded runs are covered) against
+    the residue column of a 4-column map, on the GPU (timed_hip.analysis, th_analyse_probs).  Rotamer matrices are ranked per
+    residue through the codec's column owners; their entropy is over all 338 columns.  A "<pdb> <count>" map carries no truth:
+    entropies only, n_labelled 0 and every metric null.  Writes <model>_analysis.json, <model>_entropy.csv (one float64 per row
+    in map order, np.savetxt's format) and <model>_per_structure.csv (one line per key in key order)."""
+    import json
+    from timed_hip import analysis
+    n = matrix.shape[0]
+    if n != plan.n_rows:
+        raise ValueError(f"{model_name}: the prediction matrix has {n} rows, the dataset map {plan.n_rows}")
+    if plan.old_datasetmap:
+        true_res = analysis.residue_indices(np.asarray(flat_dataset_map)[:, 3])
+    else:
+        true_res = np.full(n, -1, np.int8)
+    col_res = analysis.rotamer_columns(flat_categories) if predict_rotamers else analysis.identity_columns()
+    got = analysis.analyse_probs(matrix, true_res, col_res, device=device)
+    metrics = {"model": model_name, "rotamer_mode": bool(predict_rotamers),
+               **analysis.metrics_from_totals(got.confusion, got.rank_hist, got.n_labelled, got.n_nonfinite, got.n_similar, n,
+                                              got.entropy)}
+    with open(path_to_output / f"{model_name}_analysis.json", "w") as f:
+        json.dump(metrics, f, indent=1, allow_nan=False)
+        f.write("\n")
+    # np.savetxt's text of one value per row; rows are independent, so large vectors are formatted in parts on parallel threads
+    parts = np.array_split(got.entropy, max(1, min(8, n // 16384)))
+    with ThreadPoolExecutor(max_workers=len(parts)) as pool, open(path_to_output / f"{model_name}_entropy.csv", "wb") as f:
+        for text in pool.map(textio.format_csv, parts):
+            f.write(text)
+    labelled = true_res >= 0
+    similar = np.zeros(n, dtype=bool)
+    similar[labelled] = analysis.BLOSUM62[true_res[labelled], got.pred[labelled]] > 0
+    # per key (runs of rows, SequencePlan order): counts and sums by bincount over the key index of every row
+    key_of_row = np.empty(n, dtype=np.int64)
+    for i, key in enumerate(plan.keys):
+        for lo, hi in plan.runs[key]:
+            key_of_row[lo:hi] = i
+    n_keys = len(plan.keys)
+
+    def per_key(mask, weights=None):
+        return np.bincount(key_of_row[mask], weights=None if weights is None else weights[mask], minlength=n_keys)
+    finite = ~np.isnan(got.entropy)
+    rows, n_lab = per_key(slice(None)), per_key(labelled)
+    n_ent = per_key(finite).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        accuracy = per_key(labelled & (got.rank == 0)) / n_lab
+        similarity = per_key(similar) / n_lab
+        mean = per_key(finite, got.entropy) / n_ent
+        dev = np.where(finite, got.entropy - mean[key_of_row], 0.0)
+        std = np.sqrt(per_key(finite, dev * dev) / n_ent)           # ddof = 0
+    lines = ["key,n_residues,n_labelled,accuracy,similarity,mean_entropy,std_entropy\n"]
+    lines += [f"{key},{r},{nl},{a!r},{s!r},{m!r},{d!r}\n" for key, r, nl, a, s, m, d in
+              zip(plan.keys, rows.tolist(), n_lab.tolist(), accuracy.tolist(), similarity.tolist(), mean.tolist(), std.tolist())]
+    with open(path_to_output / f"{model_name}_per_structure.csv", "w") as f:
+        f.write("".join(lines))
+
+    def show(v):
+        return "n/a" if v is None else f"{v:.4f}"
+    print(f"[analysis] {model_name}: top-1 {show(metrics['accuracy_1'])}  top-3 {show(metrics['accuracy_3'])}  "
+          f"macro recall {show(metrics['recall'])}  mean entropy {show(metrics['mean_entropy'])} bits  N={got.n_labelled}")
 
 
 def _predict_sharded(model, gather, rank, world, dataset_path, flat_dataset_map, batch_size, start_batch, frames_per_call, files,
@@ -640,7 +708,7 @@ CLI_FLAGS = (
     ("--path_to_model", dict(type=str, help="Keras legacy .h5 model or converted .pack")),
     ("--path_to_blacklist", dict(type=str, default=None, help="directory of PDB lists to refuse (training-set structures)")),
     ("--path_to_output", dict(type=str, default=".", help="output directory (asked before it is created)")),
-    ("--output_analysis", dict(action="store_true", help="accepted for compatibility; unused, as in the reference")),
+    ("--output_analysis", dict(action="store_true", help="also write <model>_analysis.json (top-k accuracy, macro precision / recall, confusion, bias, BLOSUM62 similarity), <model>_entropy.csv and <model>_per_structure.csv")),
     ("--predict_rotamers", dict(action="store_true", help="the model predicts 338 rotamer classes instead of 20 residues")),
     ("--is_structure_nmr", dict(action="store_true", help="merge the states of an NMR ensemble into a consensus")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
@@ -687,7 +755,7 @@ def _main_predict(args, required, devices):
         dataset_map_path=Path(args.path_to_datasetmap), blacklist=required.get("blacklist"),
         predict_rotamers=args.predict_rotamers, is_consensus=args.is_structure_nmr,
         path_to_output=Path(args.path_to_output), device=getattr(args, "device", 0), devices=devices,
-        frames_per_call=getattr(args, "frames_per_call", None))
+        frames_per_call=getattr(args, "frames_per_call", None), output_analysis=bool(getattr(args, "output_analysis", False)))
 
 
 if __name__ == "__main__":
