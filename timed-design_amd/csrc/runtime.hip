@@ -94,7 +94,7 @@ void th_knobs_read(ThKnobs* k) {
     if (const char* e = getenv("TH_WINO_PIECE")) { k->wino_piece = std::max(0ll, atoll(e)); if (k->wino_piece) note("TH_WINO_PIECE", e); }
     num("TH_WINO_DBG", &k->wino_dbg, 0, 1 << 20);
     num("TH_WINO_VAR", &k->wino_var, 0, 3);
-    num("TH_WINO_B3VAR", &k->wino_b3var, 0, 1);
+    num("TH_WINO_B3VAR", &k->wino_b3var, 0, 2);
     num("TH_WINO_NOMID", &k->wino_nomid, 0, 1);
 }
 
