@@ -58,7 +58,7 @@ struct ThKnobs {
     int pw_nopipe = 0, pw_noepi = 0, pw_dbg = 0;
     int wf_resident = 0, wf_dbg = 0, wf_noblk = 0;
     long long wino_piece = 0;
-    int wino_dbg = 0, wino_var = 3, wino_b3var = 2, wino_nomid = 0;
+    int wino_dbg = 0, wino_b3var = 2, wino_nomid = 0;
     std::string nondefault;
 };
 void th_knobs_read(ThKnobs* k);                 // the process environment, now
@@ -200,8 +200,8 @@ struct ConvWinoPlan {
     int split = 0;                               // 1: the GEMM runs on bf16 MFMA with both operands split exactly into three bf16 pieces
                                                  // (x = h + m + l) and six of the nine piece products summed in fp32 (k_wino_gemm_b3)
     int narrow = 0;                              // split GEMM of a layer with Cout <= 32: one 32-column tile per wave, no LDS (k_wino_gemm_n32)
-    int b3var = 0;                               // split, not narrow: k_wino_gemm_b3 variant (TH_WINO_B3VAR at plan time; 2 = 16x16x32
-                                                 // MFMA, its own weight-stream order, so packing and launch both read it from here)
+    int b3var = 0;                               // split, not narrow: which k_wino_gemm_b3_* (TH_WINO_B3VAR at plan time; 2 = 16x16x32 MFMA,
+                                                 // else 32x32x16: each has its weight-stream order, so packing and launch both read it here)
     const ThKnobs* knobs = nullptr;
     std::string label;
 };

@@ -5,7 +5,7 @@
 //
 // Direct form (125 taps: a minimal-filtering form would need 6 points per x pair and three times the staged data), products as
 // v_mfma_f32_16x16x32_bf16 on operands split exactly into three bf16 pieces, six of nine piece products, fp32 accumulation — the
-// scheme of conv_first_b3.hip / conv_wfsplit.hip, and like the latter the data is split ONCE, when it is staged:
+// scheme of bf16x3.h, and like conv_wfsplit.hip the data is split ONCE, when it is staged:
 //   D3  [piece 3][ring of 6 planes][14 rows][25 of 28 x] x 16 bytes   a voxel's (<= 8) channels as one bf16x8 record per piece, zero halo
 //   B   [2 buffers][7 k-steps][piece 3][lane 64] x 16 bytes     the weights of ONE z tap, LDS-DMA, double-buffered over the 5 z taps
 // A k-step (K = 32) is four voxel records: for a (dz, dy) row the taps dx = 0..3 (lane group kg <-> dx), and the fifth tap dx = 4
@@ -14,6 +14,7 @@
 // window (row = 8 pooled voxel + (dx2, dz2, dy2)), so that a lane's four accumulator rows and its neighbour 16 lanes away hold
 // one window.  One persistent 8-wave workgroup per CU walks frame -> y half -> pooled plane; consecutive planes share four of
 // their six input planes: the two new ones are requested when a unit starts and written (split) when it ends.
+#include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
 
@@ -21,11 +22,6 @@
 
 #include <algorithm>
 #include <cstring>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -63,9 +59,6 @@ __device__ __forceinline__ float f5_load_elem(const void* base, int dtype, int64
         case TH_BOOL: return ((const unsigned char*)base)[i] ? 1.f : 0.f;
         default: return __half2float(((const __half*)base)[i]);
     }
-}
-__device__ __forceinline__ unsigned f5_pk(float x, float y) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((v2f){x, y}, bf16x2));
 }
 __device__ __forceinline__ void f5_glds(const void* base, unsigned voff, unsigned lds_dst) {
     unsigned keep;
@@ -112,14 +105,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_first5(const ConvF5Args a) {
     auto store_voxel = [&](int dst, const float (&x)[8]) {
         unsigned h[4], m[4], l[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float x0 = x[2 * k], x1 = x[2 * k + 1];
-            h[k] = f5_pk(x0, x1);
-            const float r0 = x0 - __builtin_bit_cast(float, h[k] << 16), r1 = x1 - __builtin_bit_cast(float, h[k] & 0xffff0000u);
-            m[k] = f5_pk(r0, r1);
-            const float q0 = r0 - __builtin_bit_cast(float, m[k] << 16), q1 = r1 - __builtin_bit_cast(float, m[k] & 0xffff0000u);
-            l[k] = f5_pk(q0, q1);
-        }
+        for (int k = 0; k < 4; ++k) bf16x3::split(x[2 * k], x[2 * k + 1], h[k], m[k], l[k]);
         D3[dst] = make_uint4(h[0], h[1], h[2], h[3]);
         D3[kF5Piece + dst] = make_uint4(m[0], m[1], m[2], m[3]);
         D3[2 * kF5Piece + dst] = make_uint4(l[0], l[1], l[2], l[3]);
@@ -294,20 +280,6 @@ __global__ void __launch_bounds__(512, 1) k_conv_first5(const ConvF5Args a) {
 
 typedef void (*F5Kernel)(const ConvF5Args);
 
-inline uint16_t f5_bf16_rne(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)(u >> 16);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline double f5_bf16_val(uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return (double)f;
-}
-
 }  // namespace
 
 // does the kernel serve this layer?  (asked by the planner before anything is packed)
@@ -346,10 +318,7 @@ void conv_first5_pack_weights(int Cin, int Cout, const float* w, float* dst_f) {
                     for (int co = 0; co < Cout; ++co) {
                         const double u = (double)w[((((size_t)dz * 5 + dy) * 5 + dx) * Cin + c) * Cout + co];
                         uint16_t pc[3];
-                        pc[0] = f5_bf16_rne((float)u);
-                        const double r1 = u - f5_bf16_val(pc[0]);
-                        pc[1] = f5_bf16_rne((float)r1);
-                        pc[2] = f5_bf16_rne((float)(r1 - f5_bf16_val(pc[1])));
+                        bf16x3::split3(u, pc);
                         for (int piece = 0; piece < 3; ++piece)
                             dst[((((size_t)dz * kF5KS + ks) * 3 + piece) * 64 + 16 * kgi + co) * 8 + c] = pc[piece];
                     }

@@ -6,8 +6,7 @@
 // Same algorithm as k_conv_first_w — F(2,3) along x, a GEMM row is an x PAIR, four transform points V0 = d0 - d2, V1 = d1 + d2,
 // V2 = d2 - d1, V3 = d1 - d3 per (dz, dy) tap and channel, out(2 tx) = M0 + M1 + M2, out(2 tx + 1) = M1 - M2 - M3 — but the
 // products run as v_mfma_f32_32x32x16_bf16 on operands split exactly into three bf16 pieces (x = h + m + l, round to nearest
-// even at every step; six of the nine piece products, fp32 accumulation: the scheme of conv_wino.hip's k_wino_gemm_b3, error of
-// one fp32 rounding).  A lane half holds the three channels 2 s + h: taps 0..7 fill 3 k-steps of 16 without a padding slot (72
+// even at every step; six of the nine piece products, fp32 accumulation: the scheme of bf16x3.h, error of one fp32 rounding).  A lane half holds the three channels 2 s + h: taps 0..7 fill 3 k-steps of 16 without a padding slot (72
 // MFMAs of 32 cycles per tile of 32 pairs), tap 8 runs as 3 v_mfma_f32_32x32x2_f32 per point (table below): 3072 matrix-pipe
 // cycles per tile where the fp32 form needs 6912 (108 MFMAs of 64).
 //
@@ -26,6 +25,7 @@
 //     the next two planes are requested from HBM when the round starts and written to their ring slots when it ends — one
 //     barrier per round, no halo plane is staged twice, frame boundaries included (the next frame's first planes arrive during
 //     the last two rounds).
+#include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
 
@@ -33,12 +33,6 @@
 
 #include <algorithm>
 #include <cstring>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -85,13 +79,6 @@ __device__ __forceinline__ float b3_load_elem(const void* base, int dtype, int64
         case TH_BOOL: return ((const unsigned char*)base)[i] ? 1.f : 0.f;
         default: return __half2float(((const __half*)base)[i]);
     }
-}
-
-__device__ __forceinline__ unsigned b3_pk(v2f x) {          // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-}
-__device__ __forceinline__ v2f b3_unpk(unsigned w) {
-    return (v2f){__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
 }
 
 // which (tap t9 = 3 dz + dy, channel slot s) sits in k-slot pair q of k-step ks.  Pairs 'P' are the two floats of a voxel's
@@ -283,12 +270,12 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                     pa[dz] = slot * kPairWords + (y * kRowVox + 2 * px) * 4 + 2 * h;
                     sa[dz] = kSingleBase + slot * kSingleWords + (y * kRowVox + 2 * px) * 2 + h;
                 }
-                auto rdP = [&](int t9, v2f (&d)[4]) {
+                auto rdP = [&](int t9, f32x2 (&d)[4]) {
                     const int dz = t9 / 3, dy = t9 % 3;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        if (DBG & 256) { d[i] = (v2f){__builtin_bit_cast(float, pa[dz] + t9), (float)i}; continue; }
-                        d[i] = *reinterpret_cast<const v2f*>(A + pa[dz] + (dy * kRowVox + i) * 4);
+                        if (DBG & 256) { d[i] = (f32x2){__builtin_bit_cast(float, pa[dz] + t9), (float)i}; continue; }
+                        d[i] = *reinterpret_cast<const f32x2*>(A + pa[dz] + (dy * kRowVox + i) * 4);
                     }
                 };
                 auto rdS = [&](int t9, float (&d)[4]) {
@@ -299,12 +286,12 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                         d[i] = A[sa[dz] + (dy * kRowVox + i) * 2];
                     }
                 };
-                auto join = [&](const float (&sa)[4], const float (&sb)[4], v2f (&d)[4]) {
+                auto join = [&](const float (&sa)[4], const float (&sb)[4], f32x2 (&d)[4]) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) d[i] = (v2f){sa[i], sb[i]};
+                    for (int i = 0; i < 4; ++i) d[i] = (f32x2){sa[i], sb[i]};
                 };
                 // the raw voxels of k-step ks as four pairs of k-slots [q][voxel i] (the table in front of the kernel)
-                auto load_raw = [&](int ks, v2f (&d)[4][4]) {
+                auto load_raw = [&](int ks, f32x2 (&d)[4][4]) {
                     float sa[4], sb[4];
                     if (ks == 0) {
                         rdP(0, d[0]); rdP(1, d[1]); rdP(2, d[2]);
@@ -318,7 +305,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                         rdS(6, sa); rdS(7, sb); join(sa, sb, d[3]);
                     }
                 };
-                auto point = [&](int p, const v2f (&d)[4]) -> v2f {
+                auto point = [&](int p, const f32x2 (&d)[4]) -> f32x2 {
                     return p == 0 ? d[0] - d[2] : p == 1 ? d[1] + d[2] : p == 2 ? d[2] - d[1] : d[1] - d[3];
                 };
                 f32x16 acc[4];                                         // (zeroed by the first MFMA of each: its C operand is the constant 0)
@@ -338,8 +325,8 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                 // 0.66 ms + everything else 0.9 ms = the 2.2 ms the unpipelined kernel took).
                 unsigned PA[2][3][4];                                  // [buffer][piece][pair]
                 bf16x8 PB[2][3];
-                v2f D[2][4][4];
-                auto prep = [&](int p, const v2f (&d)[4][4], int buf) {
+                f32x2 D[2][4][4];
+                auto prep = [&](int p, const f32x2 (&d)[4][4], int buf) {
                     // (two-float subtractions: hipcc emits v_pk_add_f32 for a third of them and two scalar adds for the rest; forcing the
                     // packed form everywhere — inline asm — is SLOWER, 1.91 against 1.79 ms: a packed fp32 add is evidently not cheaper
                     // than two scalar ones here.)
@@ -349,7 +336,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                     // hipcc encodes the operand (bf16 -1, 0) as the inline constant -1.0, which the hardware expands differently
                     // (garbage results), and a DOT result needs 3 wait states before a VALU reads it, which inline asm hides from
                     // the hazard recognizer.)
-                    v2f x[4], r1[4], r2[4];
+                    f32x2 x[4], r1[4], r2[4];
                     unsigned hh[4], mm[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) x[q] = point(p, d[q]);
@@ -361,25 +348,25 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                         return;
                     }
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) hh[q] = b3_pk(x[q]);
+                    for (int q = 0; q < 4; ++q) hh[q] = bf16x3::pk(x[q]);
                     if (INT && p != 1) {           // exact in one piece
 #pragma unroll
                         for (int q = 0; q < 4; ++q) { PA[buf][0][q] = hh[q]; PA[buf][1][q] = 0u; PA[buf][2][q] = 0u; }
                         return;
                     }
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) r1[q] = x[q] - b3_unpk(hh[q]);
+                    for (int q = 0; q < 4; ++q) r1[q] = x[q] - bf16x3::unpk(hh[q]);
                     if (INT) {                     // the sum point d1 + d2 <= 510: exact in two
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) { PA[buf][0][q] = hh[q]; PA[buf][1][q] = b3_pk(r1[q]); PA[buf][2][q] = 0u; }
+                        for (int q = 0; q < 4; ++q) { PA[buf][0][q] = hh[q]; PA[buf][1][q] = bf16x3::pk(r1[q]); PA[buf][2][q] = 0u; }
                         return;
                     }
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) mm[q] = b3_pk(r1[q]);
+                    for (int q = 0; q < 4; ++q) mm[q] = bf16x3::pk(r1[q]);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) r2[q] = r1[q] - b3_unpk(mm[q]);
+                    for (int q = 0; q < 4; ++q) r2[q] = r1[q] - bf16x3::unpk(mm[q]);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) { PA[buf][0][q] = hh[q]; PA[buf][1][q] = mm[q]; PA[buf][2][q] = b3_pk(r2[q]); }
+                    for (int q = 0; q < 4; ++q) { PA[buf][0][q] = hh[q]; PA[buf][1][q] = mm[q]; PA[buf][2][q] = bf16x3::pk(r2[q]); }
                 };
                 auto loadB = [&](int ks, int p, int buf) {
 #pragma unroll
@@ -408,7 +395,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                                       else { B3_PIPE(7, 4) B3_PIPE(7, 4) B3_PIPE(7, 4) B3_PIPE(7, 4) B3_PIPE(7, 4) B3_PIPE(7, 4) } } __builtin_amdgcn_sched_barrier(0); }
 #define B3_WIN3 { if (!(DBG & 64)) { B3_PIPE(15, 8) B3_PIPE(15, 8) B3_PIPE(15, 8) } __builtin_amdgcn_sched_barrier(0); }
                 // ---- prologue: tap 8 (fp32), the raw voxels of k-step 0, the fragments of unit 0
-                v2f d8p[4];
+                f32x2 d8p[4];
                 float d8s[4];
                 rdP(8, d8p);
                 rdS(8, d8s);
@@ -417,7 +404,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
                 float v8[4][3];
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const v2f x = point(p, d8p);
+                    const f32x2 x = point(p, d8p);
                     v8[p][0] = x.x; v8[p][1] = x.y;
                     v8[p][2] = p == 0 ? d8s[0] - d8s[2] : p == 1 ? d8s[1] + d8s[2] : p == 2 ? d8s[2] - d8s[1] : d8s[1] - d8s[3];
                 }
@@ -482,20 +469,6 @@ const FirstB3Dbg kFirstB3Dbg[] = {{1, k_conv_first_b3<1>}, {2, k_conv_first_b3<2
                                   {8, k_conv_first_b3<8>}, {64, k_conv_first_b3<64>}, {131, k_conv_first_b3<131>}, {259, k_conv_first_b3<259>},
                                   {399, k_conv_first_b3<399>}};
 
-inline uint16_t b3_bf16_rne(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)(u >> 16);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline double b3_bf16_val(uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return (double)f;
-}
-
 }  // namespace
 
 // does the split kernel serve this first layer (the planner asks before it packs the weights)?
@@ -543,11 +516,7 @@ void conv_first_b3_pack_weights(int Cin, int Cout, const float* w, float* dst_f)
                     if (c >= Cin) continue;
                     const double u = U(p, t9, c, co);
                     uint16_t pc[3];
-                    pc[0] = b3_bf16_rne((float)u);
-                    const double r1 = u - b3_bf16_val(pc[0]);
-                    pc[1] = b3_bf16_rne((float)r1);
-                    const double r2 = r1 - b3_bf16_val(pc[1]);
-                    pc[2] = b3_bf16_rne((float)r2);
+                    bf16x3::split3(u, pc);
                     for (int piece = 0; piece < 3; ++piece)
                         dst[((((size_t)p * 3 + ks) * 3 + piece) * 64 + ln) * 8 + e] = pc[piece];
                 }

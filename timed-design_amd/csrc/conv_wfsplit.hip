@@ -2,7 +2,7 @@
 // + MaxPool; SURVEY.md §8(a) P2a, the call served is reference predict.py:142) — taken OFF the fp32-input matrix pipe:
 // the same F(2,3) x F(2,3) in-plane / direct-z algorithm, but every product runs on v_mfma_f32_32x32x16_bf16 with BOTH operands
 // split exactly into three bf16 pieces (x = h + m + l, round to nearest even at each step), six of the nine piece products
-// kept (l H, m H, h H, m M, h M, h L), fp32 accumulation — the scheme of conv_wino.hip's k_wino_gemm_b3 and of
+// kept (l H, m H, h H, m M, h M, h L), fp32 accumulation — the scheme of bf16x3.h, as conv_wino.hip's k_wino_gemm_b3_* and
 // conv_first_b3.hip, error of the size of one fp32 rounding per product.  The fp32 pipe is 1/16 of the bf16 rate on gfx950:
 // six bf16 products cost 3/8 of the matrix-pipe cycles of one fp32 product.
 //
@@ -25,19 +25,13 @@
 //     (the tile is the in-plane window, the z mate is the neighbouring register), stores.
 //
 // One barrier per step, one more per phase (the first position's transform has nothing to hide behind: ~3 % bubble).
+#include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -56,10 +50,6 @@ struct ConvWfsArgs {
     int64_t nframes;
     unsigned nslots;                  // ceil(nframes / 8) * 8 * ncp logical units
 };
-
-__device__ __forceinline__ unsigned wfs_pk(float x, float y) {          // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((v2f){x, y}, bf16x2));
-}
 
 // One LDS-DMA: 64 lanes x 16 bytes from (wave-uniform base + each lane's 32-bit byte offset) to LDS at lds_dst + 16 lane.
 // Spelled in asm for the scalar-base form: through the builtin the compiler kept a 64-bit lane address per load, hoisted all
@@ -261,14 +251,7 @@ __global__ void __launch_bounds__(512, 1) k_conv_wfs(const ConvWfsArgs a) {
         for (int k = 0; k < 4; ++k) v[k] = sj1 * t1[k] + sj2 * t2[k];
         unsigned hp[2], mp[2], lp[2];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const float x0 = v[2 * k], x1 = v[2 * k + 1];
-            hp[k] = wfs_pk(x0, x1);
-            const float r0 = x0 - __builtin_bit_cast(float, hp[k] << 16), r1 = x1 - __builtin_bit_cast(float, hp[k] & 0xffff0000u);
-            mp[k] = wfs_pk(r0, r1);
-            const float q0 = r0 - __builtin_bit_cast(float, mp[k] << 16), q1 = r1 - __builtin_bit_cast(float, mp[k] & 0xffff0000u);
-            lp[k] = wfs_pk(q0, q1);
-        }
+        for (int k = 0; k < 2; ++k) bf16x3::split(v[2 * k], v[2 * k + 1], hp[k], mp[k], lp[k]);
         u32x2* const dst = reinterpret_cast<u32x2*>(V4 + buf * VBUF + wslot) + c;
         dst[0] = (u32x2){hp[0], hp[1]};
         dst[2 * VPIECE] = (u32x2){mp[0], mp[1]};
@@ -521,20 +504,6 @@ struct WfsDbg { int code; WfsKernel k; };
 const WfsDbg kWfsDbg[] = {WFS_DBG(1), WFS_DBG(2), WFS_DBG(3), WFS_DBG(4), WFS_DBG(8), WFS_DBG(16), WFS_DBG(20), WFS_DBG(21), WFS_DBG(32), WFS_DBG(29), WFS_DBG(533), WFS_DBG(1045), WFS_DBG(1565), WFS_DBG(1024), WFS_DBG(2048), WFS_DBG(4096), WFS_DBG(8192), WFS_DBG(6144)};
 #undef WFS_DBG
 
-inline uint16_t wfs_bf16_rne(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)(u >> 16);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline double wfs_bf16_val(uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return (double)f;
-}
-
 size_t wfs_lds_bytes(int D, int H, int W) {
     const int rsl = (D * H + 1) * (W + 1);
     const int rpad = (4 * rsl + 63) / 64 * 64;
@@ -594,11 +563,7 @@ void conv_wfs_pack_weights(const ConvWfsPlan& p, const float* w, float* dst_f) {
                     for (int bb = 0; bb < 4; ++bb) {
                         const double u = G[bb][0] * t[0] + G[bb][1] * t[1] + G[bb][2] * t[2];
                         uint16_t pc[3];
-                        pc[0] = wfs_bf16_rne((float)u);
-                        const double r1 = u - wfs_bf16_val(pc[0]);
-                        pc[1] = wfs_bf16_rne((float)r1);
-                        const double r2 = r1 - wfs_bf16_val(pc[1]);
-                        pc[2] = wfs_bf16_rne((float)r2);
+                        bf16x3::split3(u, pc);
                         const size_t stepi = (size_t)(pass * p.nkh + kh) * 16 + (aa * 4 + bb);
                         for (int piece = 0; piece < 3; ++piece) {
                             const size_t frag = stepi * kWfsFrags + (size_t)(dz * 2 + n) * 3 + piece;

@@ -93,7 +93,6 @@ void th_knobs_read(ThKnobs* k) {
     num("TH_WF_NOBLK", &k->wf_noblk, 0, 1);
     if (const char* e = getenv("TH_WINO_PIECE")) { k->wino_piece = std::max(0ll, atoll(e)); if (k->wino_piece) note("TH_WINO_PIECE", e); }
     num("TH_WINO_DBG", &k->wino_dbg, 0, 1 << 20);
-    num("TH_WINO_VAR", &k->wino_var, 0, 3);
     num("TH_WINO_B3VAR", &k->wino_b3var, 0, 2);
     num("TH_WINO_NOMID", &k->wino_nomid, 0, 1);
 }
