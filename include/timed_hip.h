@@ -304,6 +304,36 @@ typedef struct th_analysis_totals {
 int th_analyse_probs(int device, const void* matrix, int dtype, int64_t n, int64_t k, const int8_t* col_res, const int8_t* true_res,
                      int8_t* pred_out, int8_t* rank_out, double* entropy_out, th_analysis_totals* totals);
 
+/* ---- per-class evaluation: analyse_rotamers.py / predict.py --output_auc — what the reference's calculate_rotamer_metrics
+ * (design_utils/analyse_utils.py:731-898) computes with sklearn for a 338-class rotamer model: k x k confusion, top-k over the k
+ * columns, and the integer table behind the ROC AUC one-vs-one and one-vs-rest.  matrix: host [n, k] of TH_F16 or TH_F32,
+ * 1 <= k <= 1024, n < 2^31; true_class: host int16[n], 0..k-1 or -1 (unlabelled).  A row is SCORED when it is labelled and holds
+ * no NaN and no infinity.  Per row:
+ *   pred_out[i] = arg-max under th_argmax_letters' rules (first maximum, first NaN);
+ *   rank_out[i] = #{c : x_c > x_t or (x_c == x_t and c < t)} for the true class t; a row holding a NaN or an infinity ranks 0 if
+ *                 pred == t, else k; -1 for an unlabelled row.
+ * Totals (all int64, independent of grid, staging blocks and arrival order — two calls give the same bytes):
+ *   confusion[t * k + p]   labelled rows of true class t predicted as p;
+ *   rank_hist[r]           labelled rows by rank_out; bucket k: a non-finite row that was missed;
+ *   scored_count[c]        n_c, the scored rows of class c;
+ *   pair_u2[a * k + b]     U2[a][b] = sum over scored rows i of class a and j of class b of 2 [x[i][a] > x[j][a]] + [x[i][a] == x[j][a]]
+ *                          (twice the Mann-Whitney statistic of column a, ties half; numeric comparison of the stored values,
+ *                          -0 == +0; U2[a][a] = 0).  auc(a|b) = U2[a][b] / (2 n_a n_b).  NULL skips the AUC sweep: the other
+ *                          outputs are the same bytes either way;
+ *   counts                 labelled rows, rows holding a NaN or an infinity (labelled or not), scored rows.
+ * The matrix is staged in the blocks of th_analyse_probs (TH_ANALYSIS_BLOCK_ROWS overrides the row count, results unchanged); the
+ * AUC sweep is a second pass that re-stages the blocks unless the whole matrix is one block, which stays resident.  Device memory
+ * beside the two staging slots: 8 k^2 (+ 8 k^2 with pair_u2) bytes of totals and, with pair_u2, 21 bytes per row plus the sort's
+ * scratch.  TH_EINVAL: NULL totals, dtype, k, n, or a label outside -1..k-1.  n = 0 returns zero totals. */
+typedef struct th_class_counts { int64_t n_labelled, n_nonfinite, n_scored; } th_class_counts;
+int th_analyse_classes(int device, const void* matrix, int dtype, int64_t n, int64_t k, const int16_t* true_class,
+                       int16_t* pred_out, int16_t* rank_out,           /* [n] each, may be NULL                       */
+                       int64_t* confusion,                             /* [k*k], [true][predicted], labelled rows     */
+                       int64_t* rank_hist,                             /* [k+1], bucket k: non-finite row, missed     */
+                       int64_t* scored_count,                          /* [k]   n_c                                   */
+                       int64_t* pair_u2,                               /* [k*k] U2[a][b]; NULL: skip the AUC sweep    */
+                       th_class_counts* counts);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

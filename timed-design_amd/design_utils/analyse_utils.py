@@ -133,3 +133,82 @@ def extract_prediction_entropy_to_dict(model_pred_path, model_map_path, rotamer_
     plan = utils.SequencePlan(utils.load_datasetmap(model_map_path, is_old=is_old))
     entropy = calculate_prediction_entropy(prediction_matrix)
     return {key: entropy[plan.rows(key)] for key in plan.keys}
+
+
+# ---- per-class rotamer metrics (analyse_rotamers.py; computed on the GPU by timed_hip.analysis) -------------------------------
+def _narrow(matrix: np.ndarray) -> np.ndarray:
+    """float16 / float32 matrices as they are; others to float16 when that is exact (the probability CSVs predict.py writes),
+    else to float32"""
+    if matrix.dtype in (np.float16, np.float32):
+        return matrix
+    a64 = matrix.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        h = a64.astype(np.float16)
+    return h if np.array_equal(h.astype(np.float64), a64, equal_nan=True) else a64.astype(np.float32)
+
+
+def calculate_rotamer_metrics(pdb_to_probability, pdb_to_rotamer: dict, rot_categories: t.List[str], suffix: str, output_path,
+                              device: int = 0) -> dict:
+    """reference analyse_utils.py:731-898: per-class metrics of a rotamer model — ROC AUC one-vs-one and one-vs-rest, the
+    classification report, top-1..5 accuracy, macro precision and recall, prediction bias and the plain and label-weighted
+    confusion matrices — for {key: rows of probabilities} (a dict of lists, or the lazy mapping extract_sequence_from_pred_matrix
+    returns) against {key: rotamer class per residue} (NaN / None = untagged).  Same pairing rules: a key missing from
+    ``pdb_to_rotamer``, or whose lengths differ, is reported on stdout and skipped.  Everything is derived from the integer
+    totals of one GPU call (timed_hip.analysis.analyse_class_matrix, which documents every key and the one deliberate
+    difference: the AUC is of the matrix as stored, no residual is spread over rows that do not sum to 1).
+
+    Writes results_{suffix}.txt (the reference's line labels), results_{suffix}.json (the whole dict) and
+    cm_{suffix}_unweighted.csv / cm_{suffix}_weighted.csv (k x k, np.savetxt's format) where the reference draws two PNGs.
+    Returns the dict (the reference returns None)."""
+    import json
+    from pathlib import Path
+
+    from timed_hip import analysis, textio
+    k = len(rot_categories)
+    output_path = Path(output_path)
+    output_path.mkdir(parents=True, exist_ok=True)
+    parts, labels = [], []
+    for pdb in pdb_to_probability.keys():
+        if pdb in pdb_to_rotamer:
+            rows = pdb_to_probability.matrix(pdb) if hasattr(pdb_to_probability, "matrix") else \
+                np.asarray(pdb_to_probability[pdb]).reshape(-1, k)
+            if len(rows) == len(pdb_to_rotamer[pdb]):
+                parts.append(np.asarray(rows))
+                labels.append(np.array([np.nan if v is None else v for v in pdb_to_rotamer[pdb]], dtype=np.float64).reshape(-1))
+            else:
+                print(f"Error with pdb code {pdb} - Length Mismatch")
+        else:
+            print(f"Error with pdb code {pdb}")
+    y_pred = np.concatenate(parts).reshape(-1, k) if parts else np.empty((0, k), np.float16)
+    y_true = np.concatenate(labels) if labels else np.empty(0)
+    true_class = np.where(np.isnan(y_true), -1, y_true).astype(np.int64)
+    results = analysis.analyse_class_matrix(_narrow(y_pred), true_class, categories=list(rot_categories), device=device)
+    print("Metrics AUC_OVR")
+    print(results["auc_ovr"])
+    print("Metrics AUC_OVO")
+    print(results["auc_ovo"])
+    print(", ".join(f"{name}: {results[key]}" for name, key in (
+        ("Accuracy", "accuracy_1"), ("accuracy_2", "accuracy_2"), ("accuracy_3", "accuracy_3"), ("accuracy_4", "accuracy_4"),
+        ("accuracy_5", "accuracy_5"), ("precision", "precision"), ("recall", "recall"))))
+    with open(output_path / f"results_{suffix}.txt", "w") as f:
+        f.write(f"Metrics AUC_OVR: {results['auc_ovr']}\n")
+        f.write(f"Metrics AUC_OVO: {results['auc_ovo']}\n")
+        f.write(f"Metrics AUC_OVR (classes present): {results['auc_ovr_present']}\n")
+        f.write(f"Metrics Macro-Precision: {results['precision']}\n")
+        f.write(f"Metrics Macro-Recall: {results['recall']}\n")
+        f.write(f"Accuracy: {results['accuracy_1']}\n")
+        for kk in range(2, 6):
+            f.write(f"accuracy_{kk}: {results[f'accuracy_{kk}']}\n")
+        f.write(f"precision: {results['precision']}\nrecall: {results['recall']}\n")
+        f.write("Report:\n")
+        f.write(f"{results['report']}\n")
+        f.write("Bias:\n")
+        f.write(f"{results['bias']}\n")
+    with open(output_path / f"results_{suffix}.json", "w") as f:
+        json.dump(results, f, indent=1, allow_nan=False)
+        f.write("\n")
+    for kind in ("unweighted", "weighted"):
+        cm = np.zeros((k, k)) if results[f"{kind}_cm"] is None else np.array(results[f"{kind}_cm"], dtype=np.float64)
+        with open(output_path / f"cm_{suffix}_{kind}.csv", "wb") as f:
+            f.write(textio.format_csv(cm))
+    return results

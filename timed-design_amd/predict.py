@@ -455,6 +455,7 @@ def load_dataset_and_predict(
     model_loader=None,
     gather=None,
     output_analysis: bool = False,
+    output_auc: bool = False,
 ) -> (np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray):
     """reference predict.py:28-194 — same leading parameters and return tuple (flat_dataset_map, pdb_to_sequence,
     pdb_to_probability, pdb_to_real_sequence, pdb_to_consensus, pdb_to_consensus_prob).  ``start_batch`` keeps the
@@ -464,8 +465,11 @@ def load_dataset_and_predict(
     a GPU per call), ``model_loader(path, device=...)`` (default ``timed_hip.engine.load_model``) and ``gather`` (a
     row-gather transport from ``timed_hip.distributed``; default: RCCL when WORLD_SIZE > 1) and ``output_analysis``
     (after each model's FASTA, rank 0 writes <model>_analysis.json, <model>_entropy.csv and <model>_per_structure.csv — see
-    _write_analysis)."""
+    _write_analysis) and ``output_auc`` (20-class models with a 4-column map: rank 0 also writes <model>_auc.json — see
+    _write_auc; rotamer models are evaluated per class by analyse_rotamers.py)."""
     path_to_output = Path(path_to_output)
+    if output_auc and predict_rotamers:
+        raise ValueError("--output_auc scores the 20 residue classes; evaluate a rotamer model per class with analyse_rotamers.py")
     n_classes = N_ROTAMER_CLASSES if predict_rotamers else N_RESIDUE_CLASSES
     rank, world, local_rank, gather = _distributed_context(gather)
     sharded = world > 1 or gather is not None      # an explicit transport selects the shard + gather path even for 1 rank
@@ -558,6 +562,8 @@ def load_dataset_and_predict(
             if output_analysis:
                 _write_analysis(matrix, flat_dataset_map, plan.result(), model_name, path_to_output, predict_rotamers,
                                 flat_categories, device_ids[0])
+            if output_auc:
+                _write_auc(matrix, flat_dataset_map, plan.result(), model_name, path_to_output, device_ids[0])
     finally:
         if pending_handles is not None:          # a model that was prefetched but never used (an error above)
             try:
@@ -628,6 +634,32 @@ def _write_analysis(matrix, flat_dataset_map, plan, model_name, path_to_output, 
         return "n/a" if v is None else f"{v:.4f}"
     print(f"[analysis] {model_name}: top-1 {show(metrics['accuracy_1'])}  top-3 {show(metrics['accuracy_3'])}  "
           f"macro recall {show(metrics['recall'])}  mean entropy {show(metrics['mean_entropy'])} bits  N={got.n_labelled}")
+
+
+def _write_auc(matrix, flat_dataset_map, plan, model_name, path_to_output, device):
+    """--output_auc for one 20-class model: ROC AUC one-vs-one and one-vs-rest of the float16 matrix the FASTA was read off against
+    the residue column of a 4-column map, on the GPU (timed_hip.analysis, th_analyse_classes).  Writes <model>_auc.json: the keys
+    of roc_auc_from_pairs (auc_ovo, auc_ovr, auc_ovr_present, auc_ovr_per_class in the order ACDEFGHIKLMNPQRSTVWY,
+    n_classes_present) plus n_scored.  A "<pdb> <count>" map carries no truth: every value null."""
+    import json
+    from timed_hip import analysis
+    n = matrix.shape[0]
+    if n != plan.n_rows:
+        raise ValueError(f"{model_name}: the prediction matrix has {n} rows, the dataset map {plan.n_rows}")
+    if plan.old_datasetmap:
+        true_res = analysis.residue_indices(np.asarray(flat_dataset_map)[:, 3])
+    else:
+        true_res = np.full(n, -1, np.int8)
+    got = analysis.analyse_classes(matrix, true_res, device=device, auc=True, rows=False)
+    result = {"model": model_name, "n_scored": got.n_scored, **analysis.roc_auc_from_pairs(got.pair_u2, got.scored_count)}
+    with open(path_to_output / f"{model_name}_auc.json", "w") as f:
+        json.dump(result, f, indent=1, allow_nan=False)
+        f.write("\n")
+
+    def show(v):
+        return "n/a" if v is None else f"{v:.4f}"
+    print(f"[auc] {model_name}: OvO {show(result['auc_ovo'])}  OvR {show(result['auc_ovr'])}  "
+          f"classes present {result['n_classes_present']}  N={got.n_scored}")
 
 
 def _predict_sharded(model, gather, rank, world, dataset_path, flat_dataset_map, batch_size, start_batch, frames_per_call, files,
@@ -709,6 +741,7 @@ CLI_FLAGS = (
     ("--path_to_blacklist", dict(type=str, default=None, help="directory of PDB lists to refuse (training-set structures)")),
     ("--path_to_output", dict(type=str, default=".", help="output directory (asked before it is created)")),
     ("--output_analysis", dict(action="store_true", help="also write <model>_analysis.json (top-k accuracy, macro precision / recall, confusion, bias, BLOSUM62 similarity), <model>_entropy.csv and <model>_per_structure.csv")),
+    ("--output_auc", dict(action="store_true", help="also write <model>_auc.json (ROC AUC one-vs-one and one-vs-rest of the 20 residue classes; rotamer models: analyse_rotamers.py)")),
     ("--predict_rotamers", dict(action="store_true", help="the model predicts 338 rotamer classes instead of 20 residues")),
     ("--is_structure_nmr", dict(action="store_true", help="merge the states of an NMR ensemble into a consensus")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
@@ -755,7 +788,8 @@ def _main_predict(args, required, devices):
         dataset_map_path=Path(args.path_to_datasetmap), blacklist=required.get("blacklist"),
         predict_rotamers=args.predict_rotamers, is_consensus=args.is_structure_nmr,
         path_to_output=Path(args.path_to_output), device=getattr(args, "device", 0), devices=devices,
-        frames_per_call=getattr(args, "frames_per_call", None), output_analysis=bool(getattr(args, "output_analysis", False)))
+        frames_per_call=getattr(args, "frames_per_call", None), output_analysis=bool(getattr(args, "output_analysis", False)),
+        output_auc=bool(getattr(args, "output_auc", False)))
 
 
 if __name__ == "__main__":

@@ -80,6 +80,7 @@ PROTOTYPES = {
     "th_csv_fill": (_i, [C.c_char_p, _i64, C.c_char, _i64, _i, _i, _vp]),
     "th_argmax_letters": (_i, [_vp, _i, _i64, _i64, C.c_char_p, _vp, _vp]),
     "th_analyse_probs": (_i, [_i, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "th_analyse_classes": (_i, [_i, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "th_h5_read_chunked": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i, _pi64, _pi64, _i, _i, _pi, _i]),
     "th_h5_read_chunked_as": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i, _pi64, _pi64, _i, _i, _pi, _i, _i]),
     "th_h5_read_contiguous_as": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i64, _i, _i]),
