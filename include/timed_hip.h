@@ -334,6 +334,46 @@ int th_analyse_classes(int device, const void* matrix, int dtype, int64_t n, int
                        int64_t* pair_u2,                               /* [k*k] U2[a][b]; NULL: skip the AUC sweep    */
                        th_class_counts* counts);
 
+/* ---- structure properties: analyse_properties.py — the packing density of the reference's design_utils/analyse_utils.py
+ * (tag_packing_density :44-86: the atomic contact number of Weiss 2007; _extract_packdensity_from_polypeptide :149-201: its
+ * per-residue summary), for a BATCH of structures in one submission.  The reference loops over the atoms of one structure in
+ * NumPy, O(N^2) float64 per structure.  All arrays are host memory.
+ *   device        HIP device index;
+ *   xyz           double[total][3], the atoms of all structures, structure after structure (Angstrom; any value, NaN and
+ *                 infinities included);
+ *   total         number of atoms, 0 <= total <= 2^31 - 257;
+ *   offsets       int64[n_structures + 1]: structure s owns atoms offsets[s] .. offsets[s + 1]; offsets[0] = 0, non-decreasing,
+ *                 offsets[n_structures] = total.  Pairs are formed within a structure only; a structure may be empty;
+ *   radius        any double;
+ *   group         int32[total]: the residue (0 .. n_groups - 1, an index within the batch) that atom i is reported under, or -1
+ *                 for an atom that is only a neighbour.  The atoms of one residue are consecutive.  Read only when n_groups > 0;
+ *   selected      uint8[total]: non-zero where the atom enters its residue's value.  Read only when n_groups > 0;
+ *   n_groups      number of residues, 0 <= n_groups <= 2^31 - 1;
+ *   density_out   int32[total] or NULL (the per-atom counts are then not copied back):
+ *                   density[i] = #{ j in the structure of i, j == i included : sqrt((dx*dx + dy*dy) + dz*dz) < radius } - 1
+ *                 with dx = x_j - x_i ..., evaluated in float64 in exactly this order, every product and sum rounded on its own (no
+ *                 fused multiply-add), the root correctly rounded: NumPy's np.sqrt(np.square(xyz - xyz[i]).sum(axis=1)) < radius,
+ *                 bit for bit, pairs at a distance of "exactly" the radius included.  Hence: the atom counts itself and 1 is
+ *                 subtracted, so an atom with a NaN or infinite coordinate gets -1; atoms at equal coordinates count each other;
+ *                 radius <= 0 or NaN gives -1 everywhere.  (The kernel compares the squared distance with th_packing_threshold(radius).)
+ *   residue_out   double[n_groups] (required when n_groups > 0): the reference's running value over the SELECTED atoms of the
+ *                 residue in index order:  cur = -1;  for each: cur = (cur == -1) ? density : (cur + density) / 2.  It is not the
+ *                 mean and the order matters; -1.0 for a residue without a selected atom; like the reference, a leading selected atom
+ *                 whose density is -1 is indistinguishable from "none yet" and is replaced by the next;
+ *   kernel_ms_out NULL, or receives the device time of the two kernels (events around them), in milliseconds.
+ * Integers and exact halves of small integers only: independent of grid and arrival order, two calls give the same bytes.
+ * Device memory: 28 bytes per atom + 12 per 256 atoms of every structure (+ 1 per atom and 16 per residue with n_groups > 0).
+ * TH_EINVAL, before anything is launched or written: a NULL that is required, a negative size, total or n_groups above the limit,
+ * offsets not as described, a group value outside -1 .. n_groups - 1, a residue whose atoms are not consecutive.  total = 0
+ * (n_structures = 0, or only empty structures) returns without launching: residue_out is all -1.0. */
+int th_packing_density(int device, const double* xyz, int64_t total, const int64_t* offsets, int64_t n_structures, double radius,
+                       const int32_t* group, const uint8_t* selected, int64_t n_groups, int32_t* density_out, double* residue_out,
+                       double* kernel_ms_out);
+/* T(radius): the smallest double whose correctly rounded square root is >= radius, so that  sqrt(s) < radius  <=>  s < T  for every
+ * double s >= +0, infinite or NaN.  Not radius * radius in general.  0 for radius <= 0, radius itself when it is NaN or +infinity.
+ * Host code. */
+double th_packing_threshold(double radius);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

@@ -135,6 +135,32 @@ def extract_prediction_entropy_to_dict(model_pred_path, model_map_path, rotamer_
     return {key: entropy[plan.rows(key)] for key in plan.keys}
 
 
+# ---- structure properties (analyse_properties.py; packing density computed on the GPU by timed_hip.structure) -----------------
+def extract_packdensity_from_ampal(pdb, load_pdb: bool = True, atom_filter: str = "ca", radius: float = 7.0, device: int = 0) -> t.List[t.List[float]]:
+    """reference analyse_utils.py:204-234: ``[[packing density of each residue of the first chain]]`` — the atomic contact number
+    within ``radius`` (the reference always uses 7) summarised per residue with the reference's running half-average over the
+    atoms ``atom_filter`` selects ("ca": atoms named C and CA, the reference's substring test; "backbone"; "all"; "calpha" is
+    an addition).  ``pdb`` is a path (plain or gzipped PDB file) or, with ``load_pdb=False``, a ``timed_hip.pdbio.Model`` — where
+    the reference takes an ampal Assembly.  The object model differs from ampal's: which atoms are neighbours and which residues
+    are reported is the structure rule written out in timed_hip/structure.py (first model, all non-hydrogen ATOM and HETATM atoms
+    as neighbours, the non-hetero residues of the first chain reported), unpinned against ampal; the arithmetic is the
+    reference's, bit for bit.  Values are floats where the reference mixes NumPy integers and floats."""
+    from timed_hip import structure
+    model = structure.first_model(pdb) if load_pdb else pdb
+    res = structure.packing_density([model], radius=radius, atom_filter=atom_filter, device=device)[0]
+    return [[float(v) for v in res.residue_density]]
+
+
+def extract_bfactor_from_ampal(pdb_path, load_pdb: bool = True) -> t.List[t.List[float]]:
+    """reference analyse_utils.py:112-146: one list per chain with the B-factor of the first atom of each residue (AlphaFold2
+    models carry the pLDDT there).  ``pdb_path`` is a path or, with ``load_pdb=False``, a ``timed_hip.pdbio.Model``.  Differs
+    from ampal's object model: chains are the chain identifiers of the first model's ATOM records in file order (ampal splits
+    polypeptides by its own rules and skips ligands and nucleic acids); a missing B-factor column reads as NaN.  Host code."""
+    from timed_hip import structure
+    model = structure.first_model(pdb_path) if load_pdb else pdb_path
+    return structure.residue_bfactors(model)
+
+
 # ---- per-class rotamer metrics (analyse_rotamers.py; computed on the GPU by timed_hip.analysis) -------------------------------
 def _narrow(matrix: np.ndarray) -> np.ndarray:
     """float16 / float32 matrices as they are; others to float16 when that is exact (the probability CSVs predict.py writes),

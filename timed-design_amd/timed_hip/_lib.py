@@ -81,6 +81,8 @@ PROTOTYPES = {
     "th_argmax_letters": (_i, [_vp, _i, _i64, _i64, C.c_char_p, _vp, _vp]),
     "th_analyse_probs": (_i, [_i, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "th_analyse_classes": (_i, [_i, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "th_packing_density": (_i, [_i, _vp, _i64, _vp, _i64, _d, _vp, _vp, _i64, _vp, _vp, _pd]),
+    "th_packing_threshold": (_d, [_d]),
     "th_h5_read_chunked": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i, _pi64, _pi64, _i, _i, _pi, _i]),
     "th_h5_read_chunked_as": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i, _pi64, _pi64, _i, _i, _pi, _i, _i]),
     "th_h5_read_contiguous_as": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i64, _i, _i]),

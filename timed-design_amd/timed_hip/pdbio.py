@@ -2,6 +2,7 @@
 gzipped (the reference ships tests/testing_files/1ubq.pdb1.gz and passes ``is_pdb_gzipped`` to aposteriori, ui.py:81).
 Only what voxelisation needs: coordinates, atom / residue names, chain, residue number (+ insertion code), element,
 model number.  Alternate locations: the first one seen for an atom name within a residue wins (blank or 'A').
+The temperature factor (columns 61-66; AlphaFold2 writes pLDDT there) is kept per atom for timed_hip.structure.
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ class Residue:
     atoms: Dict[str, np.ndarray] = field(default_factory=dict)   # atom name -> xyz (float64)
     elements: Dict[str, str] = field(default_factory=dict)
     hetero: bool = False
+    bfactors: Dict[str, float] = field(default_factory=dict)     # atom name -> B-factor (NaN when the column is absent or unparsable)
 
 
 @dataclass
@@ -79,5 +81,9 @@ def read_pdb(path) -> List[Model]:
                 res.atoms[name] = xyz
                 el = line[76:78].strip() if len(line) >= 78 else ""
                 res.elements[name] = el or name[:1]
+                try:
+                    res.bfactors[name] = float(line[60:66])
+                except ValueError:                   # a short line, blanks, or not a number
+                    res.bfactors[name] = float("nan")
     close_model()
     return models

@@ -1,0 +1,213 @@
+"""Structure properties of PDB files, batched on the GPU: packing density (atomic contact number, Weiss 2007) per atom and per
+residue — the reference's ``tag_packing_density`` / ``_extract_packdensity_from_polypeptide`` (design_utils/analyse_utils.py:44-86,
+:149-201) through th_packing_density (csrc/packdensity.hip) — and the B-factor column.
+
+The ARITHMETIC is pinned to the reference's own functions, bit for bit (tests/golden/packdensity_golden.npz is their output).
+
+    *** STRUCTURE RULE: PARITY UNPINNED AGAINST AMPAL ***  Which atoms of a file are neighbours and which residues are reported is
+    decided in the reference by ampal's object model (``ampal.load_pdb``), and ampal is neither in the reference tree nor installed
+    where this project is built — the same standing as timed_hip/voxeliser.py.  The rule implemented here is this project's own:
+
+    * the first model of the file (``pdbio.read_pdb(path)[0]``); of alternate locations the first one seen per atom name;
+    * NEIGHBOURS are all non-hydrogen atoms of ATOM and HETATM records, waters and ligands included (``include_hetero=False``
+      keeps ATOM records only).  Hydrogen: element column ``H`` (any case); where the column is absent, the first letter of the
+      atom name;
+    * REPORTED residues are the non-hetero residues of the first chain — the chain of the first ATOM residue —, which is what the
+      reference's ``assembly[0]`` iterates; ``all_chains=True`` reports the non-hetero residues of every chain;
+    * atoms keep file order (the per-residue value depends on it).
+
+Atom filters, under the reference's names (which atoms of a residue enter its value; hydrogens never do):
+    ``"all"``       every non-hydrogen atom
+    ``"backbone"``  N, CA, C, O
+    ``"ca"``        the reference tests ``atom.res_label in "CA"`` — a SUBSTRING test on the string "CA", so it selects the atoms
+                    named ``C`` and ``CA`` (and a nameless or ``A`` atom).  Reproduced as it is: published numbers were made with it
+    ``"calpha"``    CA alone (an addition of this project)
+The per-residue value is the reference's running half-average over the selected atoms in file order, not their mean (see
+include/timed_hip.h, th_packing_density).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import _lib, pdbio
+
+ATOM_FILTERS = ("all", "ca", "backbone", "calpha")
+_BACKBONE = ("N", "CA", "C", "O")
+BATCH_BYTES = 256 << 20            # host bytes of atom arrays handed to one th_packing_density call
+_ATOM_BYTES = 3 * 8 + 4 + 1 + 4    # xyz, group, selected, density
+
+
+def atom_selected(name: str, atom_filter: str) -> bool:
+    """Does a (non-hydrogen) atom of this name enter its residue's value under ``atom_filter``?"""
+    if atom_filter == "all":
+        return True
+    if atom_filter == "backbone":
+        return name in _BACKBONE
+    if atom_filter == "ca":
+        return name in "CA"            # the reference's substring test: "C", "CA", "A", ""
+    if atom_filter == "calpha":
+        return name == "CA"
+    raise ValueError(f"Atom Filter function {atom_filter} not in {ATOM_FILTERS}")
+
+
+def is_hydrogen(name: str, element: str) -> bool:
+    el = element.strip().upper()
+    if not el or not el[0].isalpha():          # no element column and a name like "1HB": pdbio fell back to the name's first character
+        el = name.lstrip("0123456789 ").upper()[:1]
+    return el == "H"
+
+
+@dataclass
+class Layout:
+    """One structure as th_packing_density takes it."""
+    xyz: np.ndarray                    # [n, 3] float64, neighbours in file order
+    group: np.ndarray                  # [n] int32: index into ``residues`` or -1
+    selected: np.ndarray               # [n] uint8
+    residues: List[pdbio.Residue]      # reported residues
+    atom_names: List[Tuple[int, str]]  # per atom: (index into the model's residues, atom name)
+
+
+def first_model(structure) -> pdbio.Model:
+    if isinstance(structure, pdbio.Model):
+        return structure
+    models = pdbio.read_pdb(structure)
+    if not models:
+        return pdbio.Model(1, [])
+    return models[0]
+
+
+def reported_residues(model: pdbio.Model, all_chains: bool = False) -> List[pdbio.Residue]:
+    polymer = [r for r in model.residues if not r.hetero]
+    if all_chains or not polymer:
+        return polymer
+    return [r for r in polymer if r.chain == polymer[0].chain]
+
+
+def layout(model: pdbio.Model, atom_filter: str = "ca", include_hetero: bool = True, all_chains: bool = False) -> Layout:
+    """Apply the structure rule (module docstring) to one model."""
+    atom_selected("CA", atom_filter)           # raises for an unknown filter
+    reported = {id(r): k for k, r in enumerate(reported_residues(model, all_chains))}
+    xyz, group, selected, names = [], [], [], []
+    for ri, res in enumerate(model.residues):
+        if res.hetero and not include_hetero:
+            continue
+        g = reported.get(id(res), -1)
+        for name, pos in res.atoms.items():
+            if is_hydrogen(name, res.elements.get(name, "")):
+                continue
+            xyz.append(pos)
+            group.append(g)
+            selected.append(1 if g >= 0 and atom_selected(name, atom_filter) else 0)
+            names.append((ri, name))
+    residues = [None] * len(reported)
+    for r in model.residues:
+        if id(r) in reported:
+            residues[reported[id(r)]] = r
+    return Layout(np.array(xyz, dtype=np.float64).reshape(-1, 3), np.array(group, dtype=np.int32), np.array(selected, dtype=np.uint8),
+                  residues, names)
+
+
+def packing_threshold(radius: float) -> float:
+    """T with sqrt(s) < radius <=> s < T for every double s (th_packing_threshold; host code, no GPU needed)."""
+    return float(_lib.load().th_packing_threshold(float(radius)))
+
+
+def contact_numbers(xyz, offsets, radius: float = 7.0, group=None, selected=None, n_groups: int = 0, device: int = 0,
+                    atoms: bool = True, timing: Optional[dict] = None):
+    """One th_packing_density call.  ``xyz`` [total, 3] float64, ``offsets`` [S + 1]; ``group`` / ``selected`` [total] with
+    ``n_groups`` residues (or none).  Returns (int32 [total] or None when ``atoms`` is false, float64 [n_groups]).  ``timing``: a
+    dict that receives ``kernel_ms``."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    if offsets.size < 1:
+        raise ValueError("offsets needs at least one entry")
+    total = xyz.shape[0]
+    if n_groups:
+        group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        selected = np.ascontiguousarray(selected, dtype=np.uint8).reshape(-1)
+        if group.size != total or selected.size != total:
+            raise ValueError(f"group and selected need {total} entries")
+    density = np.empty(total, np.int32) if atoms else None
+    residue = np.empty(int(n_groups), np.float64)
+    ms = C.c_double(0.0)
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.load().th_packing_density(int(device), ptr(xyz), total, ptr(offsets), offsets.size - 1, float(radius),
+                                              ptr(group) if n_groups else None, ptr(selected) if n_groups else None, int(n_groups),
+                                              ptr(density), ptr(residue) if n_groups else None, C.byref(ms) if timing is not None else None))
+    if timing is not None:
+        timing["kernel_ms"] = ms.value
+    return density, residue
+
+
+@dataclass
+class StructureDensity:
+    atom_density: np.ndarray           # [atoms] int32, the neighbours of the structure in file order
+    residue_density: np.ndarray        # [residues] float64
+    residues: List[pdbio.Residue]      # the reported residues
+    layout: Layout
+
+
+def cut_batches(sizes: Sequence[int], budget_bytes: int = BATCH_BYTES) -> List[Tuple[int, int]]:
+    """[lo, hi) runs of consecutive structures whose atom arrays fit ``budget_bytes`` (a structure above it goes alone)."""
+    runs, lo, used = [], 0, 0
+    for k, n in enumerate(sizes):
+        need = int(n) * _ATOM_BYTES
+        if k > lo and used + need > budget_bytes:
+            runs.append((lo, k))
+            lo, used = k, 0
+        used += need
+    if len(sizes) > lo:
+        runs.append((lo, len(sizes)))
+    return runs
+
+
+def packing_density_layouts(layouts: Sequence[Layout], radius: float = 7.0, device: int = 0, budget_bytes: int = BATCH_BYTES,
+                            stats: Optional[dict] = None) -> List[StructureDensity]:
+    """The layouts through th_packing_density in as few calls as ``budget_bytes`` allows.  ``stats`` receives ``submissions``."""
+    out: List[StructureDensity] = []
+    runs = cut_batches([len(l.xyz) for l in layouts], budget_bytes)
+    for lo, hi in runs:
+        part = layouts[lo:hi]
+        offsets = np.zeros(len(part) + 1, np.int64)
+        np.cumsum([len(l.xyz) for l in part], out=offsets[1:])
+        res_lo = np.zeros(len(part) + 1, np.int64)
+        np.cumsum([len(l.residues) for l in part], out=res_lo[1:])
+        xyz = np.concatenate([l.xyz for l in part]) if part else np.zeros((0, 3))
+        group = np.concatenate([np.where(l.group >= 0, l.group + res_lo[k], -1) for k, l in enumerate(part)]).astype(np.int32)
+        selected = np.concatenate([l.selected for l in part])
+        density, residue = contact_numbers(xyz, offsets, radius, group, selected, int(res_lo[-1]), device)
+        for k, l in enumerate(part):
+            out.append(StructureDensity(density[offsets[k]:offsets[k + 1]].copy(), residue[res_lo[k]:res_lo[k + 1]].copy(), l.residues, l))
+    if stats is not None:
+        stats["submissions"] = stats.get("submissions", 0) + len(runs)
+    return out
+
+
+def packing_density(structures: Sequence[Union[pdbio.Model, str, os.PathLike]], radius: float = 7.0, atom_filter: str = "ca",
+                    device: int = 0, include_hetero: bool = True, all_chains: bool = False, budget_bytes: int = BATCH_BYTES,
+                    stats: Optional[dict] = None) -> List[StructureDensity]:
+    """Packing density of every structure (``pdbio.Model`` objects or paths of PDB files, plain or gzipped) under the structure
+    rule and the atom filters of the module docstring.  One GPU call per batch; batches are cut by ``budget_bytes`` of atom arrays,
+    not per structure.  Per structure: the int32 contact number of every neighbour atom and the float64 value of every reported
+    residue (-1.0 for a residue without a selected atom)."""
+    layouts = [layout(first_model(s), atom_filter, include_hetero, all_chains) for s in structures]
+    return packing_density_layouts(layouts, radius, device, budget_bytes, stats)
+
+
+def residue_bfactors(model: pdbio.Model) -> List[List[float]]:
+    """Per chain (non-hetero residues, chains in file order) the B-factor of each residue's first atom — the reference's
+    ``_extract_bfactor_from_polypeptide`` (analyse_utils.py:89-109: AlphaFold2 writes one pLDDT for all atoms of a residue)."""
+    chains: dict = {}
+    for r in model.residues:
+        if r.hetero or not r.atoms:
+            continue
+        first = next(iter(r.atoms))
+        chains.setdefault(r.chain, []).append(float(r.bfactors.get(first, float("nan"))))
+    return list(chains.values())
