@@ -453,7 +453,9 @@ int th_h5_group_links(const void* file, int64_t file_len, int64_t base, int64_t 
  * Angstrom; may be NULL for boolean frames), frames_rt [n_res,12] = per residue a row-major 3x3 rotation (rows = local
  * x, y, z axes) followed by the origin (the residue's CA).  Out: [n_res, V, V, V, n_channels], float32 when gaussian
  * else uint8 (0/1); `out` is host memory, or device memory of `device` when out_on_device (frames then go straight to
- * th_predict_device without leaving HBM).  One frame holds at most 2048 encodable atoms (TH_EUNSUP beyond). */
+ * th_predict_device without leaving HBM).  One frame holds at most 2048 encodable atoms (TH_EUNSUP beyond).  An atom
+ * whose coordinate in a frame is NaN or infinite is not encoded there: a frames_rt row that holds such a value gives an
+ * all-zero frame, never a NaN in the output. */
 int th_voxelise(int device, const float* atoms_xyz, const int32_t* atom_channel, const float* atom_sigma, int64_t n_atoms,
                 const float* frames_rt, int64_t n_res, int voxels_per_side, float frame_edge_length, int n_channels, int gaussian,
                 void* out, int out_on_device);

@@ -12,6 +12,26 @@ from __future__ import annotations
 import numpy as np
 
 
+def locate(atoms_xyz, frame_rt, voxels_per_side=21, frame_edge_length=21.0):
+    """Spec items 3-4 for one frame row: (local float32 [n,3], index int64 [n,3], inside bool [n]).  "Inside" is decided on
+    the floored float32 values with ordered comparisons, so a NaN or infinite local coordinate is outside and nothing that
+    is not a small integer is ever cast; the index of an atom outside is 0 and means nothing."""
+    f32 = np.float32
+    xyz = np.asarray(atoms_xyz, dtype=f32).reshape(-1, 3)
+    row = np.asarray(frame_rt, dtype=f32)
+    V = int(voxels_per_side)
+    a = f32(frame_edge_length) / f32(V)
+    centre = V // 2
+    R, ca = row[:9].reshape(3, 3), row[9:]
+    with np.errstate(invalid="ignore", over="ignore"):                   # inf - inf, 0 * inf, 1e20 * 1e20: results wanted as IEEE gives them
+        d = xyz - ca[None, :]                                            # float32 subtract
+        loc = np.stack([(R[i, 0] * d[:, 0] + R[i, 1] * d[:, 1]) + R[i, 2] * d[:, 2] for i in range(3)], axis=1).astype(f32)
+        q = np.floor(loc / a + f32(0.5))
+    inside = np.all((q >= f32(-centre)) & (q <= f32(V - 1 - centre)), axis=1)   # false for NaN
+    idx = np.where(inside[:, None], q + f32(centre), f32(0.0)).astype(np.int64)
+    return loc, idx, inside
+
+
 def voxelise(atoms_xyz, atom_channel, atom_sigma, frames_rt, voxels_per_side=21, frame_edge_length=21.0, n_channels=5,
              gaussian=True):
     f32 = np.float32
@@ -24,11 +44,7 @@ def voxelise(atoms_xyz, atom_channel, atom_sigma, frames_rt, voxels_per_side=21,
     centre = V // 2
     out = np.zeros((frt.shape[0], V, V, V, n_channels), dtype=f32 if gaussian else np.uint8)
     for r in range(frt.shape[0]):
-        R, ca = frt[r, :9].reshape(3, 3), frt[r, 9:]
-        d = xyz - ca[None, :]                                            # float32 subtract
-        loc = np.stack([(R[i, 0] * d[:, 0] + R[i, 1] * d[:, 1]) + R[i, 2] * d[:, 2] for i in range(3)], axis=1).astype(f32)
-        idx = np.floor(loc / a + f32(0.5)).astype(np.int64) + centre
-        inside = np.all((idx >= 0) & (idx < V), axis=1)
+        loc, idx, inside = locate(xyz, frt[r], V, frame_edge_length)
         for k in np.nonzero(inside)[0]:                                   # atom order
             c = int(chn[k])
             if not 0 <= c < n_channels:

@@ -27,7 +27,7 @@ struct VoxArgs {
 __global__ void __launch_bounds__(256) k_voxelise(const VoxArgs p) {
 #pragma clang fp contract(off)
     __shared__ float Lx[kMaxList], Ly[kMaxList], Lz[kMaxList], Lk[kMaxList], Lt[kMaxList];   // local xyz, 1/(2 sigma^2), sum of the 27 weights
-    __shared__ int Li[kMaxList];          // (i0 << 20) | (i1 << 10) | i2, channel in the top bits
+    __shared__ int Li[kMaxList];          // (ch << 27) | (i0 << 18) | (i1 << 9) | i2: 3 bits of channel, 9 bits per index
     __shared__ int wave_cnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = blockIdx.x, V = p.V, centre = V / 2;
@@ -45,11 +45,13 @@ __global__ void __launch_bounds__(256) k_voxelise(const VoxArgs p) {
             l0 = (R00 * d0 + R01 * d1) + R02 * d2;
             l1 = (R10 * d0 + R11 * d1) + R12 * d2;
             l2 = (R20 * d0 + R21 * d1) + R22 * d2;
-            i0 = (int)floorf(l0 / p.a + 0.5f) + centre;
-            i1 = (int)floorf(l1 / p.a + 0.5f) + centre;
-            i2 = (int)floorf(l2 / p.a + 0.5f) + centre;
+            // inside or not is decided on the floored float, with ordered comparisons: NaN and infinity are outside, and only a
+            // small integer is ever converted (the conversion turns NaN into 0, the centre voxel, and saturates beyond 2^31)
+            const float q0 = floorf(l0 / p.a + 0.5f), q1 = floorf(l1 / p.a + 0.5f), q2 = floorf(l2 / p.a + 0.5f);
+            const float lo = (float)(-centre), hi = (float)(V - 1 - centre);
             ch = p.chn[ai];
-            ok = i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V && ch >= 0 && ch < p.C;
+            ok = q0 >= lo && q0 <= hi && q1 >= lo && q1 <= hi && q2 >= lo && q2 <= hi && ch >= 0 && ch < p.C;
+            if (ok) { i0 = (int)q0 + centre; i1 = (int)q1 + centre; i2 = (int)q2 + centre; }
         }
         const unsigned long long mask = __ballot(ok);
         const int before = __popcll(mask & ((1ull << lane) - 1ull));

@@ -24,7 +24,11 @@ Specification
      z = x cross y.  local = R (p - CA) with R = rows (e_x, e_y, e_z), evaluated in float32 as
      (R_i0*dx + R_i1*dy) + R_i2*dz with separate multiplies and adds.
   4. Grid: voxel edge a = frame_edge_length / voxels_per_side; index_k = floor(local_k / a + 0.5) + voxels_per_side//2;
-     an atom is encoded iff all three indices are inside [0, voxels_per_side).
+     an atom is encoded iff all three indices are inside [0, voxels_per_side).  The decision is taken on the floored
+     float32 value, before any conversion to an integer: an atom whose local coordinate is not finite in some component
+     (NaN or infinite coordinates, or a frames_rt row that holds such a value), or whose floor(local_k / a + 0.5) lies
+     outside [-(voxels_per_side//2), voxels_per_side - 1 - voxels_per_side//2] for some k, is not encoded.  A frame
+     whose frames_rt row holds a non-finite value is therefore all zeros.
   5. Boolean frames (voxels_as_gaussian=False): frame[index][channel] = 1 (uint8).
   6. Gaussian frames: the atom is spread over the 3x3x3 block of voxels around its own voxel with weights
      w = exp(-r^2 / (2 sigma^2)), r = distance from the voxel centre to the atom, sigma = sigma_scale * vdW radius
