@@ -374,6 +374,46 @@ int th_packing_density(int device, const double* xyz, int64_t total, const int64
  * Host code. */
 double th_packing_threshold(double radius);
 
+/* ---- rotamer labels from structures: analyse_rotamers.py / tag_rotamers.py — what the reference's tag_pdb_with_rot and
+ * extract_rotamer_encoding (design_utils/analyse_utils.py:901-1036) get from ampal's tag_sidechain_dihedrals: the chi angles of every
+ * residue and its class among the 338 categories of get_rotamer_codec, for a BATCH of structures in one submission.
+ *
+ *     *** PARITY UNPINNED AGAINST AMPAL ***  ampal is neither in the reference tree nor installed where this project is built.  The
+ *     rule below — atom paths, bin edges, the ALA / GLY class — is this project's reading of ampal 1.5's
+ *     classify_angle_as_rotamer / tag_sidechain_dihedrals, and no test can pin it against ampal itself.
+ *
+ * All arrays are host memory.
+ *   xyz           double[total][3], atoms in file order (any value);
+ *   atom_name     uint32[total]: the stripped atom name as 4 ASCII bytes, left-justified, zero-padded, little-endian ("CA" = 0x4143);
+ *   total         number of atoms, 0 <= total <= 2^31 - 1;
+ *   res_offsets   int64[n_res + 1], non-decreasing, within 0 .. total: residue r owns atoms res_offsets[r] .. res_offsets[r + 1]
+ *                 (atoms outside every residue are allowed and never read);
+ *   res_type      int8[n_res]: 0..19 in the order of design_utils.amino_acids.standard_amino_acids (ALA CYS ASP GLU PHE GLY HIS ILE
+ *                 LYS LEU MET ASN PRO GLN ARG SER THR VAL TRP TYR: the codec's order), or -1 for anything else;
+ *   n_res         0 <= n_res <= 2^31 - 1;
+ *   flags         bit 0: ALA and GLY get -1 instead of their single class;
+ *   cls_out       int16[n_res]: the index into get_rotamer_codec()[1], or -1 (unlabelled);
+ *   chi_out       double[n_res][4] or NULL: degrees in (-180, 180], NaN where the residue has no such angle or is unlabelled;
+ *   kernel_ms     NULL, or receives the device time of the kernel (events around it), in milliseconds.
+ * Every chi angle is a window of four consecutive atoms on one path of n_chi + 3 atoms, N CA CB + the residue's tail
+ * (th_rotamer_table; ARG: CG CD NE CZ, ASN ASP: CG OD1, CYS: SG, GLN GLU: CG CD OE1, HIS: CG ND1, ILE: CG1 CD1, LEU PHE TRP TYR: CG CD1,
+ * LYS: CG CD CE NZ, MET: CG SD CE, PRO: CG CD, SER: OG, THR: OG1, VAL: CG1; ALA and GLY have none): chi k uses path[k .. k + 3].  Each
+ * name is searched among the residue's own atoms on the device; the first atom with the name wins.  With a, b, c, d the four atoms:
+ *   b1 = b - a, b2 = c - b, b3 = d - c, n1 = b1 x b2, n2 = b2 x b3, chi = atan2(|b2| (b1 . n2), n1 . n2) in degrees (IUPAC sign),
+ * in float64, every product and sum rounded on its own, dot products summed as (x + y) + z.  Bin 1: 0 <= chi < 120; bin 3:
+ * -120 <= chi < 0; bin 2 (trans): everything else.  class = class_base[type] + sum_k (bin_k - 1) 3^(n_chi - 1 - k): the first angle
+ * varies slowest, as itertools.product orders the codec.  UNLABELLED (-1, chi all NaN): res_type -1, any path atom absent, any angle
+ * not finite.  ALA and GLY carry their single class ALA_0 / GLY_0 whatever their atoms (flags bit 0: -1).
+ * Integers decided by float64 comparisons: independent of grid and arrival order, two calls give the same bytes.  Device memory:
+ * 28 bytes per atom + 11 (43 with chi_out) per residue.  TH_EINVAL, before anything is launched or written: a negative or too large
+ * size, a NULL that is required, res_offsets decreasing or outside 0 .. total, a res_type outside -1 .. 19.  n_res = 0 is success. */
+int th_tag_rotamers(int device, const double* xyz, const uint32_t* atom_name, int64_t total, const int64_t* res_offsets,
+                    const int8_t* res_type, int64_t n_res, int flags, int16_t* cls_out, double* chi_out, double* kernel_ms);
+/* The table th_tag_rotamers uses, for one residue type 0..19: the number of chi angles, the index of the type's first class, and the
+ * n_chi + 3 path names (zero-padded to 4 bytes, not terminated when 4 long; all zero beyond the path and for ALA / GLY).  Any output
+ * may be NULL.  Host code. */
+int th_rotamer_table(int res_type, int* n_chi, int* class_base, char names[7][4]);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

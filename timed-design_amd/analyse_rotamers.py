@@ -7,14 +7,21 @@ GPU (design_utils.analyse_utils.calculate_rotamer_metrics -> th_analyse_classes)
         --path_to_rotamer_labels rotamer_labels.json --output_path analysis
 
 The true rotamers come from ``--path_to_rotamer_labels``: JSON {"<pdb><chain>": [class index or null, ...]}, which is the first
-dict the reference's ``tag_pdb_with_rot`` returns.  With the reference installed, three lines write it:
+dict the reference's ``tag_pdb_with_rot`` returns, or — without that flag — from the structures under ``--path_to_pdb``:
 
-    from design_utils.analyse_utils import tag_pdb_with_rot
-    wt_results_dict, _ = tag_pdb_with_rot(workers, path_to_pdb, pdb_codes)
-    json.dump({k: [None if v != v else int(v) for v in vals] for k, vals in wt_results_dict.items()}, open("rotamer_labels.json", "w"))
+    python analyse_rotamers.py --path_to_pred_matrix TIMED_rotamer_rot.csv --path_to_datasetmap datasetmap.txt \\
+        --path_to_pdb biounits/ --output_path analysis
 
-Tagging structures here would need ampal's side-chain dihedral code, and the reference's analyses 2 and 3 need SCWRL4; neither
-can be pinned by this project's tests, so they are not rebuilt: without --path_to_rotamer_labels the program stops and says so.
+tags the structures of the dataset map's pdb codes here (design_utils.analyse_utils.tag_pdb_with_rot: the reference's file rule,
+``<path>/<code[1:3]>/<code[:4]>.pdb1.gz`` then ``.pdb1``, ``<path>/<code>.pdb`` for a code with ``_``; nothing is fetched; chi
+angles and classes on the GPU, th_tag_rotamers), writes ``rotamer_labels.json`` into the output directory in the format above, and
+runs the analysis on it.  The reference tags with ampal's side-chain dihedral code, which is not available to pin this against:
+the atom paths, bin edges and the ALA / GLY class are this project's own rule, written out in timed_hip/structure.py (PARITY
+UNPINNED AGAINST AMPAL).  Labels and matrix rows are paired by position, as the reference pairs them.  ``tag_rotamers.py`` writes
+the same labels file (and the chi angles) for any set of PDB files.
+
+The reference's analyses 2 and 3 need SCWRL4, which cannot be pinned by this project's tests, so they are not rebuilt.  With neither
+--path_to_rotamer_labels nor --path_to_pdb the program stops and says so.
 """
 import argparse
 import json
@@ -27,10 +34,12 @@ from design_utils import utils as du
 from design_utils.analyse_utils import calculate_rotamer_metrics
 
 NO_LABELS_MESSAGE = (
-    "analyse_rotamers.py needs --path_to_rotamer_labels FILE: JSON {\"<pdb><chain>\": [rotamer class index or null, ...]}, the first "
-    "dict the reference's tag_pdb_with_rot returns (see --help for the three lines that dump it).  Tagging the structures under "
-    "--path_to_pdb needs ampal's side-chain dihedral code, and the analyses against SCWRL4-packed structures need SCWRL4 "
-    "(--scwrl_path); neither is part of this build.")
+    "analyse_rotamers.py needs the true rotamers: either --path_to_rotamer_labels FILE, JSON {\"<pdb><chain>\": [rotamer class index "
+    "or null, ...]} — the first dict the reference's tag_pdb_with_rot returns, or what tag_rotamers.py writes — or --path_to_pdb DIR, "
+    "the biounit structures of the dataset map's pdb codes, which are then tagged here (this project's own rule: ampal's side-chain "
+    "dihedral code is not available to pin it).  The analyses against SCWRL4-packed structures need SCWRL4 (--scwrl_path) and are "
+    "not part of this build.")
+LABELS_FILE = "rotamer_labels.json"
 
 
 def load_rotamer_labels(path) -> dict:
@@ -41,18 +50,34 @@ def load_rotamer_labels(path) -> dict:
     return labels
 
 
+def tag_structures(args, dataset_map, output_path: Path) -> Path:
+    """tag the structures of the map's pdb codes under --path_to_pdb and write the labels file into the output directory"""
+    from design_utils.analyse_utils import rotamer_labels_json, tag_pdb_with_rot
+    pdb_codes = np.unique(np.asarray([row[0] for row in dataset_map]))           # as the reference (analyse_rotamers.py:41)
+    wt_results_dict, _assemblies = tag_pdb_with_rot(args.workers, Path(args.path_to_pdb), pdb_codes, device=args.device)
+    labels_path = output_path / LABELS_FILE
+    with open(labels_path, "w") as f:
+        json.dump(rotamer_labels_json(wt_results_dict), f)
+        f.write("\n")
+    print(f"tagged {len(wt_results_dict)} chains of {len(pdb_codes)} pdb codes -> {labels_path}")
+    return labels_path
+
+
 def main(args):
-    if not getattr(args, "path_to_rotamer_labels", None):
+    labels_given = getattr(args, "path_to_rotamer_labels", None)
+    if not labels_given and not getattr(args, "path_to_pdb", None):
         sys.exit(NO_LABELS_MESSAGE)
     matrix_path, map_path = Path(args.path_to_pred_matrix), Path(args.path_to_datasetmap)
-    labels_path = Path(args.path_to_rotamer_labels)
     model_name = matrix_path.stem
     output_path = Path(f"{args.output_path}_{model_name}")          # the reference's naming (analyse_rotamers.py:23)
-    for what, path in (("prediction matrix", matrix_path), ("dataset map", map_path), ("rotamer labels file", labels_path)):
+    checks = [("prediction matrix", matrix_path), ("dataset map", map_path)]
+    checks.append(("rotamer labels file", Path(labels_given)) if labels_given else ("PDB folder", Path(args.path_to_pdb)))
+    for what, path in checks:
         assert path.exists(), f"No {what} at {path}"
     output_path.mkdir(parents=True, exist_ok=True)
     from sample import _one_letter_rotamer_categories, _read_matrix
     dataset_map = du.load_datasetmap(map_path, is_old=args.support_old_datasetmap)
+    labels_path = Path(labels_given) if labels_given else tag_structures(args, dataset_map, output_path)
     # float16, as the reference reads it (analyse_rotamers.py:46-48): text -> float64 -> float16 is genfromtxt's double rounding
     prediction_matrix = _read_matrix(matrix_path).astype(np.float16)
     _, flat_categories = du.get_rotamer_codec()
@@ -71,12 +96,12 @@ def main(args):
 CLI_FLAGS = (
     ("--path_to_pred_matrix", dict(type=str, help="338-column probability matrix written by predict.py --predict_rotamers (<model>_rot.csv)")),
     ("--output_path", dict(default="output", type=str, help="the analysis is written to the directory <output_path>_<matrix name>")),
-    ("--path_to_pdb", dict(type=str, help="biounit pdb dataset, pdb/{2nd and 3rd char}/{pdb}.pdb1.gz (accepted for compatibility: structures are not tagged here)")),
+    ("--path_to_pdb", dict(type=str, help="biounit pdb dataset, pdb/{2nd and 3rd char}/{pdb}.pdb1.gz: without --path_to_rotamer_labels its structures are tagged here and rotamer_labels.json is written")),
     ("--path_to_datasetmap", dict(default="datasetmap.txt", type=str, help="dataset map written by predict.py (.txt)")),
-    ("--workers", dict(type=int, default=8, help="accepted for compatibility; the metrics are computed on the GPU")),
+    ("--workers", dict(type=int, default=8, help="host threads that parse the structures of --path_to_pdb (at most 16); the metrics are computed on the GPU")),
     ("--support_old_datasetmap", dict(default=False, action="store_true", help="the dataset map is the old 4-column csv")),
     ("--scwrl_path", dict(default="/Users/leo/scwrl4/Scwrl4", type=str, help="accepted for compatibility: the SCWRL4 analyses are not part of this build")),
-    ("--path_to_rotamer_labels", dict(type=str, default=None, help="JSON {\"<pdb><chain>\": [rotamer class index or null, ...]}: the first dict tag_pdb_with_rot returns")),
+    ("--path_to_rotamer_labels", dict(type=str, default=None, help="JSON {\"<pdb><chain>\": [rotamer class index or null, ...]}: the first dict tag_pdb_with_rot returns (tag_rotamers.py writes it)")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
 )
 

@@ -238,3 +238,83 @@ def calculate_rotamer_metrics(pdb_to_probability, pdb_to_rotamer: dict, rot_cate
         with open(output_path / f"cm_{suffix}_{kind}.csv", "wb") as f:
             f.write(textio.format_csv(cm))
     return results
+
+
+# ---- rotamer labels from structures (analyse_rotamers.py, tag_rotamers.py; computed on the GPU by timed_hip.structure) ----------
+class RotamerChain:
+    """One chain of a tagged structure — what the reference iterates as an ampal Polypeptide: ``id``, ``sequence`` (one letter
+    per residue, X for a residue that is not one of the 20), ``residues`` (timed_hip.pdbio.Residue) and ``classes`` (rotamer class
+    per residue, -1 where unlabelled)."""
+
+    def __init__(self, chain_id: str, residues: list, classes: np.ndarray):
+        from .amino_acids import standard_amino_acids
+        one_letter = {three: one for one, three in standard_amino_acids.items()}
+        self.id, self.residues, self.classes = chain_id, residues, np.asarray(classes)
+        self.sequence = "".join(one_letter.get(r.name, "X") for r in residues)
+
+    def __len__(self):
+        return len(self.residues)
+
+
+def chains_of(tagged) -> t.Dict[str, RotamerChain]:
+    """{chain id: RotamerChain} of one timed_hip.structure.StructureRotamers, chains in file order"""
+    members: t.Dict[str, t.List[int]] = {}
+    for k, r in enumerate(tagged.residues):
+        members.setdefault(r.chain, []).append(k)
+    return {cid: RotamerChain(cid, [tagged.residues[k] for k in idx], tagged.cls[idx]) for cid, idx in members.items()}
+
+
+def extract_rotamer_encoding(pdb_code: str, monomer: RotamerChain) -> dict:
+    """reference analyse_utils.py:901-930: ``{pdb_code[:4] + chain id: [rotamer class or nan per residue]}`` for one tagged chain
+    (a RotamerChain where the reference takes an ampal Polypeptide that went through tag_sidechain_dihedrals)."""
+    return {f"{pdb_code[:4]}{monomer.id}": [float("nan") if c < 0 else int(c) for c in monomer.classes.tolist()]}
+
+
+def rotamer_structure_path(path_to_pdb, pdb_code: str):
+    """The reference's file rule (analyse_utils.py:951-963): a code with ``_`` is ``<path>/<code>.pdb``; any other is
+    ``<path>/<code[1:3]>/<code[:4]>.pdb1.gz``, then ``.pdb1``.  Returns (the file or None, the last path tried).  Nothing is
+    created and nothing is ever fetched (the reference downloads a missing biological unit)."""
+    from pathlib import Path
+    path_to_pdb = Path(path_to_pdb)
+    if "_" in pdb_code:
+        tried = [path_to_pdb / (pdb_code + ".pdb")]
+    else:
+        tried = [path_to_pdb / pdb_code[1:3] / (pdb_code[:4] + suffix) for suffix in (".pdb1.gz", ".pdb1")]
+    for candidate in tried:
+        if candidate.exists():
+            return candidate, candidate
+    return None, tried[-1]
+
+
+def tag_pdb_with_rot(workers: int, path_to_pdb, pdb_codes, device: int = 0) -> t.Tuple[dict, dict]:
+    """reference analyse_utils.py:933-1036: ``(results_dict, pdb_to_assemblies)`` for the structures of ``pdb_codes`` under
+    ``path_to_pdb`` (file rule: rotamer_structure_path; a missing file prints ``Could not find ...`` and is skipped).
+    ``results_dict`` is {pdb4 + chain: [rotamer class or nan per residue]}, ``pdb_to_assemblies`` {pdb4: {chain: RotamerChain}} —
+    ``pdb_to_assemblies[pdb4][chain].sequence`` is what the reference reads from it.  The files are parsed on ``workers`` host
+    threads (at most 16) and ALL structures are tagged on the GPU together (timed_hip.structure.tag_rotamers; the rule is this
+    project's own, PARITY UNPINNED AGAINST AMPAL, see timed_hip/structure.py)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from timed_hip import structure
+    found = []
+    for code in pdb_codes:
+        code = str(code)
+        path, tried = rotamer_structure_path(path_to_pdb, code)
+        if path is None:
+            print(f"Could not find {tried}")
+        else:
+            found.append((code, path))
+    with ThreadPoolExecutor(max_workers=max(1, min(int(workers), 16))) as pool:
+        layouts = list(pool.map(lambda item: structure.rotamer_layout(structure.first_model(item[1])), found))
+    results_dict, pdb_to_assemblies = {}, {}
+    for (code, _), tagged in zip(found, structure.tag_rotamers(layouts, device=device)):
+        chains = chains_of(tagged)
+        for monomer in chains.values():
+            results_dict.update(extract_rotamer_encoding(code, monomer))
+        pdb_to_assemblies[code[:4]] = chains
+    return results_dict, pdb_to_assemblies
+
+
+def rotamer_labels_json(results_dict: dict) -> dict:
+    """{key: [class or None]}: the labels file analyse_rotamers.py reads (--path_to_rotamer_labels) from a results_dict"""
+    return {key: [None if v != v else int(v) for v in values] for key, values in results_dict.items()}

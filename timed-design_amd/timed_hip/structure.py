@@ -24,6 +24,21 @@ Atom filters, under the reference's names (which atoms of a residue enter its va
     ``"calpha"``    CA alone (an addition of this project)
 The per-residue value is the reference's running half-average over the selected atoms in file order, not their mean (see
 include/timed_hip.h, th_packing_density).
+
+Rotamer labels (``tag_rotamers``; th_tag_rotamers, csrc/rotamers.hip): the chi angles of every residue and its class among the 338
+categories of ``design_utils.utils.get_rotamer_codec`` — what the reference's ``tag_pdb_with_rot`` / ``extract_rotamer_encoding``
+(design_utils/analyse_utils.py:901-1036) get from ampal's ``tag_sidechain_dihedrals``.
+
+    *** ROTAMER RULE: PARITY UNPINNED AGAINST AMPAL ***  The same standing as the structure rule above.  This project's reading of
+    ampal 1.5's ``classify_angle_as_rotamer`` / ``tag_sidechain_dihedrals``, written out in include/timed_hip.h (th_tag_rotamers):
+
+    * the first model; the non-hetero residues of every chain, chains in file order (``all_chains=False``: the first chain);
+    * chi k is the dihedral of atoms k .. k + 3 of the path N, CA, CB + the residue's tail (``rotamer_table``), IUPAC sign, float64;
+      the first atom of a residue that carries a name is the one used (pdbio keeps the first alternate location);
+    * bin 1: 0 <= chi < 120; bin 3: -120 <= chi < 0; bin 2: everything else; the first angle varies slowest in the class index;
+    * unlabelled (class -1, ``None``): a residue that is not one of the 20, lacks a path atom or has a non-finite angle;
+    * ALA and GLY carry their single class ``ALA_0`` / ``GLY_0`` — the only label the codec has for them; ``ala_gly_class=False``
+      leaves them unlabelled, which is what a tagger that tags nothing on a residue without dihedrals would give.
 """
 from __future__ import annotations
 
@@ -40,6 +55,7 @@ ATOM_FILTERS = ("all", "ca", "backbone", "calpha")
 _BACKBONE = ("N", "CA", "C", "O")
 BATCH_BYTES = 256 << 20            # host bytes of atom arrays handed to one th_packing_density call
 _ATOM_BYTES = 3 * 8 + 4 + 1 + 4    # xyz, group, selected, density
+TAG_NO_ALA_GLY = 1                 # th_tag_rotamers flag bit 0: ALA and GLY stay unlabelled
 
 
 def atom_selected(name: str, atom_filter: str) -> bool:
@@ -211,3 +227,144 @@ def residue_bfactors(model: pdbio.Model) -> List[List[float]]:
         first = next(iter(r.atoms))
         chains.setdefault(r.chain, []).append(float(r.bfactors.get(first, float("nan"))))
     return list(chains.values())
+
+
+# ---- rotamer labels --------------------------------------------------------------------------------------------------------------
+def rotamer_table() -> List[Tuple[str, int, int, Tuple[str, ...]]]:
+    """th_rotamer_table for the 20 residue types in the codec's order: (three-letter code, n_chi, index of the first class, the
+    n_chi + 3 path names; empty for ALA and GLY).  Host code, no GPU needed."""
+    from design_utils.amino_acids import standard_amino_acids
+    lib, rows = _lib.load(), []
+    for t, res in enumerate(standard_amino_acids.values()):
+        n_chi, base, names = C.c_int(0), C.c_int(0), C.create_string_buffer(28)
+        _lib.check(lib.th_rotamer_table(t, C.byref(n_chi), C.byref(base), names))
+        path = tuple(names.raw[4 * p:4 * p + 4].rstrip(b"\0").decode("ascii") for p in range(7))
+        rows.append((res, n_chi.value, base.value, tuple(nm for nm in path if nm)))
+    return rows
+
+
+def pack_atom_names(names: Sequence[str]) -> np.ndarray:
+    """atom names as th_tag_rotamers reads them: 4 ASCII bytes, left-justified, zero-padded, little-endian uint32"""
+    raw = b"".join(nm.encode("ascii", "replace")[:4].ljust(4, b"\0") for nm in names)
+    return np.frombuffer(raw, dtype="<u4").astype(np.uint32)
+
+
+@dataclass
+class RotamerLayout:
+    """One structure as th_tag_rotamers takes it."""
+    xyz: np.ndarray                    # [n, 3] float64, the atoms of the reported residues, residue after residue
+    atom_name: np.ndarray              # [n] uint32 (pack_atom_names)
+    res_offsets: np.ndarray            # [residues + 1] int64
+    res_type: np.ndarray               # [residues] int8: 0..19 in the codec's order, -1 for anything else
+    residues: List[pdbio.Residue]
+
+
+def rotamer_layout(model: pdbio.Model, all_chains: bool = True) -> RotamerLayout:
+    """Flat arrays of the non-hetero residues, chains in file order (a chain that comes back later in the file continues its
+    entry).  Hydrogens stay in: they match no path name."""
+    from design_utils.amino_acids import standard_amino_acids
+    type_of = {res: t for t, res in enumerate(standard_amino_acids.values())}
+    chains: dict = {}
+    for r in reported_residues(model, all_chains):
+        chains.setdefault(r.chain, []).append(r)
+    residues = [r for members in chains.values() for r in members]
+    offsets = np.zeros(len(residues) + 1, np.int64)
+    np.cumsum([len(r.atoms) for r in residues], out=offsets[1:])
+    xyz = np.array([pos for r in residues for pos in r.atoms.values()], dtype=np.float64).reshape(-1, 3)
+    return RotamerLayout(xyz, pack_atom_names([nm for r in residues for nm in r.atoms]), offsets,
+                         np.array([type_of.get(r.name, -1) for r in residues], dtype=np.int8), residues)
+
+
+def rotamer_classes(xyz, atom_name, res_offsets, res_type, device: int = 0, ala_gly_class: bool = True, chi: bool = True,
+                    timing: Optional[dict] = None):
+    """One th_tag_rotamers call.  Returns (int16 [n_res], float64 [n_res, 4] or None when ``chi`` is false).  ``timing``: a dict
+    that receives ``kernel_ms``."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    atom_name = np.ascontiguousarray(atom_name, dtype=np.uint32).reshape(-1)
+    res_offsets = np.ascontiguousarray(res_offsets, dtype=np.int64).reshape(-1)
+    res_type = np.ascontiguousarray(res_type, dtype=np.int8).reshape(-1)
+    if atom_name.size != xyz.shape[0]:
+        raise ValueError(f"atom_name needs {xyz.shape[0]} entries")
+    if res_offsets.size != res_type.size + 1:
+        raise ValueError(f"res_offsets needs {res_type.size + 1} entries")
+    n_res = res_type.size
+    cls = np.empty(n_res, np.int16)
+    angles = np.empty((n_res, 4), np.float64) if chi else None
+    ms = C.c_double(0.0)
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.load().th_tag_rotamers(int(device), ptr(xyz), ptr(atom_name), xyz.shape[0], ptr(res_offsets), ptr(res_type), n_res,
+                                           0 if ala_gly_class else TAG_NO_ALA_GLY, ptr(cls), ptr(angles),
+                                           C.byref(ms) if timing is not None else None))
+    if timing is not None:
+        timing["kernel_ms"] = timing.get("kernel_ms", 0.0) + ms.value
+    return cls, angles
+
+
+@dataclass
+class StructureRotamers:
+    residues: List[pdbio.Residue]      # the non-hetero residues, chains in file order
+    cls: np.ndarray                    # [residues] int16: index into get_rotamer_codec()[1], -1 unlabelled
+    chi: np.ndarray                    # [residues, 4] float64 degrees, NaN where there is no such angle
+
+    @property
+    def rotamers(self) -> List[Optional[str]]:
+        """the bins of each residue as the codec spells them: "13", "2212", "0" for ALA / GLY, None when unlabelled"""
+        from design_utils.utils import get_rotamer_codec
+        names = get_rotamer_codec()[1]
+        return [None if c < 0 else names[c].split("_")[1] for c in self.cls.tolist()]
+
+
+def tag_rotamer_layouts(layouts: Sequence[RotamerLayout], device: int = 0, ala_gly_class: bool = True, budget_bytes: int = BATCH_BYTES,
+                        stats: Optional[dict] = None) -> List[StructureRotamers]:
+    """The layouts through th_tag_rotamers in as few calls as ``budget_bytes`` allows (cut_batches, as packing_density_layouts).
+    ``stats`` receives ``submissions`` and ``kernel_ms``."""
+    out: List[StructureRotamers] = []
+    runs = cut_batches([len(l.xyz) for l in layouts], budget_bytes)
+    timing = {} if stats is not None else None
+    for lo, hi in runs:
+        part = layouts[lo:hi]
+        atom_lo = np.zeros(len(part) + 1, np.int64)
+        np.cumsum([len(l.xyz) for l in part], out=atom_lo[1:])
+        res_lo = np.zeros(len(part) + 1, np.int64)
+        np.cumsum([len(l.residues) for l in part], out=res_lo[1:])
+        offsets = np.concatenate([l.res_offsets[:-1] + atom_lo[k] for k, l in enumerate(part)] + [atom_lo[-1:]])
+        cls, chi = rotamer_classes(np.concatenate([l.xyz for l in part]), np.concatenate([l.atom_name for l in part]), offsets,
+                                   np.concatenate([l.res_type for l in part]), device, ala_gly_class, timing=timing)
+        for k, l in enumerate(part):
+            out.append(StructureRotamers(l.residues, cls[res_lo[k]:res_lo[k + 1]].copy(), chi[res_lo[k]:res_lo[k + 1]].copy()))
+    if stats is not None:
+        stats["submissions"] = stats.get("submissions", 0) + len(runs)
+        stats["kernel_ms"] = stats.get("kernel_ms", 0.0) + timing.get("kernel_ms", 0.0)
+    return out
+
+
+def tag_rotamers(structures: Sequence[Union[pdbio.Model, RotamerLayout, str, os.PathLike]], device: int = 0, ala_gly_class: bool = True,
+                 budget_bytes: int = BATCH_BYTES, stats: Optional[dict] = None) -> List[StructureRotamers]:
+    """Chi angles and rotamer classes of every structure (``pdbio.Model`` objects, ``RotamerLayout`` objects or paths of PDB files,
+    plain or gzipped) under the rotamer rule of the module docstring.  One GPU call per batch; batches are cut by ``budget_bytes``
+    of atom arrays, not per structure."""
+    layouts = [s if isinstance(s, RotamerLayout) else rotamer_layout(first_model(s)) for s in structures]
+    return tag_rotamer_layouts(layouts, device, ala_gly_class, budget_bytes, stats)
+
+
+def labels_for_map(tagged: StructureRotamers, dataset_map_rows) -> Tuple[List[Optional[int]], int]:
+    """The classes of one tagged structure in DATASET-MAP order: ``dataset_map_rows`` are rows of an old-format map (pdb, chain,
+    residue number, label), all of this structure; each is matched on (chain, residue number as pdbio writes it, insertion code
+    included).  Returns (labels, unmatched): ``None`` for a row whose residue the structure lacks or that is unlabelled, and the
+    count of rows without a matching residue.  The reference pairs labels and matrix rows BY POSITION and silently misaligns when
+    a structure has residues the map lacks; positional pairing stays the default wherever the reference does it — this is the
+    opt-in alternative."""
+    by_key = {}
+    for r, c in zip(tagged.residues, tagged.cls.tolist()):
+        by_key.setdefault((r.chain, r.number), c)
+    labels, unmatched = [], 0
+    for row in dataset_map_rows:
+        key = (str(row[1]).strip(), str(row[2]).strip())
+        if key not in by_key:
+            unmatched += 1
+            labels.append(None)
+        else:
+            labels.append(None if by_key[key] < 0 else int(by_key[key]))
+    return labels, unmatched
