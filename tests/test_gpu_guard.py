@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import cnn_oracle
-from timed_hip import engine, synth
+from timed_hip import _lib, engine, synth
 
 pytestmark = pytest.mark.gpu
 TIGHT = 5e-6
@@ -158,10 +158,29 @@ def test_knobs_belong_to_the_handle_not_to_the_process(gpu, monkeypatch):
     assert not any("conv_wino" in l for l in _labels(a)) and any("conv_wino" in l for l in _labels(b))
     pa, pb = a.predict(frames), b.predict(frames)
     monkeypatch.setenv("TH_WINOGRAD", "0")               # a later change reaches neither handle
-    monkeypatch.setenv("TH_WF_DBG", "3")
+    monkeypatch.setenv("TH_WFUSED", "0")                 # (it would change b's plan and bits if it reached b)
     assert np.array_equal(a.predict(frames), pa) and np.array_equal(b.predict(frames), pb)
     np.testing.assert_allclose(pa, pb, atol=TIGHT, rtol=0)
     a.close(); b.close()
+
+
+KNOCKOUT_VARS = ("TH_WF_DBG", "TH_FIRST_DBG", "TH_WINO_DBG", "TH_CONV_DBG", "TH_PW_DBG")
+
+
+def test_the_product_library_refuses_knockout_variables(gpu, monkeypatch):
+    """the timing knock-outs live in a build of their own (tools/build_knockouts.py): the product library has none, and a model
+    load under a set TH_*_DBG variable fails, naming it, instead of timing the whole kernels; unset, empty or 0 loads as ever"""
+    cfg, w = synth.timed_synth(20, widths=(4,), side=5, in_channels=2)
+    for var in KNOCKOUT_VARS:
+        monkeypatch.setenv(var, "1")
+        with pytest.raises(_lib.TimedHipError) as e:
+            engine.HipFrameModel.from_keras(cfg, w, device=gpu)
+        assert e.value.code == _lib.TH_EINVAL and var in str(e.value), (var, str(e.value))
+        for ok in ("0", "", None):
+            monkeypatch.setenv(var, ok) if ok is not None else monkeypatch.delenv(var)
+            model = engine.HipFrameModel.from_keras(cfg, w, device=gpu)
+            assert model.knobs() == "", (var, ok, model.knobs())
+            model.close()
 
 
 def test_a_pass_is_remembered_for_the_same_pack_knobs_and_device(gpu):

@@ -74,12 +74,19 @@ def test_abi_exports_every_declared_symbol(lib):
     assert lib.th_version() == 1
 
 
-def test_no_gpu_is_an_error_not_a_fallback(lib):
-    """Without a device the product must fail loudly (there is no CPU path)."""
+def test_no_gpu_is_an_error_not_a_fallback(lib, monkeypatch):
+    """Without a device the product must fail loudly (there is no CPU path).  A timing knock-out variable is refused by name
+    before the device is looked for: the product library has no knock-outs (tools/build_knockouts.py builds the one that has)."""
     from timed_hip import _lib, engine
+    cfg, w = synth.timed_synth(20, widths=(4,), side=5, in_channels=2)
+    for var in ("TH_WF_DBG", "TH_FIRST_DBG", "TH_WINO_DBG", "TH_CONV_DBG", "TH_PW_DBG"):
+        monkeypatch.setenv(var, "1")
+        with pytest.raises(_lib.TimedHipError) as e:
+            engine.HipFrameModel.from_keras(cfg, w)
+        assert e.value.code == _lib.TH_EINVAL and var in str(e.value), (var, str(e.value))
+        monkeypatch.delenv(var)
     if _lib.device_count() > 0:
         pytest.skip("a GPU is present")
-    cfg, w = synth.timed_synth(20, widths=(4,), side=5, in_channels=2)
     with pytest.raises(_lib.TimedHipError):
         engine.HipFrameModel.from_keras(cfg, w)
 

@@ -30,12 +30,33 @@ void th_set_error(const char* fmt, ...);
         }                                                                                        \
     } while (0)
 
+// ---- timing knock-outs ------------------------------------------------------------------------
+// The product library contains none.  tools/build_knockouts.py compiles the same sources with -DTH_KNOCKOUTS=1 into
+// libtimedhip_knock.so (load it through TIMED_HIP_LIB): only that build has the TH_*_DBG knobs, the knock-out instantiations of the
+// template kernels and the run-time knock-out bits of the kernels below.  Results are wrong by design when a knock-out is set.
+#ifndef TH_KNOCKOUTS
+#define TH_KNOCKOUTS 0
+#endif
+// Kernels that take their knock-outs at run time (the Winograd GEMMs, k_conv_n16) read TH_KNOCK(a), the constant 0 in the product
+// build, and their argument struct declares TH_KNOCK_FIELD, which is nothing there; launchers fill it with TH_KNOCK_SET.  Two kernels
+// keep a plain `int dbg`, 0 in the product build, because hipcc spills more with the constant: k_conv_mfma and k_conv_pw2 (their
+// argument structs give the figures).
+#if TH_KNOCKOUTS
+#define TH_KNOCK_FIELD int dbg;
+#define TH_KNOCK(a) ((a).dbg)
+#define TH_KNOCK_SET(a, v) ((a).dbg = (v))
+#else
+#define TH_KNOCK_FIELD
+#define TH_KNOCK(a) 0
+#define TH_KNOCK_SET(a, v) ((void)0)
+#endif
+
 // ---- A/B and test knobs ---------------------------------------------------------------------
 // Every TH_* environment variable that changes what a MODEL plans or launches is read exactly once, by th_model_load, into the
 // handle (th_knobs_read).  Planners are handed the snapshot of the load in progress (a `const ThKnobs&`) and leave a pointer to it
 // in their plan structs, launchers read it from there: no getenv in a launch path, no process-wide static caches — two models
 // loaded under different environments keep their own settings, whatever the call order.  `nondefault` lists what was set
-// ("TH_WINOGRAD=0 TH_WF_DBG=3"); th_model_knobs() returns it and bench.py prints it.
+// ("TH_WINOGRAD=0 TH_WFUSED=0"); th_model_knobs() returns it and bench.py prints it.
 struct ThKnobs {
     int winograd = 1;          // TH_WINOGRAD: 0 direct kernels, 1 F(3,3)+F(2,3) in-plane (default), 2 F(5,3) (opt-in)
     int wino_split = 1;        // TH_WINO_SPLIT: Winograd GEMMs on bf16 MFMA with exactly split operands (0: fp32-input MFMA)
@@ -48,20 +69,21 @@ struct ThKnobs {
     int conv_gl = 1;           // TH_CONV_GL: 1 strided convolutions and those with <= 64 outputs per frame on conv_gl.hip (2: every eligible layer, 0: none)
     int dense_gemm = 1;        // TH_DENSE_GEMM: Dense layers of >= 512 features and 8..128 outputs as a batch GEMM on fp32 MFMA (dense_gemm.hip)
     int first_int = 1;         // TH_FIRST_INT: uint8 / bool frames on the one-piece form of conv_first_b3 (0: the general six-product kernel)
-    int first_zb = 0;          // TH_FIRST_ZB: brick depth of the first-layer kernel (tuning)
-    int first_dbg = 0;         // TH_FIRST_DBG: timing knock-outs (results wrong)
     int no_pool_first = 0;     // TH_NO_POOL_FIRST: act / BN before the max-pool even when the chain is monotone
     int no_tail_fuse = 0;      // TH_NO_TAIL_FUSE: keep GAP / Dense / Softmax as separate launches
     int conv_nogeo = 0, n16_nogeo = 0, conv_noxc = 0, conv_notail = 0, conv_nozmajor = 0, conv_nocompact = 0, conv_nopw = 0;
     int conv_bmode = 0;        // TH_CONV_BMODE: 1 dbuf, 2 stream8, 3 no16
-    int conv_dbg = 0, conv_ldspad = 0, n16_resident = 0;
-    int pw_nopipe = 0, pw_noepi = 0, pw_dbg = 0;
-    int wf_resident = 0, wf_dbg = 0, wf_noblk = 0;
+    int n16_resident = 0;
+    int pw_nopipe = 0, pw_noepi = 0;
+    int wf_resident = 0, wf_noblk = 0;
     long long wino_piece = 0;
-    int wino_dbg = 0, wino_b3var = 2, wino_nomid = 0;
+    int wino_b3var = 2, wino_nomid = 0;
+#if TH_KNOCKOUTS
+    int wf_dbg = 0, first_dbg = 0, wino_dbg = 0, conv_dbg = 0, pw_dbg = 0;     // TH_*_DBG: which knock-outs (each kernel's comment lists its codes)
+#endif
     std::string nondefault;
 };
-void th_knobs_read(ThKnobs* k);                 // the process environment, now
+int th_knobs_read(ThKnobs* k);                  // the process environment, now (TH_EINVAL: a knock-out variable is set and this build has none)
 inline const ThKnobs& th_knobs_of(const ThKnobs* k) { static const ThKnobs dflt; return k ? *k : dflt; }
 
 // hipMalloc for every allocator inside the library: when the device is out of memory the blocks parked in the model block
@@ -171,7 +193,7 @@ struct ConvMfmaPlan {
     int first_wino = 0;           // first-layer kernel only: F(2,3) along x (k_conv_first_w), rows are x pairs
     double own_flops = 0;         // first_wino: the algorithm's own multiply-adds x 2 per frame (4 points per x pair and (dz, dy) tap)
     int geo = 0;                  // > 0: the kernel instantiation with Hp = Wp = geo at compile time (tap offsets as immediates)
-    const ThKnobs* knobs = nullptr;   // the owning model's A/B knobs (launch-time ones: dbg, resident, ...)
+    const ThKnobs* knobs = nullptr;   // the owning model's A/B knobs (launch-time ones: resident, ...)
     std::string label;
 };
 // choose a tiling for this convolution; returns false when the MFMA kernel does not apply

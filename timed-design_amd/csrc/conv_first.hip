@@ -567,8 +567,10 @@ const FirstGeo kFirstWGeo[] = {
     {3, 3, 22, k_conv_first_w<3, 3, 22>},
     {3, 1, 22, k_conv_first_w<3, 1, 22>},
 };
+#if TH_KNOCKOUTS
 const FirstKernel kFirstWDbg[8] = {nullptr, k_conv_first_w<3, 3, 22, 1>, k_conv_first_w<3, 3, 22, 2>, k_conv_first_w<3, 3, 22, 3>,
                                    k_conv_first_w<3, 3, 22, 4>, nullptr, nullptr, k_conv_first_w<3, 3, 22, 7>};
+#endif
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -617,10 +619,6 @@ bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& oc, const 
     if (!ZB) return false;
     for (int zb = ZB; zb >= step && zb * 10 >= ZB * 6; zb -= step)
         if (p->Dc % zb == 0) { ZB = zb; break; }
-    if (kn.first_zb) {  // tuning experiments
-        const int zb = kn.first_zb;
-        if (zb >= step && zb % step == 0 && zb <= p->Dc && lds_for(zb) <= (size_t)160 * 1024) ZB = zb;
-    }
     p->ZB = ZB;
     p->nzb = (p->Dc + ZB - 1) / ZB;
     p->Zp = ZB + 2;
@@ -725,10 +723,10 @@ int launch_conv_first(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const voi
     const int nst = (Cin + 1) / 2;
     int pmode, geo;
     FirstKernel k = pick_first_kernel(p, nst, post, &pmode, &geo);
-    {   // timing experiments only (tools/bench_layer.py): knock-out instantiations of k_conv_first_w<3,3,22>
-        const int dbg = th_knobs_of(p.knobs).first_dbg;
-        if (dbg > 0 && dbg < 8 && kFirstWDbg[dbg] && p.first_wino && nst == 3 && pmode == 3 && geo == 22) k = kFirstWDbg[dbg];
-    }
+#if TH_KNOCKOUTS   // the knock-out build only (tools/build_knockouts.py): TH_FIRST_DBG instantiations of k_conv_first_w<3,3,22>
+    const int dbg = th_knobs_of(p.knobs).first_dbg;
+    if (dbg > 0 && dbg < 8 && kFirstWDbg[dbg] && p.first_wino && nst == 3 && pmode == 3 && geo == 22) k = kFirstWDbg[dbg];
+#endif
     HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kWaves * 64), p.lds_bytes, s, a);
     hipError_t e = hipGetLastError();

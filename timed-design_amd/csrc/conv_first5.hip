@@ -343,10 +343,12 @@ int launch_conv_first5(hipStream_t s, int64_t n, const ThKnobs* knobs, int ncu, 
     const int64_t trips = (n + resident - 1) / resident;
     const int64_t grid = (n + trips - 1) / trips;
     F5Kernel k = k_conv_first5<0>;
+#if TH_KNOCKOUTS   // the knock-out build only (tools/build_knockouts.py): TH_FIRST_DBG instantiations
     if (kn.first_dbg == 1) k = k_conv_first5<1>;
     else if (kn.first_dbg == 2) k = k_conv_first5<2>;
     else if (kn.first_dbg == 4) k = k_conv_first5<4>;
     else if (kn.first_dbg == 7) k = k_conv_first5<7>;
+#endif
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(512), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) TH_FAIL(TH_EHIP, "conv_first5 launch failed: %s", hipGetErrorString(e));

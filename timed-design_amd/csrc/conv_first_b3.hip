@@ -464,10 +464,12 @@ __global__ void __launch_bounds__(512, 1) k_conv_first_b3(const ConvFirstB3Args 
 }
 
 typedef void (*FirstB3Kernel)(const ConvFirstB3Args);
+#if TH_KNOCKOUTS
 struct FirstB3Dbg { int code; FirstB3Kernel k; };
 const FirstB3Dbg kFirstB3Dbg[] = {{1, k_conv_first_b3<1>}, {2, k_conv_first_b3<2>}, {3, k_conv_first_b3<3>}, {4, k_conv_first_b3<4>},
                                   {8, k_conv_first_b3<8>}, {64, k_conv_first_b3<64>}, {131, k_conv_first_b3<131>}, {259, k_conv_first_b3<259>},
                                   {399, k_conv_first_b3<399>}};
+#endif
 
 }  // namespace
 
@@ -552,8 +554,10 @@ int launch_conv_first_b3(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const 
     // integer frames (uint8 / bool): one-piece data, 3 products (TH_FIRST_INT=0: the general kernel, same bits)
     const bool ints = (dtype == TH_U8 || dtype == TH_BOOL) && kn.first_int;
     FirstB3Kernel k = ints ? k_conv_first_b3<0, 1> : k_conv_first_b3<0>;
+#if TH_KNOCKOUTS   // the knock-out build only (tools/build_knockouts.py): TH_FIRST_DBG instantiations of the general kernel
     if (kn.first_dbg > 0)
         for (const FirstB3Dbg& d : kFirstB3Dbg) if (d.code == kn.first_dbg) k = d.k;
+#endif
     HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(512), kB3Lds, s, a);
     hipError_t e = hipGetLastError();

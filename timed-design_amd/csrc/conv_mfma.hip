@@ -37,17 +37,18 @@ constexpr size_t kLdsLimit = 160 * 1024;
 #ifndef STAGE_U
 #define STAGE_U 8  // staging loads in flight per thread
 #endif
-// -DCONV_PROF=1: per-wave s_memtime phase totals of k_conv_mfma printed by workgroup 0 (timing experiments)
-#ifndef CONV_PROF
-#define CONV_PROF 0
-#endif
 
 struct ConvMfmaArgs {
     const float* in; int64_t in_fs; int in_cs, in_coff, Din, Hin, Win, Cin, vec_ok;
     int kd, kh, kw, pz, py, px, ntaps;
     int Dc, Hc, Wc;
     int FB, ZB, nzb, Zp, Hp, Wp, rows_pf, nrows, n_mtiles;
-    int CS, nchunks, nnb, tab_off, zmajor, dbg;  // dbg: timing experiments only (TH_CONV_DBG), results are wrong when set
+    int CS, nchunks, nnb, tab_off, zmajor;
+    // TH_CONV_DBG timing knock-outs (the knock-out build only; results are WRONG when set): 1 only the first chunk is staged, 64 no
+    // next-chunk prefetch in k_conv_n16.  k_conv_n16 reads it as TH_KNOCK (common.h).  k_conv_mfma reads the field itself, 0 in the
+    // product build: with that one read folded to a constant seven of its TM = 4 instantiations, which spill already, spill one or
+    // two VGPRs more (4 to 8 bytes of scratch per lane), so the field stays for it.
+    int dbg;
     const float* wpk;
     int Cout;
     const float* bias;
@@ -76,10 +77,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_mfma(co
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
     const int CS4 = a.CS >> 2;
-#if CONV_PROF
-    const long long cp_t0 = clock64();
-    long long cp_tab = 0, cp_stage = 0, cp_mfma = 0, cp_epi = 0;
-#endif
 
     // ---- workgroup -> (frame group, z brick, channel block) ---------------------------------
     int bid = blockIdx.x;
@@ -191,9 +188,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_mfma(co
                 for (int i = 0; i < 16; ++i) acc[tm][tn][i] = 0.f;
 
         if (rd == 0) __syncthreads();  // row tables visible
-#if CONV_PROF
-        if (rd == 0) cp_tab = clock64() - cp_t0;
-#endif
         // a wave's TM m-tiles are interleaved (mb, mb + nmb, ...) so that every wave gets its share of the
         // boundary-plane tiles that skip taps
         const int nmb = (a.n_mtiles + TM - 1) / TM;
@@ -211,9 +205,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_mfma(co
             constexpr bool kLdsEpi = (TM * TN > 2);  // the LDS epilogue clobbers the staging area
             const bool need_a = (kLdsEpi || !(a.nchunks == 1 && rd > 0)) && !((a.dbg & 1) && ch > 0);
             const bool need_b = BRES == 2 ? false : (BRES ? need_a : true);
-#if CONV_PROF
-            const long long cp_a = clock64();
-#endif
             __syncthreads();  // everyone is done reading the previous A image / B slabs
             if (need_a) {
                 // ---- stage the haloed input brick for channels [ch*CI, ch*CI+CI) ------------------
@@ -328,10 +319,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_mfma(co
                 for (int i = tid; i < n4; i += NTHREADS) B4[i] = wch4[i];
             }
             __syncthreads();
-#if CONV_PROF
-            const long long cp_b = clock64();
-            cp_stage += cp_b - cp_a;
-#endif
 
             if (BRES == 2) {
                 // weights streamed L2 -> registers, one tap ahead: every lane fetches exactly its own MFMA
@@ -590,13 +577,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_mfma(co
                             }
                         }
             }
-#if CONV_PROF
-            cp_mfma += clock64() - cp_b;
-#endif
         }  // chunks
-#if CONV_PROF
-        const long long cp_e = clock64();
-#endif
 
         // ---- epilogue: bias, activation / BN-affine chain, optional 2x2x2 pool, store ------------
         constexpr bool REG_EPI = (TM * TN <= 2);
@@ -743,15 +724,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_mfma(co
             }
             }
         }
-#if CONV_PROF
-        cp_epi += clock64() - cp_e;
-#endif
     }  // rounds
-#if CONV_PROF
-    if (blockIdx.x == 0 && lane == 0)
-        printf("conv_mfma prof wave %d: total %lld  tables %lld  staging+barriers %lld  mfma-phase %lld  epilogue %lld (s_memtime ticks)\n", wave,
-               clock64() - cp_t0, cp_tab, cp_stage, cp_mfma, cp_epi);
-#endif
 }
 
 // =====================================================================================================
@@ -771,13 +744,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
-
-// Compile-time knock-outs for timing experiments on k_conv_n16's inner loop (results are WRONG when set; build a
-// second library with -DN16_KNOCK=n and load it through TIMED_HIP_LIB): 1 no weight-ring refills, 2 A fragments read
-// from conflict-free dummy addresses, 4 no A-fragment reads after tap 0.
-#ifndef N16_KNOCK
-#define N16_KNOCK 0
-#endif
 
 // XC > 0: output channels 16..16+XC-1 (Cout = 17..20, e.g. the 20 amino-acid classes of a TIMED head) ride on
 // v_mfma_f32_4x4x1_16B_f32 from the SAME A registers: the instruction is 16 independent 4x4 outer products (lane
@@ -881,7 +847,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
     const int nzr = min(a.Zp, a.Din + a.pz - z0) - zlo, nyr = min(a.Hp, a.Hin + a.py) - ylo, nxr = min(a.Wp, a.Win + a.px) - xlo;
     const int real_pf = nzr * nyr * nxr;          // real voxels of one staged frame
     const int nreal4 = a.FB * real_pf * CI4;
-    const bool can_pf = rounds == 1 && nreal4 <= PF * NTHREADS && nzr > 0 && nyr > 0 && nxr > 0 && a.vec_ok && (a.Cin & 3) == 0 && !(a.dbg & 64);
+    const bool can_pf = rounds == 1 && nreal4 <= PF * NTHREADS && nzr > 0 && nyr > 0 && nxr > 0 && a.vec_ok && (a.Cin & 3) == 0 && !(TH_KNOCK(a) & 64);
 
     // nvalid: frames of the group that exist (the last group of a batch may be ragged)
     auto load_vec = [&](const float* inb, int nvalid, int ch, int i, bool* okp) -> float4 {
@@ -978,9 +944,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
         }
     }
     bool staged = false;   // chunk 0 of the current group was already written to LDS from the prefetch registers
-#if N16_KNOCK & 8
-    long long prof_t0 = clock64(), prof_mfma = 0, prof_bar = 0, prof_epi = 0, prof_pf = 0, prof_issue = 0, prof_grp = 0;
-#endif
     for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const int64_t f0 = grp / a.nzb * a.FB;
         const int nvalid = (int)min((int64_t)a.FB, a.nframes - f0);
@@ -992,16 +955,11 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
         const float* inb_next = a.in + f0_next * a.in_fs + a.in_coff;
         const int nvalid_next = has_next ? (int)min((int64_t)a.FB, a.nframes - f0_next) : nvalid;
         // a ragged group (the last one of a launch) takes the plain staging path, which knows about missing frames
-        const bool grp_pf = can_pf && nvalid == a.FB && !(a.dbg & 1);
-        const bool nxt_pf = can_pf && has_next && nvalid_next == a.FB && !(a.dbg & 1);
+        const bool grp_pf = can_pf && nvalid == a.FB && !(TH_KNOCK(a) & 1);
+        const bool nxt_pf = can_pf && has_next && nvalid_next == a.FB && !(TH_KNOCK(a) & 1);
         const __amdgpu_buffer_rsrc_t rs_cur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(inb0), 0, (int)a.in_grp_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_nxt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(inb_next), 0, (int)a.in_grp_bytes, 0x00020000);
 
-#if N16_KNOCK & 8
-        long long prof_d = 0;
-        const long long prof_g0 = clock64();
-        bool prof_first = true;
-#endif
         for (int rd = 0; rd < rounds; ++rd) {
             const int blk = rd * WAVES + wave;
             const bool active = blk < total_blocks;
@@ -1018,11 +976,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                 aidx[tm] = ((active && mt < n_mt) ? ROWVOX(mt * 16 + i16) : 0) * CS4 + q;
             }
             for (int ch = 0; ch < a.nchunks; ++ch) {
-                const bool need_a = !(a.nchunks == 1 && rd > 0) && !((a.dbg & 1) && (ch > 0 || grp != blockIdx.x));
-#if N16_KNOCK & 8
-                long long prof_a = clock64();
-                if (prof_first) { prof_grp += prof_a - prof_g0; prof_first = false; }
-#endif
+                const bool need_a = !(a.nchunks == 1 && rd > 0) && !((TH_KNOCK(a) & 1) && (ch > 0 || grp != blockIdx.x));
                 if (!(ch > 0 ? grp_pf : staged)) {   // otherwise this chunk was written from registers already
                     __syncthreads();
                     if (need_a) {
@@ -1038,10 +992,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                     }
                 }
                 __syncthreads();
-#if N16_KNOCK & 8
-                const long long prof_a2 = clock64();
-                prof_bar += prof_a2 - prof_a;
-#endif
                 const bool last_ch = ch + 1 == a.nchunks;
                 const bool do_pf = last_ch ? nxt_pf : grp_pf;
                 const int pch = last_ch ? 0 : ch + 1;
@@ -1069,10 +1019,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                 const bool pbn = a.pre.scale && can_pf;   // can_pf: Cin % 4 == 0, so pc0 is aligned and in bounds
                 const float4 psc = *reinterpret_cast<const float4*>(pbn ? a.pre.scale + pc0 : a.wpk);
                 const float4 psh = *reinterpret_cast<const float4*>(pbn ? a.pre.shift + pc0 : a.wpk);
-#if N16_KNOCK & 8
-                long long prof_b = clock64();
-                prof_issue += prof_b - prof_a2;
-#endif
                 const char* wsc = reinterpret_cast<const char*>(a.wpk) + (size_t)ch * (NTAPS * 1024);          // uniform
                 const char* wxs = reinterpret_cast<const char*>(a.wx) + (size_t)ch * (NTAPS * 4 * (XC ? XC : 1) * 16);
                 if (active) {
@@ -1093,9 +1039,9 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                         // runtime geometry: opaque to LICM, otherwise hipcc hoists all 27*TM read addresses out of the
                         // chunk loop and spills them to scratch
                         if (!GEO) asm volatile("" : "+s"(noff));
-                        if (PING && nt < NTAPS && !(N16_KNOCK & 4)) {
+                        if (PING && nt < NTAPS) {
 #pragma unroll
-                            for (int tm = 0; tm < TM; ++tm) av[nt & 1][tm] = (N16_KNOCK & 2) ? A4v[tid + tm * NTHREADS + (nt & 1) * 64] : A4v[aidx[tm] + noff];
+                            for (int tm = 0; tm < TM; ++tm) av[nt & 1][tm] = A4v[aidx[tm] + noff];
                         }
                         __builtin_amdgcn_sched_barrier(0);
                         if (!XC) {
@@ -1128,9 +1074,9 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                             xw[t % 3] = *reinterpret_cast<const f32x4*>(wxs + voffx[xb >> 12] + (xb & 4095));
                         }
                         if (!PING) {
-                            if (nt < NTAPS && !(N16_KNOCK & 4)) {
+                            if (nt < NTAPS) {
 #pragma unroll
-                                for (int tm = 0; tm < HT; ++tm) av[0][tm] = (N16_KNOCK & 2) ? A4v[tid + tm * NTHREADS + (nt & 1) * 64] : A4v[aidx[tm] + noff];
+                                for (int tm = 0; tm < HT; ++tm) av[0][tm] = A4v[aidx[tm] + noff];
                             }
                             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1143,18 +1089,13 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                             }
                             __builtin_amdgcn_sched_barrier(0);
                         }
-                        if (!(N16_KNOCK & 1))
-                            breg[t % BR] = *reinterpret_cast<const float4*>(wsc + voff[(t + BR) >> 2] + ((t + BR) & 3) * 1024);
-                        if (!PING && nt < NTAPS && !(N16_KNOCK & 4)) {
+                        breg[t % BR] = *reinterpret_cast<const float4*>(wsc + voff[(t + BR) >> 2] + ((t + BR) & 3) * 1024);
+                        if (!PING && nt < NTAPS) {
 #pragma unroll
-                            for (int tm = HT; tm < TM; ++tm) av[0][tm] = (N16_KNOCK & 2) ? A4v[tid + tm * NTHREADS + (nt & 1) * 64] : A4v[aidx[tm] + noff];
+                            for (int tm = HT; tm < TM; ++tm) av[0][tm] = A4v[aidx[tm] + noff];
                         }
                     }
                 }
-#if N16_KNOCK & 8
-                prof_mfma += clock64() - prof_b;
-                long long prof_c = clock64();
-#endif
                 if (do_pf) {
                     // BN -> activation prologue in registers BEFORE the barrier (overlaps the other waves' last MFMAs).  The
                     // activation is decoded ONCE for all 4 PF values (th_act_vec): th_act's switch inlined per element
@@ -1181,13 +1122,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                     for (int u = 0; u < PF; ++u)
                         if (pf_boff[u] != OOB) A4[pf_dst[u]] = pfv[u];
                 }
-#if N16_KNOCK & 8
-                prof_pf += clock64() - prof_c;
-#endif
             }
-#if N16_KNOCK & 8
-            prof_d = clock64();
-#endif
             // ---- epilogue in registers: C layout col = lane&15, row = 4*(lane>>4) + reg --------------------
             if (active) {
 #pragma unroll
@@ -1247,16 +1182,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) k_conv_n16(con
                 }
             }
         }
-#if N16_KNOCK & 8
-        prof_epi += clock64() - prof_d;
-#endif
         staged = nxt_pf;
     }
-#if N16_KNOCK & 8
-    if (blockIdx.x == 0 && lane == 0)
-        printf("n16 prof wave %d: total %lld  mfma-phase %lld  barrier+stage %lld  prefetch-issue %lld  pf-write %lld  epilogue %lld  group-setup %lld (s_memtime ticks)\n", wave,
-               clock64() - prof_t0, prof_mfma, prof_bar, prof_issue, prof_pf, prof_epi, prof_grp);
-#endif
 }
 
 #undef ROWVOX
@@ -1601,7 +1528,7 @@ int launch_conv_mfma(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, 
     a.tab_off = (int)p.tab_off;
     const ThKnobs& kn = th_knobs_of(p.knobs);
     { const bool nozm = kn.conv_nozmajor != 0; a.zmajor = (!nozm && !n16 && p.pool == 0 && p.bres == 2 && c.CI == 16 && g.sd == 1 && g.sh == 1 && g.sw == 1) ? 1 : 0; }
-    a.dbg = kn.conv_dbg;
+    TH_KNOCK_SET(a, kn.conv_dbg);
     a.wpk = wpk; a.Cout = Cout; a.bias = bias; a.pre = pre; a.post = post;
     a.wx = n16 ? wpk + ((size_t)p.nchunks * 27 + 9) * 256 : wpk;
     a.in_grp_bytes = (unsigned)std::min<int64_t>(0xfffffff0LL, ((int64_t)(p.FB - 1) * in.fs + ((int64_t)in.D * in.H * in.W - 1) * in.cs + Cin) * 4);
@@ -1632,8 +1559,7 @@ int launch_conv_mfma(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, 
         for (const N16Geo& ge : kN16Geo)
             if (ge.variant == p.cfg - 200 && ge.geo == p.geo) k = ge.k;
     HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
-    const size_t lds_pad = (size_t)std::max(0, kn.conv_ldspad);  // occupancy experiments
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(c.WAVES * 64), std::min(p.lds_bytes + lds_pad, kLdsLimit), s, a);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(c.WAVES * 64), p.lds_bytes, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) TH_FAIL(TH_EHIP, "conv_mfma launch failed: %s (%s)", hipGetErrorString(e), p.label.c_str());
     return TH_OK;

@@ -155,7 +155,7 @@ int launch_conv_pw(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, TV
     if (nrows >= 0x7fffffffLL) TH_FAIL(TH_EINVAL, "conv_pw: %lld rows per launch exceed the 32-bit row index; lower the chunk size", (long long)nrows);
     a.nrows = (unsigned)nrows;
     a.ntiles = (unsigned)((nrows + 31) / 32);
-    a.dbg = th_knobs_of(p.knobs).pw_dbg;
+    TH_KNOCK_SET(a, th_knobs_of(p.knobs).pw_dbg);
     const unsigned want = (a.ntiles + 3) / 4;
     const unsigned grid = std::min(want, 256u * 8u);   // persistent: up to 8 workgroups per CU queued, waves stride over tiles
     PwKernel k = kPw[kmi][nti][p.pool];

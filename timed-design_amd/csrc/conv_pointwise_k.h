@@ -25,7 +25,10 @@ struct ConvPwArgs {
     unsigned nrows;     // GEMM rows: frames*V, or frames*Vo*8 when pooled
     unsigned ntiles;
     unsigned in_bytes, out_bytes;   // k_conv_pw2: byte spans of the activation views (buffer descriptors, < 4 GiB)
-    int dbg;            // k_conv_pw2 timing knock-outs (TH_PW_DBG; results are WRONG when set): 1 no loads, 2 no stores
+    // k_conv_pw2 timing knock-outs (TH_PW_DBG, the knock-out build only; results are WRONG when set): 1 no loads, 2 no stores.
+    // A plain field, 0 in the product build, and not TH_KNOCK (common.h): with the reads folded to a constant hipcc spills
+    // 17 VGPRs (44 bytes of scratch per lane) in k_conv_pw2<12, 2, 1|2, 0, 0>, which have none with the run-time read.
+    int dbg;
 };
 
 // this lane's input row for a tile: lane j supplies GEMM row tile*32 + j (POOL: pooled voxel tile*4 + j/8, mate j%8);

@@ -499,10 +499,12 @@ struct WfsGeo { int D, H, W; WfsKernel k[3]; };      // [pool]
 #define WFS_INST(D, H, W) {D, H, W, {k_conv_wfs<D, H, W, 0>, k_conv_wfs<D, H, W, 1>, k_conv_wfs<D, H, W, 2>}}
 const WfsGeo kWfsGeo[] = {WFS_INST(10, 10, 10)};
 #undef WFS_INST
+#if TH_KNOCKOUTS
 struct WfsDbg { int code; WfsKernel k; };
 #define WFS_DBG(c) {c, k_conv_wfs<10, 10, 10, 1, c>}
 const WfsDbg kWfsDbg[] = {WFS_DBG(1), WFS_DBG(2), WFS_DBG(3), WFS_DBG(4), WFS_DBG(8), WFS_DBG(16), WFS_DBG(20), WFS_DBG(21), WFS_DBG(32), WFS_DBG(29), WFS_DBG(533), WFS_DBG(1045), WFS_DBG(1565), WFS_DBG(1024), WFS_DBG(2048), WFS_DBG(4096), WFS_DBG(8192), WFS_DBG(6144)};
 #undef WFS_DBG
+#endif
 
 size_t wfs_lds_bytes(int D, int H, int W) {
     const int rsl = (D * H + 1) * (W + 1);
@@ -600,8 +602,10 @@ int launch_conv_wfs(hipStream_t s, int64_t n, const ConvWfsPlan& p, TView in, TV
     int64_t grid = (nslots + trips - 1) / trips;
     grid = (grid + 7) / 8 * 8;
     WfsKernel k = kWfsGeo[p.geo].k[p.pool];
+#if TH_KNOCKOUTS   // the knock-out build only (tools/build_knockouts.py): TH_WF_DBG instantiations of the pooled 10^3 kernel
     if (kn.wf_dbg > 0 && p.geo == 0 && p.pool == 1)
         for (const WfsDbg& d : kWfsDbg) if (d.code == kn.wf_dbg) k = d.k;
+#endif
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(512), 0, s, a);            // (static LDS)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) TH_FAIL(TH_EHIP, "conv_wfs launch failed: %s (%s)", hipGetErrorString(e), p.label.c_str());

@@ -479,10 +479,12 @@ struct WfGeo { int D, H, W; WfKernel k[3][3]; };     // [pool][pre]
                                     {k_conv_wf<D, H, W, 2, 0>, k_conv_wf<D, H, W, 2, 1>, k_conv_wf<D, H, W, 2, 2>}}}
 const WfGeo kWfGeo[] = {WF_INST(10, 10, 10)};
 #undef WF_INST
+#if TH_KNOCKOUTS
 struct WfDbg { int code; WfKernel k; };
 #define WF_DBG(c) {c, k_conv_wf<10, 10, 10, 0, 0, c>}
 const WfDbg kWfDbg[] = {WF_DBG(1), WF_DBG(2), WF_DBG(3), WF_DBG(4), WF_DBG(7), WF_DBG(8), WF_DBG(15), WF_DBG(32), WF_DBG(64), WF_DBG(256)};
 #undef WF_DBG
+#endif
 
 }  // namespace
 
@@ -578,11 +580,10 @@ int launch_conv_wf(hipStream_t s, int64_t n, const ConvWfPlan& p, TView in, TVie
     const int pre_kind = conv_wf_pre_kind(pre);
     WfKernel k = kWfGeo[p.geo].k[p.pool][pre_kind];
     const size_t lds = p.lds_bytes;
-    {   // timing experiments only (tools/bench_layer.py): knock-out instantiations of the plain 10^3 kernel
-        const int dbg = kn.wf_dbg;
-        if (dbg > 0 && p.geo == 0 && p.pool == 0 && pre_kind == 0)
-            for (const WfDbg& d : kWfDbg) if (d.code == dbg) k = d.k;
-    }
+#if TH_KNOCKOUTS   // the knock-out build only (tools/build_knockouts.py): TH_WF_DBG instantiations of the plain 10^3 kernel
+    if (kn.wf_dbg > 0 && p.geo == 0 && p.pool == 0 && pre_kind == 0)
+        for (const WfDbg& d : kWfDbg) if (d.code == kn.wf_dbg) k = d.k;
+#endif
     HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWfLdsLimit));
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(512), lds, s, a);
     hipError_t e = hipGetLastError();

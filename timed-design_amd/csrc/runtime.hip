@@ -40,7 +40,7 @@ void th_set_error(const char* fmt, ...) {
 }
 
 // ---- A/B and test knobs (ThKnobs, common.h) ---------------------------------------------------------------------------------
-void th_knobs_read(ThKnobs* k) {
+int th_knobs_read(ThKnobs* k) {
     *k = ThKnobs();
     std::string& nd = k->nondefault;
     auto note = [&](const char* name, const char* v) { nd += (nd.empty() ? "" : " "); nd += name; nd += "="; nd += v; };
@@ -55,6 +55,13 @@ void th_knobs_read(ThKnobs* k) {
         const char* e = getenv(name);                                    // (NAME=0 used to switch these ON by presence)
         if (e && *e && atoi(e) != 0) { *dst = 1; note(name, e); }
     };
+    const char* refused = nullptr;      // a knock-out variable that is set where no knock-out exists: whole kernels must not be timed as knocked out
+#if TH_KNOCKOUTS
+#define KNOCK(name, field) num(name, &k->field, 0, 1 << 20)
+#else
+    auto refuse = [&](const char* name) { const char* e = getenv(name); if (!refused && e && atoi(e) != 0) refused = name; };
+#define KNOCK(name, field) refuse(name)
+#endif
     num("TH_WINOGRAD", &k->winograd, 0, 2);
     num("TH_WINO_SPLIT", &k->wino_split, 0, 1);
     num("TH_WFUSED", &k->wfused, 0, 1);
@@ -67,8 +74,7 @@ void th_knobs_read(ThKnobs* k) {
     num("TH_FIRST_INT", &k->first_int, 0, 1);
     num("TH_DENSE_GEMM", &k->dense_gemm, 0, 1);
     num("TH_CONV_GL", &k->conv_gl, 0, 2);
-    num("TH_FIRST_ZB", &k->first_zb, 0, 1 << 20);
-    num("TH_FIRST_DBG", &k->first_dbg, 0, 1 << 20);
+    KNOCK("TH_FIRST_DBG", first_dbg);
     flag("TH_NO_POOL_FIRST", &k->no_pool_first);
     flag("TH_NO_TAIL_FUSE", &k->no_tail_fuse);
     flag("TH_CONV_NOGEO", &k->conv_nogeo);
@@ -82,19 +88,23 @@ void th_knobs_read(ThKnobs* k) {
         k->conv_bmode = !std::strcmp(e, "dbuf") ? 1 : !std::strcmp(e, "stream8") ? 2 : !std::strcmp(e, "no16") ? 3 : 0;
         if (k->conv_bmode) note("TH_CONV_BMODE", e);
     }
-    num("TH_CONV_DBG", &k->conv_dbg, 0, 1 << 20);
-    num("TH_CONV_LDSPAD", &k->conv_ldspad, 0, 160 * 1024);
+    KNOCK("TH_CONV_DBG", conv_dbg);
     num("TH_N16_RESIDENT", &k->n16_resident, 0, 1 << 20);
     flag("TH_PW_NOPIPE", &k->pw_nopipe);
     flag("TH_PW_NOEPI", &k->pw_noepi);
-    num("TH_PW_DBG", &k->pw_dbg, 0, 1 << 20);
+    KNOCK("TH_PW_DBG", pw_dbg);
     num("TH_WF_RESIDENT", &k->wf_resident, 0, 1 << 20);
-    num("TH_WF_DBG", &k->wf_dbg, 0, 1 << 20);
+    KNOCK("TH_WF_DBG", wf_dbg);
     num("TH_WF_NOBLK", &k->wf_noblk, 0, 1);
     if (const char* e = getenv("TH_WINO_PIECE")) { k->wino_piece = std::max(0ll, atoll(e)); if (k->wino_piece) note("TH_WINO_PIECE", e); }
-    num("TH_WINO_DBG", &k->wino_dbg, 0, 1 << 20);
+    KNOCK("TH_WINO_DBG", wino_dbg);
     num("TH_WINO_B3VAR", &k->wino_b3var, 0, 2);
     num("TH_WINO_NOMID", &k->wino_nomid, 0, 1);
+#undef KNOCK
+    if (refused)
+        TH_FAIL(TH_EINVAL, "%s is set, but this library has no timing knock-outs: build the knock-out library "
+                           "(tools/build_knockouts.py) and load it through TIMED_HIP_LIB", refused);
+    return TH_OK;
 }
 
 // ---- device block cache ---------------------------------------------------------------------------------------------------
@@ -1569,7 +1579,7 @@ int run_device(th_model* m, const void* d_frames, int dtype, int64_t n, float* d
     return TH_OK;
 }
 
-int load_common(th_model* m, const ThKnobs* forced = nullptr) {
+int load_common(th_model* m, const ThKnobs& knobs) {
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceGetAttribute(&m->ncu, hipDeviceAttributeMultiprocessorCount, m->device));
     HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
@@ -1578,9 +1588,7 @@ int load_common(th_model* m, const ThKnobs* forced = nullptr) {
     HIP_TRY(hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
-    // every A/B / test knob of this handle, read here and nowhere else (ThKnobs, common.h)
-    if (forced) m->knobs = *forced;             // (the load-time guard's reference / fallback plans)
-    else th_knobs_read(&m->knobs);
+    m->knobs = knobs;       // every A/B / test knob of this handle: the environment as th_model_load_mem read it, or the load-time guard's
     m->lanes = m->knobs.lanes; m->lane_lag = m->knobs.lane_lag;
     for (int r = 0; r < th_model::kRing; ++r) {
         HIP_TRY(hipEventCreateWithFlags(&m->ev_h2d[r], hipEventDisableTiming));
@@ -1869,18 +1877,21 @@ int th_device_info(int device, char* name, size_t name_len, char* arch, size_t a
 
 int th_model_load_mem(const void* pack, size_t nbytes, int device, unsigned flags, th_model** out) {
     if (!pack || !out) TH_FAIL(TH_EINVAL, "null argument");
+    ThKnobs env;            // read here and nowhere else (ThKnobs, common.h), before the device is touched
+    int rc = th_knobs_read(&env);
+    if (rc) return rc;
     std::unique_ptr<th_model> m(new th_model);
     m->device = device;
     m->flags = flags;
     m->pack.assign((const char*)pack, (const char*)pack + nbytes);
-    int rc = load_common(m.get());
+    rc = load_common(m.get(), env);
     if (rc) { th_model_free(m.release()); return rc; }
     auto reload = [&](const ThKnobs& k, int* lrc) -> th_model* {          // another plan of the same pack under other knobs
         std::unique_ptr<th_model> x(new th_model);
         x->device = device;
         x->flags = flags;
         x->pack.assign((const char*)pack, (const char*)pack + nbytes);
-        *lrc = load_common(x.get(), &k);
+        *lrc = load_common(x.get(), k);
         if (*lrc) { th_model_free(x.release()); return nullptr; }
         return x.release();
     };

@@ -34,4 +34,4 @@ for s in m.steps():
     if s["launches"] and s["flops"]:
         ms = s["ms"] / 3
         print(json.dumps(dict(label=s["label"], ms_per_4096=ms * 4096 / n, tflops_algo=s["flops"] * n / (ms * 1e-3) / 1e12,
-                              frac=s["flops"] * n / (ms * 1e-3) / 1e12 / 157.3, env={k: v for k, v in os.environ.items() if k.startswith("TH_")})))
+                              frac=s["flops"] * n / (ms * 1e-3) / 1e12 / 157.3, knobs=m.knobs(), env={k: v for k, v in os.environ.items() if k.startswith("TH_")})))
