@@ -414,6 +414,65 @@ int th_tag_rotamers(int device, const double* xyz, const uint32_t* atom_name, in
  * may be NULL.  Host code. */
 int th_rotamer_table(int res_type, int* n_chi, int* class_base, char names[7][4]);
 
+/* ---- superposition of models on their native: analyse_models.py — what the reference's calculate_RMSD_and_gdt
+ * (scripts/analyse_af2.py) gets from PyMOL one pair at a time: cmd.align on the CA atoms, its RMSD, and the fractions of aligned
+ * pairs within 1, 2, 4 and 8 Angstrom.  Here for a BATCH of position-paired coordinate lists in one launch.
+ *
+ *     *** PARITY UNPINNED AGAINST PYMOL ***  PyMOL is not available where this project is built.  The rule below is this project's
+ *     reading of the DOCUMENTED behaviour of cmd.align (cycles default 5, cutoff default 2.0: "outlier rejection cutoff in RMS") on
+ *     atoms that are already paired by position; it is not PyMOL's code, it aligns no sequences, and no test can pin it against
+ *     PyMOL itself.
+ *
+ * All arrays are host memory.
+ *   ref_xyz, mob_xyz   double[total][3]: the reference (target) and the mobile coordinates of all pairs, pair after pair; position i
+ *                      of one list is paired with position i of the other (any value, NaN and infinities included);
+ *   total              number of positions, 0 <= total <= 2^31 - 1;
+ *   offsets            int64[n_pairs + 1]: pair p owns positions offsets[p] .. offsets[p + 1] of both lists; offsets[0] = 0,
+ *                      non-decreasing, offsets[n_pairs] = total.  A pair may be empty;
+ *   n_pairs            0 <= n_pairs <= 2^31 - 1;
+ *   cycles             refinement cycles at most, >= 0 (PyMOL's default: 5);
+ *   cutoff             outlier rejection in units of the RMS, finite and > 0 (PyMOL's default: 2.0);
+ *   dist_out           double[total]: d_i under the final fit, NaN at an invalid position;
+ *   kept_out           uint8[total]: 1 where the position is in the final kept set;
+ *   rmsd_out           double[n_pairs][3]: rmsd_kept, rmsd_all, rmsd_fit_all;
+ *   count_out          int32[n_pairs][7]: n_valid, n_kept, cycles_run, then the number of valid positions with d_i <= 1, 2, 4, 8;
+ *   transform_out      double[n_pairs][12] or NULL: rows of [R | t], moved = R mob + t with t = cr - R cm (the identity when no
+ *                      position is valid);
+ *   kernel_ms          NULL, or receives the device time of the kernel (events around it), in milliseconds.
+ * The rule, for one pair of equally long lists ref[i], mob[i], all arithmetic float64:
+ *   - a position is VALID when all six coordinates are finite.  An invalid position is never kept, its d_i is NaN and it counts in
+ *     no total;
+ *   - FIT over a kept set: the centroids cm, cr are plain sums over the kept positions in index order, divided by the count (the
+ *     kernel sums each lane's positions l, l + 64, ... in index order and then the 64 lanes in a fixed tree).  The 3 x 3
+ *     cross-covariance S[x][y] = sum (mob - cm)_x (ref - cr)_y is taken over the centred coordinates: two passes, never
+ *     sum xy - n mean(x) mean(y).  The rotation is the PROPER one (determinant +1) that minimises the squared deviation, from Horn's
+ *     symmetric 4 x 4 matrix
+ *         [ Sxx+Syy+Szz   Syz-Szy       Szx-Sxz       Sxy-Syx     ]
+ *         [ Syz-Szy       Sxx-Syy-Szz   Sxy+Syx       Szx+Sxz     ]
+ *         [ Szx-Sxz       Sxy+Syx      -Sxx+Syy-Szz   Syz+Szy     ]
+ *         [ Sxy-Syx       Szx+Sxz       Syz+Szy      -Sxx-Syy+Szz ]
+ *     whose unit eigenvector of largest eigenvalue (cyclic Jacobi, pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), at most 10 sweeps; of
+ *     equal eigenvalues the first) is the quaternion (w, x, y, z) of R.  A mirror image therefore gives a large RMSD, not zero;
+ *   - moved_i = R (mob_i - cm) + cr for every valid position, and d_i = |moved_i - ref_i|, the square root of a sum of three
+ *     squares, computed as such (not through the eigenvalue);
+ *   - cycle 0 keeps every valid position.  REFINEMENT, at most `cycles` times: rms = sqrt(sum over kept of d_i^2 / n_kept); the kept
+ *     positions with d_i > cutoff * rms are dropped and the fit is made again over the smaller set — unless none is dropped or
+ *     fewer than 3 would remain: the set then stays as it is and refinement ends.  cycles_run counts the fits made after cycle 0;
+ *   - rmsd_kept: over the final kept set under the final fit (the number cmd.align returns); rmsd_all: over all valid positions
+ *     under the final fit; rmsd_fit_all: the value of cycle 0, the conventional RMSD of the whole set.  The counts within 1, 2, 4 and
+ *     8 Angstrom are over all valid positions under the final fit; the GDT fractions and their mean are formed by the caller;
+ *   - n_valid = 0: the three RMSDs are NaN and all counts 0.  n_valid = 1 or 2: the fit is made (its RMSD is the unique minimum, its
+ *     rotation need not be unique) and there is no refinement.
+ * One launch for the whole batch, the refinement loop inside the kernel; no atomics.  A pair's outputs depend on its own coordinates
+ * alone — not on its place in the batch or on its neighbours — and two calls give the same bytes.  Device memory: 57 bytes per
+ * position + 60 (156 with transform_out) per pair.  TH_EINVAL, before anything is launched or written: a negative or too large size,
+ * a NULL that is required (offsets, rmsd_out, count_out; with total > 0 also both lists, dist_out and kept_out), offsets that
+ * decrease, do not start at 0 or do not end at total, cycles < 0, cutoff not finite or <= 0.  n_pairs = 0 (with total = 0) is
+ * success without a launch. */
+int th_superpose(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
+                 int cycles, double cutoff, double* dist_out, uint8_t* kept_out, double* rmsd_out, int32_t* count_out,
+                 double* transform_out, double* kernel_ms);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

@@ -1,0 +1,120 @@
+"""analyse_models.py — score structure models against their native backbone: RMSD after superposition, the GDT fractions and the
+deviation of every residue, for all pairs in as few th_superpose submissions as the byte budget allows.  This is the step of the
+reference's evaluation chain that scripts/analyse_af2.py does one PyMOL call at a time (calculate_RMSD_and_gdt: cmd.align on the CA
+atoms, then the fractions of aligned pairs within 1, 2, 4 and 8 Angstrom).
+
+    python analyse_models.py --path_to_reference native/1ubq.pdb1.gz --path_to_models af2_models/ --path_to_output scores
+    python analyse_models.py --pairs pairs.csv --path_to_output scores
+
+--pairs reads lines of ``reference_path,model_path[,label]`` (relative paths are taken from the CSV's directory).  Every file is
+parsed once, on host threads, however many pairs name it.
+
+Writes ``model_scores.csv``, one row per pair — label, reference, model, n_valid, n_kept, cycles_run, rmsd_kept (the number
+cmd.align returns: over the positions the refinement kept), rmsd_all (every position under that final fit), rmsd_fit_all (the
+conventional CA RMSD: one fit over every position), gdt_1, gdt_2, gdt_4, gdt_8 and mean_gdt (the reference's column),
+sequence_identity (the reference's seq_accuracy), unpaired_reference, unpaired_model, error — and ``residue_deviation.csv`` — label,
+chain, residue number (of the reference), the distance d_i under the final fit and whether the refinement kept the position.
+
+PARITY UNPINNED AGAINST PYMOL: PyMOL is not available to pin this against.  The rule is this project's reading of the documented
+behaviour of cmd.align (cycles 5, cutoff 2.0), written out in include/timed_hip.h and timed_hip/superpose.py: a least-squares fit
+with a proper rotation, then up to --cycles rounds that drop positions further than --cutoff x RMS and fit again.  Pairing is by
+position (file order; native and model must be equally long, as the reference asserts) or by number (chain, residue number and
+insertion code), NOT by a sequence alignment.  Out of scope: AlphaFold2 folder layouts and parsing FASTA or file names into model /
+temperature / sample columns — the label is the model's path below --path_to_models, or the third CSV field.
+"""
+import argparse
+import csv
+import sys
+from pathlib import Path
+
+from analyse_properties import find_structures
+from timed_hip import superpose
+
+SCORE_COLUMNS = ["label", "reference", "model", "n_valid", "n_kept", "cycles_run", "rmsd_kept", "rmsd_all", "rmsd_fit_all", "gdt_1", "gdt_2",
+                 "gdt_4", "gdt_8", "mean_gdt", "sequence_identity", "unpaired_reference", "unpaired_model", "error"]
+RESIDUE_COLUMNS = ["label", "chain", "residue_number", "distance", "kept"]
+
+
+def read_pairs(path):
+    """[(label, reference path, model path)] of a --pairs CSV; empty lines and lines starting with # are skipped"""
+    path = Path(path)
+    out = []
+    with open(path, newline="") as f:
+        for row in csv.reader(f):
+            row = [field.strip() for field in row]
+            if not row or not any(row) or row[0].startswith("#"):
+                continue
+            if len(row) < 2 or not row[0] or not row[1]:
+                sys.exit(f"{path}: a line needs reference_path,model_path[,label], got {row}")
+            ref, model = (p if p.is_absolute() else path.parent / p for p in (Path(row[0]), Path(row[1])))
+            out.append((row[2] if len(row) > 2 and row[2] else row[1], ref, model))
+    return out
+
+
+def _fmt(v: float) -> str:
+    return repr(float(v))
+
+
+def main(args):
+    if args.pairs:
+        if args.path_to_reference or args.path_to_models:
+            sys.exit("--pairs replaces --path_to_reference / --path_to_models")
+        todo = read_pairs(args.pairs)
+    else:
+        if not (args.path_to_reference and args.path_to_models):
+            sys.exit("give --path_to_reference FILE --path_to_models DIR_OR_FILES, or --pairs CSV")
+        reference = Path(args.path_to_reference)
+        if not reference.is_file():
+            sys.exit(f"no reference file at {reference}")
+        todo = [(label, reference, path) for label, path in find_structures(args.path_to_models)]
+    if not todo:
+        sys.exit("no pair to score: no *.pdb / *.pdb1 / *.ent (.gz) file under --path_to_models, or an empty --pairs file")
+    stats = {}
+    results = superpose.superpose([(ref, model) for _, ref, model in todo], pair_by=args.pair_by, cycles=args.cycles, cutoff=args.cutoff,
+                                  device=args.device, workers=args.workers, stats=stats)
+    out = Path(args.path_to_output)
+    out.mkdir(parents=True, exist_ok=True)
+    with open(out / "model_scores.csv", "w", newline="") as fs, open(out / "residue_deviation.csv", "w", newline="") as fr:
+        ws, wr = csv.writer(fs), csv.writer(fr)
+        ws.writerow(SCORE_COLUMNS)
+        wr.writerow(RESIDUE_COLUMNS)
+        for (label, ref, model), res in zip(todo, results):
+            ws.writerow([label, str(ref), str(model), res.n_valid, res.n_kept, res.cycles_run, _fmt(res.rmsd_kept), _fmt(res.rmsd_all),
+                         _fmt(res.rmsd_fit_all)] + [_fmt(g) for g in res.gdt] + [_fmt(res.mean_gdt), _fmt(res.sequence_identity),
+                                                                                res.unpaired_reference, res.unpaired_model, res.error or ""])
+            for r, d, k in zip(res.residues, res.dist, res.kept.tolist()):
+                wr.writerow([label, r.chain, r.number, _fmt(d), k])
+    failed = sum(1 for res in results if res.error)
+    print(f"{len(todo)} pairs ({failed} with an error), {sum(len(res.dist) for res in results)} positions, {stats.get('files_parsed', 0)} files parsed "
+          f"in {stats.get('submissions', 0)} GPU submission(s) -> {out}")
+    return results
+
+
+# (flag, argparse keywords)
+CLI_FLAGS = (
+    ("--path_to_reference", dict(type=str, default=None, help="the native structure every model is scored against")),
+    ("--path_to_models", dict(type=str, nargs="+", default=None,
+                              help="model files and / or directories searched recursively for *.pdb, *.pdb1, *.ent, each optionally .gz")),
+    ("--pairs", dict(type=str, default=None, help="CSV of reference_path,model_path[,label] lines instead of the two options above")),
+    ("--cycles", dict(type=int, default=5, help="outlier-rejection refinement cycles at most (default 5, cmd.align's; 0: one fit over all)")),
+    ("--cutoff", dict(type=float, default=2.0, help="a refinement cycle drops positions further than this many RMS (default 2.0, cmd.align's)")),
+    ("--pair_by", dict(type=str, default="position", choices=list(superpose.PAIR_BY),
+                       help="position: CA atoms in file order, equal length required (default); number: by chain, residue number and "
+                            "insertion code.  Never by a sequence alignment")),
+    ("--device", dict(type=int, default=0, help="HIP device index")),
+    ("--workers", dict(type=int, default=8, help="host threads that read and parse the files (at most 16)")),
+    ("--path_to_output", dict(type=str, default="model_scores", help="directory for model_scores.csv and residue_deviation.csv")),
+)
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="RMSD, GDT and per-residue deviation of models superposed on their native, batched on the "
+                                                 "GPU (MI355X).  PARITY UNPINNED AGAINST PYMOL; pairing by position or number, not by alignment",
+                                     epilog=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    for flag, keywords in CLI_FLAGS:
+        parser.add_argument(flag, **keywords)
+    return parser
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

@@ -1,0 +1,358 @@
+// th_superpose: least-squares superposition of a BATCH of position-paired coordinate lists (the CA atoms of a model on those of its
+// native), with outlier-rejection refinement — RMSD, the counts behind a GDT and the per-position deviation.  The reference gets
+// these one pair at a time from PyMOL's cmd.align (scripts/analyse_af2.py calculate_RMSD_and_gdt).
+//
+//     *** PARITY UNPINNED AGAINST PYMOL ***  PyMOL is not available where this project is built.  The rule — written out in
+//     include/timed_hip.h — is this project's reading of the documented behaviour of cmd.align (cycles 5, cutoff 2.0) on atoms that
+//     are already paired; it is not PyMOL's code and no test can pin it against PyMOL.
+//
+// k_superpose: one wavefront per pair, four pairs per 256-thread workgroup, the whole batch and every refinement cycle in one launch.
+// Lane l owns positions l, l + 64, ... of its pair; the kept byte and the distance of a position are written to global memory by the
+// lane that owns it and read back by that lane only, so a cycle needs no barrier and no LDS.  The 3 + 3 + 9 float64 sums of a fit
+// and the sums of squared distances are reduced by an xor butterfly of shuffles: a + b is b + a, so every lane ends with the same
+// bits, and every lane then solves the 4 x 4 eigenproblem of Horn's matrix itself (cyclic Jacobi, at most kSweeps sweeps) — nothing
+// is broadcast.  A pair's arithmetic depends on its own coordinates and its lane layout alone: not on the grid, not on its
+// neighbours, and two calls give the same bytes.  No atomics.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+
+#include "common.h"
+
+// every float64 product and sum below is rounded separately, as the NumPy restatement's are
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kBlock = 256;                       // threads per workgroup
+constexpr int kPerBlock = kBlock / kWave;         // pairs per workgroup
+constexpr int kSweeps = 10;                       // Jacobi sweeps at most (a 4 x 4 matrix is diagonal to the last bit after 5 or 6)
+
+__device__ inline double wave_sum(double v) {
+    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+    return v;
+}
+
+__device__ inline int wave_sum(int v) {
+    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+    return v;
+}
+
+__device__ inline bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
+
+// one Jacobi rotation in the (P, Q) plane: A <- J^T A J, V <- V J
+template <int P, int Q>
+__device__ inline void rotate(double (&A)[4][4], double (&V)[4][4]) {
+    const double apq = A[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+    const double root = fabs(theta) + sqrt(theta * theta + 1.0);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / root;
+    const double c = 1.0 / sqrt(t * t + 1.0);
+    const double s = t * c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double akp = A[k][P], akq = A[k][Q];
+        A[k][P] = c * akp - s * akq;
+        A[k][Q] = s * akp + c * akq;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double apk = A[P][k], aqk = A[Q][k];
+        A[P][k] = c * apk - s * aqk;
+        A[Q][k] = s * apk + c * aqk;
+    }
+    A[P][Q] = 0.0;
+    A[Q][P] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double vkp = V[k][P], vkq = V[k][Q];
+        V[k][P] = c * vkp - s * vkq;
+        V[k][Q] = s * vkp + c * vkq;
+    }
+}
+
+// the proper rotation (row-major R[9]) that takes the centred mobile coordinates onto the centred reference ones, from the
+// cross-covariance S[x][y] = sum mob_x ref_y: the unit eigenvector of largest eigenvalue of Horn's matrix is its quaternion
+__device__ inline void horn_rotation(const double (&S)[3][3], double (&R)[9]) {
+    double A[4][4], V[4][4];
+    A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
+    A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
+    A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
+    A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
+    A[0][1] = A[1][0] = S[1][2] - S[2][1];
+    A[0][2] = A[2][0] = S[2][0] - S[0][2];
+    A[0][3] = A[3][0] = S[0][1] - S[1][0];
+    A[1][2] = A[2][1] = S[0][1] + S[1][0];
+    A[1][3] = A[3][1] = S[2][0] + S[0][2];
+    A[2][3] = A[3][2] = S[1][2] + S[2][1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < kSweeps; ++sweep) {
+        if (A[0][1] == 0.0 && A[0][2] == 0.0 && A[0][3] == 0.0 && A[1][2] == 0.0 && A[1][3] == 0.0 && A[2][3] == 0.0) break;
+        rotate<0, 1>(A, V);
+        rotate<0, 2>(A, V);
+        rotate<0, 3>(A, V);
+        rotate<1, 2>(A, V);
+        rotate<1, 3>(A, V);
+        rotate<2, 3>(A, V);
+    }
+    // the first of the largest diagonal entries
+    double best = A[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (A[k][k] > best) {
+            best = A[k][k];
+            w = V[0][k];
+            x = V[1][k];
+            y = V[2][k];
+            z = V[3][k];
+        }
+    const double len = sqrt(((w * w + x * x) + y * y) + z * z);
+    w = w / len;
+    x = x / len;
+    y = y / len;
+    z = z / len;
+    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+    R[0] = ((ww + xx) - yy) - zz;
+    R[1] = 2.0 * (x * y - w * z);
+    R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z);
+    R[4] = ((ww - xx) + yy) - zz;
+    R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y);
+    R[7] = 2.0 * (y * z + w * x);
+    R[8] = ((ww - xx) - yy) + zz;
+}
+
+__global__ void __launch_bounds__(kBlock) k_superpose(const double* __restrict__ ref_xyz, const double* __restrict__ mob_xyz,
+                                                      const long long* __restrict__ offsets, long long n_pairs, int cycles, double cutoff,
+                                                      double* dist_out, unsigned char* kept_out, double* __restrict__ rmsd_out,
+                                                      int* __restrict__ count_out, double* __restrict__ transform_out) {
+    const long long pair = (long long)blockIdx.x * kPerBlock + threadIdx.x / kWave;
+    if (pair >= n_pairs) return;                                       // the whole wavefront leaves: nothing below is a workgroup barrier
+    const int lane = threadIdx.x % kWave;
+    const long long lo = offsets[pair];
+    const long long n = offsets[pair + 1] - lo;
+    const double* ref = ref_xyz + 3 * lo;
+    const double* mob = mob_xyz + 3 * lo;
+    double* dist = dist_out + lo;
+    unsigned char* kept = kept_out + lo;
+    const double nan = __builtin_nan("");
+
+    // cycle 0 keeps every valid position
+    int n_valid = 0;
+    for (long long i = lane; i < n; i += kWave) {
+        const bool ok = finite3(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]) && finite3(mob[3 * i], mob[3 * i + 1], mob[3 * i + 2]);
+        kept[i] = ok ? 1 : 0;
+        dist[i] = nan;
+        n_valid += ok ? 1 : 0;
+    }
+    n_valid = wave_sum(n_valid);
+
+    int n_kept = n_valid, cycles_run = 0;
+    double fit_all = nan, rms_kept = nan, sq_all = 0.0;
+    double cm[3] = {0.0, 0.0, 0.0}, cr[3] = {0.0, 0.0, 0.0};
+    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    while (n_valid > 0) {
+        // centroids of the kept set
+        double sm[3] = {0.0, 0.0, 0.0}, sr[3] = {0.0, 0.0, 0.0};
+        for (long long i = lane; i < n; i += kWave)
+            if (kept[i]) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    sm[a] += mob[3 * i + a];
+                    sr[a] += ref[3 * i + a];
+                }
+            }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            cm[a] = wave_sum(sm[a]) / (double)n_kept;
+            cr[a] = wave_sum(sr[a]) / (double)n_kept;
+        }
+        // cross-covariance of the centred coordinates (two-pass)
+        double S[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+        for (long long i = lane; i < n; i += kWave)
+            if (kept[i]) {
+                double a[3], b[3];
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+                    a[x] = mob[3 * i + x] - cm[x];
+                    b[x] = ref[3 * i + x] - cr[x];
+                }
+#pragma unroll
+                for (int x = 0; x < 3; ++x)
+#pragma unroll
+                    for (int y = 0; y < 3; ++y) S[x][y] += a[x] * b[y];
+            }
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) S[x][y] = wave_sum(S[x][y]);
+        horn_rotation(S, R);
+        // distances of every valid position under this fit
+        double sq_kept = 0.0;
+        sq_all = 0.0;
+        for (long long i = lane; i < n; i += kWave) {
+            const double mx = mob[3 * i], my = mob[3 * i + 1], mz = mob[3 * i + 2];
+            const double rx = ref[3 * i], ry = ref[3 * i + 1], rz = ref[3 * i + 2];
+            if (!(finite3(mx, my, mz) && finite3(rx, ry, rz))) continue;
+            const double ax = mx - cm[0], ay = my - cm[1], az = mz - cm[2];
+            const double dx = (((R[0] * ax + R[1] * ay) + R[2] * az) + cr[0]) - rx;
+            const double dy = (((R[3] * ax + R[4] * ay) + R[5] * az) + cr[1]) - ry;
+            const double dz = (((R[6] * ax + R[7] * ay) + R[8] * az) + cr[2]) - rz;
+            const double d = sqrt((dx * dx + dy * dy) + dz * dz);
+            dist[i] = d;
+            sq_all += d * d;
+            if (kept[i]) sq_kept += d * d;
+        }
+        sq_all = wave_sum(sq_all);
+        rms_kept = sqrt(wave_sum(sq_kept) / (double)n_kept);
+        if (cycles_run == 0) fit_all = rms_kept;
+        if (cycles_run >= cycles || n_valid < 3) break;
+        // refinement: drop the kept positions beyond cutoff * rms, unless none is or fewer than 3 would remain
+        const double limit = cutoff * rms_kept;
+        int drop = 0;
+        for (long long i = lane; i < n; i += kWave)
+            if (kept[i] && dist[i] > limit) ++drop;
+        drop = wave_sum(drop);
+        if (drop == 0 || n_kept - drop < 3) break;
+        for (long long i = lane; i < n; i += kWave)
+            if (kept[i] && dist[i] > limit) kept[i] = 0;
+        n_kept -= drop;
+        ++cycles_run;
+    }
+
+    int within[4] = {0, 0, 0, 0};
+    for (long long i = lane; i < n; i += kWave) {
+        const double d = dist[i];                                      // NaN (an invalid position) is within nothing
+        within[0] += d <= 1.0 ? 1 : 0;
+        within[1] += d <= 2.0 ? 1 : 0;
+        within[2] += d <= 4.0 ? 1 : 0;
+        within[3] += d <= 8.0 ? 1 : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) within[k] = wave_sum(within[k]);
+    if (lane != 0) return;
+    rmsd_out[3 * pair] = rms_kept;
+    rmsd_out[3 * pair + 1] = n_valid > 0 ? sqrt(sq_all / (double)n_valid) : nan;
+    rmsd_out[3 * pair + 2] = fit_all;
+    int* count = count_out + 7 * pair;
+    count[0] = n_valid;
+    count[1] = n_kept;
+    count[2] = cycles_run;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) count[3 + k] = within[k];
+    if (transform_out) {                                               // moved = R mob + t, t = cr - R cm; the identity when nothing is valid
+        double* t = transform_out + 12 * pair;
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            t[4 * x] = R[3 * x];
+            t[4 * x + 1] = R[3 * x + 1];
+            t[4 * x + 2] = R[3 * x + 2];
+            t[4 * x + 3] = cr[x] - ((R[3 * x] * cm[0] + R[3 * x + 1] * cm[1]) + R[3 * x + 2] * cm[2]);
+        }
+    }
+}
+
+struct SpCall {
+    int device = -1;
+    hipStream_t st = nullptr;
+    unsigned char* mem = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~SpCall() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (mem) (void)hipFree(mem);
+    }
+};
+
+size_t sp_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" int th_superpose(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
+                            int cycles, double cutoff, double* dist_out, uint8_t* kept_out, double* rmsd_out, int32_t* count_out,
+                            double* transform_out, double* kernel_ms) {
+    if (total < 0 || n_pairs < 0) TH_FAIL(TH_EINVAL, "th_superpose: negative size (total = %lld, n_pairs = %lld)", (long long)total, (long long)n_pairs);
+    if (total > INT_MAX || n_pairs > INT_MAX)
+        TH_FAIL(TH_EINVAL, "th_superpose: %lld positions / %lld pairs in one call (limit 2^31 - 1 each)", (long long)total, (long long)n_pairs);
+    if (cycles < 0) TH_FAIL(TH_EINVAL, "th_superpose: cycles = %d is negative", cycles);
+    if (!std::isfinite(cutoff) || cutoff <= 0.0) TH_FAIL(TH_EINVAL, "th_superpose: cutoff = %g is not a positive finite number", cutoff);
+    if (n_pairs == 0) {
+        if (total != 0) TH_FAIL(TH_EINVAL, "th_superpose: n_pairs = 0 owns no position, total = %lld", (long long)total);
+        if (kernel_ms) *kernel_ms = 0.0;
+        return TH_OK;
+    }
+    if (!offsets || !rmsd_out || !count_out || (total > 0 && (!ref_xyz || !mob_xyz || !dist_out || !kept_out)))
+        TH_FAIL(TH_EINVAL, "th_superpose: n_pairs = %lld needs offsets, rmsd_out and count_out, total = %lld needs ref_xyz, mob_xyz, dist_out and kept_out",
+                (long long)n_pairs, (long long)total);
+    if (offsets[0] != 0 || offsets[n_pairs] != total)
+        TH_FAIL(TH_EINVAL, "th_superpose: offsets run from %lld to %lld, not from 0 to total = %lld", (long long)offsets[0], (long long)offsets[n_pairs],
+                (long long)total);
+    for (int64_t p = 0; p < n_pairs; ++p)
+        if (offsets[p + 1] < offsets[p]) TH_FAIL(TH_EINVAL, "th_superpose: offsets[%lld] > offsets[%lld]", (long long)p, (long long)p + 1);
+
+    SpCall call;
+    HIP_TRY(hipSetDevice(device));
+    call.device = device;
+    const size_t n = (size_t)total, np = (size_t)n_pairs;
+    const size_t off_mob = sp_align(n * 3 * sizeof(double));
+    const size_t off_offsets = off_mob + sp_align(n * 3 * sizeof(double));
+    const size_t off_dist = off_offsets + sp_align((np + 1) * sizeof(int64_t));
+    const size_t off_kept = off_dist + sp_align(n * sizeof(double));
+    const size_t off_rmsd = off_kept + sp_align(n);
+    const size_t off_count = off_rmsd + sp_align(np * 3 * sizeof(double));
+    const size_t off_tr = off_count + sp_align(np * 7 * sizeof(int32_t));
+    const size_t bytes = off_tr + sp_align(transform_out ? np * 12 * sizeof(double) : 0) + 256;      // never a zero-byte allocation
+    hipError_t e = th_malloc_retry(&call.mem, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        call.mem = nullptr;
+        th_set_error("th_superpose: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
+    if (kernel_ms)
+        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
+    double* d_ref = (double*)call.mem;
+    double* d_mob = (double*)(call.mem + off_mob);
+    long long* d_offsets = (long long*)(call.mem + off_offsets);
+    double* d_dist = (double*)(call.mem + off_dist);
+    unsigned char* d_kept = call.mem + off_kept;
+    double* d_rmsd = (double*)(call.mem + off_rmsd);
+    int* d_count = (int*)(call.mem + off_count);
+    double* d_tr = transform_out ? (double*)(call.mem + off_tr) : nullptr;
+    hipStream_t st = call.st;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(d_ref, ref_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_mob, mob_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    hipLaunchKernelGGL(k_superpose, dim3((unsigned)((np + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_ref, d_mob, d_offsets,
+                       (long long)n_pairs, cycles, cutoff, d_dist, d_kept, d_rmsd, d_count, d_tr);
+    HIP_TRY(hipGetLastError());
+    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(dist_out, d_dist, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(kept_out, d_kept, n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(rmsd_out, d_rmsd, np * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(count_out, d_count, np * 7 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (transform_out) HIP_TRY(hipMemcpyAsync(transform_out, d_tr, np * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
+        *kernel_ms = ms;
+    }
+    return TH_OK;
+}

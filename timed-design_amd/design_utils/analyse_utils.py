@@ -161,6 +161,20 @@ def extract_bfactor_from_ampal(pdb_path, load_pdb: bool = True) -> t.List[t.List
     return structure.residue_bfactors(model)
 
 
+def calculate_RMSD_and_gdt(pdb_original_path, pdb_predicted_path, device: int = 0) -> t.Tuple[float, float]:
+    """reference scripts/analyse_af2.py:12-45: ``(rmsd, mean_gdt)`` of a predicted structure on its original — there PyMOL's
+    ``cmd.align`` on the CA atoms and the mean of the fractions of aligned pairs within 1, 2, 4 and 8 Angstrom.  Here
+    ``(rmsd_kept, mean_gdt)`` of ``timed_hip.superpose.superpose`` with the CA atoms paired by position, ``cycles=5``,
+    ``cutoff=2.0``: PARITY UNPINNED AGAINST PYMOL, the rule is this project's reading of cmd.align's documented behaviour
+    (include/timed_hip.h, th_superpose) and no sequence alignment is made.  Structures of different length raise ValueError, where
+    the reference's callers assert equal length beforehand.  For many pairs call ``superpose`` itself: it batches them."""
+    from timed_hip import superpose
+    (res,) = superpose.superpose([(pdb_original_path, pdb_predicted_path)], device=device)
+    if res.error:
+        raise ValueError(f"{pdb_original_path} / {pdb_predicted_path}: {res.error}")
+    return res.rmsd_kept, res.mean_gdt
+
+
 # ---- per-class rotamer metrics (analyse_rotamers.py; computed on the GPU by timed_hip.analysis) -------------------------------
 def _narrow(matrix: np.ndarray) -> np.ndarray:
     """float16 / float32 matrices as they are; others to float16 when that is exact (the probability CSVs predict.py writes),
