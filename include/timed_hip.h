@@ -473,6 +473,54 @@ int th_superpose(int device, const double* ref_xyz, const double* mob_xyz, int64
                  int cycles, double cutoff, double* dist_out, uint8_t* kept_out, double* rmsd_out, int32_t* count_out,
                  double* transform_out, double* kernel_ms);
 
+/* ---- *** PARITY UNPINNED AGAINST OPENSTRUCTURE *** lDDT of models against their native: analyse_models.py --lddt — the local
+ * Distance Difference Test (Mariani et al. 2013), the measured counterpart of the pLDDT that AlphaFold2 writes into the B-factor
+ * column of its models (the reference plots that prediction in plot_af2IDDT_vs_position).  Here for a BATCH of position-paired
+ * coordinate lists in one launch.
+ *
+ *     *** PARITY UNPINNED AGAINST OPENSTRUCTURE ***  Neither OpenStructure nor AlphaFold's lddt.py is available where this project
+ *     is built.  The rule below is this project's reading of the PUBLISHED definition (Mariani et al. 2013) in the CA-only form
+ *     AlphaFold uses: one position per residue, no stereochemistry checks, strict inequalities on both tests; it is neither
+ *     implementation's code, it aligns no sequences, and no test can pin it against OpenStructure itself.
+ *
+ * All arrays are host memory.
+ *   ref_xyz, mob_xyz   double[total][3]: the reference (native) and the model coordinates of all pairs, pair after pair; position i
+ *                      of one list is paired with position i of the other (any value, NaN and infinities included);
+ *   total              number of positions, 0 <= total <= 2^31 - 1;
+ *   offsets            int64[n_pairs + 1]: pair p owns positions offsets[p] .. offsets[p + 1] of both lists; offsets[0] = 0,
+ *                      non-decreasing, offsets[n_pairs] = total.  A pair may be empty;
+ *   n_pairs            0 <= n_pairs <= 2^31 - 1;
+ *   radius             inclusion radius, finite and > 0 (the published default: 15.0);
+ *   thresholds         double[4], each finite and > 0 (the published default: 0.5, 1, 2, 4);
+ *   residue_out        int32[total][5]: n_i, c_i[0..3]; five zeros at an invalid position;
+ *   pair_out           int64[n_pairs][6]: n_valid, N, C[0..3];
+ *   kernel_ms          NULL, or receives the device time of the two kernels (events around them), in milliseconds.
+ * The rule, for one pair of equally long lists ref[i], mob[i], all arithmetic float64 and no fused multiply-add:
+ *   - a position is VALID when all six of its coordinates are finite.  An invalid position is never an i and never a j: an infinity
+ *     in one list does not leak through the other list's distance (the kernel makes both lists NaN at such a position);
+ *   - DISTANCE  d(a, b) = sqrt((dx*dx + dy*dy) + dz*dz), in that order, each product and sum rounded on its own, the square root
+ *     correctly rounded;
+ *   - an ordered pair (i, j) is INCLUDED when j != i, both positions are valid and d_ref(i, j) < radius.  Strict.  Two different
+ *     positions with identical coordinates are a pair like any other.  (The kernel compares the squared distance with
+ *     th_packing_threshold(radius), which decides the same for every double, and takes square roots of included pairs only.)
+ *   - an included pair is PRESERVED at threshold t when |d_ref(i, j) - d_mob(i, j)| < t.  Strict;
+ *   - per position: n_i is the number of included j, c_i[k] the number of those preserved at thresholds[k];
+ *   - per pair: n_valid, N = sum n_i and C[k] = sum c_i[k], over ORDERED pairs (every unordered pair counts twice), 64-bit;
+ *   - the caller forms the fractions, as it does for GDT: lddt_i = sum_k c_i[k] / (4 n_i), NaN when n_i = 0, and
+ *     lddt = sum_k C[k] / (4 N), NaN when N = 0.  The global score is PAIR-weighted, as in both published implementations; it is
+ *     not the mean of lddt_i.
+ * MIRROR IMAGES: every distance of a mirror image is that of the original, so lDDT does not see one — the mirror case of the
+ * superposition fixture scores 1.0 here where th_superpose reports 10.7 Angstrom.  Conversely one re-oriented domain costs
+ * th_superpose everything and lDDT only the pairs across the hinge.  That is the reason to report both.
+ * All outputs are integers decided by float64 comparisons: a pair's outputs depend on its own coordinates alone — not on its place
+ * in the batch or on its neighbours — and two calls give the same bytes.  No atomics.  Device memory: 68 bytes per position + 8 per
+ * 256 positions of every pair + 56 per pair; the O(L^2) distances exist in registers only.  TH_EINVAL, before anything is launched
+ * or written: a negative or too large size, a NULL that is required (offsets, thresholds, pair_out; with total > 0 also both lists
+ * and residue_out), offsets that decrease, do not start at 0 or do not end at total, a radius or a threshold that is not finite
+ * or not > 0.  n_pairs = 0 (with total = 0) is success without a launch. */
+int th_lddt(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
+            double radius, const double* thresholds, int32_t* residue_out, int64_t* pair_out, double* kernel_ms);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

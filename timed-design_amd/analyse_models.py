@@ -21,6 +21,20 @@ with a proper rotation, then up to --cycles rounds that drop positions further t
 position (file order; native and model must be equally long, as the reference asserts) or by number (chain, residue number and
 insertion code), NOT by a sequence alignment.  Out of scope: AlphaFold2 folder layouts and parsing FASTA or file names into model /
 temperature / sample columns — the label is the model's path below --path_to_models, or the third CSV field.
+
+--lddt additionally writes ``model_lddt.csv``, one row per pair — label, reference, model, n_valid, n_included (ordered pairs of
+positions closer than --lddt_radius in the reference), lddt, the fractions of those pairs preserved within 0.5, 1, 2 and 4 Angstrom,
+mean_model_bfactor (over the paired positions that have one), error — and ``residue_lddt.csv`` — label, chain, number and residue name
+(of the reference), n_included, lddt and model_bfactor of every position.  The score is superposition-free: it compares distances
+within each structure and never fits one on the other, so a re-oriented domain costs only the pairs across its hinge — and a mirror
+image, which the fit above rejects with a large RMSD, scores 1.0.  That is the reason to report both.  model_bfactor is the model's
+B-factor of the paired atom as stored; AlphaFold2 writes its own PREDICTION of this score there (pLDDT, 0-100), lddt is the
+measured one (0-1).  Both scores come from one parse of every file that can be read.
+
+PARITY UNPINNED AGAINST OPENSTRUCTURE: neither OpenStructure nor AlphaFold's lddt.py is available to pin this against.  The rule is
+this project's reading of the published definition (Mariani et al. 2013) in the CA-only form AlphaFold uses, written out in
+include/timed_hip.h and timed_hip/lddt.py: one position per residue, no stereochemistry checks, strict inequalities on both tests, the
+global score weighted by pairs (not the mean of the per-residue scores).
 """
 import argparse
 import csv
@@ -28,11 +42,15 @@ import sys
 from pathlib import Path
 
 from analyse_properties import find_structures
+from timed_hip import lddt as lddt_module
 from timed_hip import superpose
 
 SCORE_COLUMNS = ["label", "reference", "model", "n_valid", "n_kept", "cycles_run", "rmsd_kept", "rmsd_all", "rmsd_fit_all", "gdt_1", "gdt_2",
                  "gdt_4", "gdt_8", "mean_gdt", "sequence_identity", "unpaired_reference", "unpaired_model", "error"]
 RESIDUE_COLUMNS = ["label", "chain", "residue_number", "distance", "kept"]
+LDDT_COLUMNS = ["label", "reference", "model", "n_valid", "n_included", "lddt", "preserved_0.5", "preserved_1", "preserved_2", "preserved_4",
+                "mean_model_bfactor", "error"]
+RESIDUE_LDDT_COLUMNS = ["label", "chain", "number", "residue", "n_included", "lddt", "model_bfactor"]
 
 
 def read_pairs(path):
@@ -55,6 +73,20 @@ def _fmt(v: float) -> str:
     return repr(float(v))
 
 
+def write_lddt(out, todo, scores):
+    """model_lddt.csv and residue_lddt.csv"""
+    with open(out / "model_lddt.csv", "w", newline="") as fs, open(out / "residue_lddt.csv", "w", newline="") as fr:
+        ws, wr = csv.writer(fs), csv.writer(fr)
+        ws.writerow(LDDT_COLUMNS)
+        wr.writerow(RESIDUE_LDDT_COLUMNS)
+        for (label, ref, model), res in zip(todo, scores):
+            known = res.model_bfactor[res.model_bfactor == res.model_bfactor]
+            ws.writerow([label, str(ref), str(model), res.n_valid, res.n_included, _fmt(res.lddt)] + [_fmt(p) for p in res.preserved]
+                        + [_fmt(known.mean() if len(known) else float("nan")), res.error or ""])
+            for r, n, score, b in zip(res.residues, res.n_i.tolist(), res.lddt_i, res.model_bfactor):
+                wr.writerow([label, r.chain, r.number, r.name, n, _fmt(score), _fmt(b)])
+
+
 def main(args):
     if args.pairs:
         if args.path_to_reference or args.path_to_models:
@@ -70,10 +102,22 @@ def main(args):
     if not todo:
         sys.exit("no pair to score: no *.pdb / *.pdb1 / *.ent (.gz) file under --path_to_models, or an empty --pairs file")
     stats = {}
-    results = superpose.superpose([(ref, model) for _, ref, model in todo], pair_by=args.pair_by, cycles=args.cycles, cutoff=args.cutoff,
+    sides = [(ref, model) for _, ref, model in todo]
+    if args.lddt:                                                          # both scores from one parse of every file
+        if not (args.lddt_radius > 0 and args.lddt_radius < float("inf")):
+            sys.exit(f"--lddt_radius {args.lddt_radius} is not a positive finite number")
+        paths = list(dict.fromkeys(side for pair in sides for side in pair))
+        parsed = dict(zip(paths, superpose._load_layouts(paths, "CA", args.workers)))
+        # a file that could not be read stays a path: each score reports the error itself
+        sides = [tuple(side if isinstance(parsed[side], str) else parsed[side] for side in pair) for pair in sides]
+    results = superpose.superpose(sides, pair_by=args.pair_by, cycles=args.cycles, cutoff=args.cutoff,
                                   device=args.device, workers=args.workers, stats=stats)
     out = Path(args.path_to_output)
     out.mkdir(parents=True, exist_ok=True)
+    if args.lddt:
+        write_lddt(out, todo, lddt_module.lddt(sides, pair_by=args.pair_by, radius=args.lddt_radius, device=args.device, workers=args.workers,
+                                               stats=stats))
+        stats["files_parsed"] = len(paths)
     with open(out / "model_scores.csv", "w", newline="") as fs, open(out / "residue_deviation.csv", "w", newline="") as fr:
         ws, wr = csv.writer(fs), csv.writer(fr)
         ws.writerow(SCORE_COLUMNS)
@@ -104,6 +148,10 @@ CLI_FLAGS = (
     ("--device", dict(type=int, default=0, help="HIP device index")),
     ("--workers", dict(type=int, default=8, help="host threads that read and parse the files (at most 16)")),
     ("--path_to_output", dict(type=str, default="model_scores", help="directory for model_scores.csv and residue_deviation.csv")),
+    ("--lddt", dict(action="store_true",
+                    help="also write model_lddt.csv and residue_lddt.csv: the lDDT of every model and residue (CA atoms, thresholds 0.5, 1, 2, 4), "
+                         "a superposition-free score, beside the model's B-factor (AlphaFold2's pLDDT).  PARITY UNPINNED AGAINST OPENSTRUCTURE")),
+    ("--lddt_radius", dict(type=float, default=15.0, help="inclusion radius of --lddt in the reference structure (default 15.0)")),
 )
 
 
