@@ -112,6 +112,10 @@ int th_predict_wait(th_model* m, int ticket);
  *         uint32   bitmap[n_frames][W]     bit k of word w set <=> element 32 w + k is stored (every element whose bit pattern is
  *                                          not +0.0: -0.0, NaN payloads and denormals are stored)
  *         float    values[n_values]        the stored elements, frame by frame, in element order
+ * The whole blob is checked on the host before anything is queued: W <= 4096 (131 072 elements per frame), n_values within
+ * blob_bytes, and for every frame popcount(bitmap[i]) == rank[i + 1] - rank[i] with no bit set at or beyond element E (the tail
+ * of the last real word, the padding words).  A blob that fails returns TH_EINVAL (the message names the frame), takes no
+ * ticket and writes nothing to probs_out.
  * Same ticket / wait / ownership rules as th_predict_async (TH_PREDICT_LOGITS and TH_PREDICT_OUT_DEVICE apply). */
 #define TH_SPARSE_MAGIC "THSPF001"
 int th_predict_sparse_async(th_model* m, const void* blob, size_t blob_bytes, float* probs_out, unsigned flags, int* ticket);

@@ -88,6 +88,92 @@ def test_pack_files_sparsify_slices_and_a_pack_without_dense_frames(tmp_path):
         framepack.sparsify(stem)
 
 
+def _hand_pack(stem, x):
+    """a float32 pack written by hand (26 rows of (7, 7, 7, 5), like tests/golden/frames_tiny*.hdf5) with its sparse files"""
+    n = len(x)
+    np.save(stem + ".frames.npy", x)
+    np.save(stem + ".labels.npy", np.eye(20, dtype=np.uint8)[np.arange(n) % 20])
+    np.savetxt(stem + ".map.txt", np.array([["1abc", "A", str(i), "ALA"] for i in range(n)]), delimiter=",", fmt="%s")
+    json.dump(dict(frame_dims=list(x.shape[1:]), voxels_as_gaussian=True, n_frames=n, source="x", make_frame_dataset_ver=""), open(stem + ".meta.json", "w"))
+    framepack.sparsify(stem)
+    fp = framepack.FramePack(stem)
+    assert fp.sparse is not None and fp.sparse_batch(0, n).dense().tobytes() == x.tobytes()
+
+
+@pytest.mark.parametrize("src", ["frames_tiny.hdf5", "frames_tiny_bool.hdf5"])
+def test_a_repack_onto_a_sparsified_stem_leaves_no_stale_sparse_files(tmp_path, src):
+    """pack_dataset(sparse=False) of other float32 frames, or of a uint8 dataset, onto a stem that has sparse files: the old
+    .sparse.* files (same frame count, same frame shape) are not served"""
+    import warnings
+    stem = str(tmp_path / "p")
+    _hand_pack(stem, _gaussianish(26, (7, 7, 7, 5), 21, fill=0.3))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        fresh = framepack.pack_dataset(os.path.join(G, src), tmp_path / "fresh")
+        y = np.array(fresh.frames)
+        framepack.pack_dataset(os.path.join(G, src), stem, sparse=False)
+    fp = framepack.FramePack(stem)
+    assert fp.sparse is None and not any(os.path.exists(stem + s) for s in framepack.SPARSE_SUFFIXES)
+    X, _ = fp.load_batch(fp.flat_map)
+    assert y.shape == (26, 7, 7, 7, 5) and X.dtype == y.dtype and np.asarray(X).tobytes() == y.tobytes()
+
+
+def test_uint8_frames_beside_sparse_files_do_not_load_them(tmp_path):
+    """sparse files describe float32 frames: next to a uint8 .frames.npy (written by anything) they are left alone"""
+    stem = str(tmp_path / "p")
+    x = _gaussianish(26, (7, 7, 7, 5), 22)
+    _hand_pack(stem, x)
+    y = (x != 0).astype(np.uint8)[::-1].copy()
+    np.save(stem + ".frames.npy", y)
+    fp = framepack.FramePack(stem)
+    assert fp.sparse is None
+    X, _ = fp.load_batch(fp.flat_map)
+    assert X.dtype == np.uint8 and np.asarray(X).tobytes() == y.tobytes()
+
+
+def test_an_interrupted_sparsify_leaves_no_sparse_triple(tmp_path, monkeypatch):
+    """new frames, then sparsify dies in its second pass (the second np.packbits call): new bitmaps and values beside the OLD rank
+    table must not load"""
+    stem = str(tmp_path / "p")
+    _hand_pack(stem, _gaussianish(26, (7, 7, 7, 5), 23, fill=0.08))
+    y = _gaussianish(26, (7, 7, 7, 5), 24, fill=0.4)
+    np.save(stem + ".frames.npy", y)
+    real, calls = np.packbits, []
+
+    def dying(*a, **k):
+        calls.append(1)
+        if len(calls) == 2:
+            raise KeyboardInterrupt
+        return real(*a, **k)
+    monkeypatch.setattr(np, "packbits", dying)
+    with pytest.raises(KeyboardInterrupt):
+        framepack.sparsify(stem, rows_per_pass=8)
+    monkeypatch.undo()
+    assert len(calls) == 2
+    assert not all(os.path.exists(stem + s) for s in framepack.SPARSE_SUFFIXES)
+    fp = framepack.FramePack(stem)
+    assert fp.sparse is None and np.asarray(fp.load_batch(fp.flat_map)[0]).tobytes() == y.tobytes()
+    framepack.sparsify(stem)                                   # and a complete run afterwards gives the new frames
+    fp = framepack.FramePack(stem)
+    assert fp.sparse is not None and fp.sparse_batch(0, 26).dense().tobytes() == y.tobytes()
+
+
+@pytest.mark.parametrize("where", [0, 13, 25])
+def test_frames_replaced_under_their_sparse_files_are_refused(tmp_path, where):
+    """.frames.npy replaced by hand, same shape, other data in the first, the middle or the last frame: FramePack refuses the pack
+    instead of handing predict.py the old frames"""
+    stem = str(tmp_path / "p")
+    x = _gaussianish(26, (7, 7, 7, 5), 25)
+    _hand_pack(stem, x)
+    y = x.copy()
+    y[where] = _gaussianish(1, (7, 7, 7, 5), 26)[0]
+    np.save(stem + ".frames.npy", y)
+    with pytest.raises(ValueError, match="inconsistent sparse transport files"):
+        framepack.FramePack(stem)
+    framepack.sparsify(stem)
+    assert framepack.FramePack(stem).sparse_batch(0, 26).dense().tobytes() == y.tobytes()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin", [6, 5])
 def test_frames_that_travel_sparse_give_the_same_bits(gpu, cin):

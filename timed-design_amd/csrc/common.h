@@ -275,6 +275,7 @@ void conv_wfs_pack_weights(const ConvWfsPlan& p, const float* w_keras, float* ds
 int launch_conv_wfs(hipStream_t s, int64_t n, const ConvWfsPlan& p, TView in, TView out, const float* wpk, const float* bias, PostOps post);
 
 // ---- sparse float32 frames expanded on the device (sparse_frames.hip) ----
+constexpr int kSpMaxWords = 4096;             // words of bitmap per frame held in LDS (131 072 elements; an aposteriori frame has 1 737)
 int launch_sparse_expand(hipStream_t s, int64_t n, const uint32_t* bits, const uint64_t* vidx, const float* values, float* out, int E, int W);
 
 // ---- first-layer convolution (conv_first.hip): Cin <= 8, Cout <= 32, 3x3x3, reads the caller's frames ----

@@ -2131,6 +2131,48 @@ static int predict_async_locked(th_model* m, const void* frames, int dtype, int6
     return TH_OK;
 }
 
+// ---- a sparse batch is checked completely on the host before any of it is queued: k_sparse_expand trusts its bitmaps ----
+// stored elements of one frame: the set bits of its W bitmap words (W is a multiple of 4 and a frame's words are 16-byte aligned
+// in the blob, so they are read as W / 2 64-bit words).  The library is built for baseline x86-64, whose popcount is a dozen
+// shift-and-mask operations per word: the POPCNT instruction comes in through a function-level target and a check of the CPU.
+static uint64_t popcount_words_portable(const uint64_t* p, size_t n) {
+    uint64_t c = 0;
+    for (size_t i = 0; i < n; ++i) c += (uint64_t)__builtin_popcountll(p[i]);
+    return c;
+}
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+__attribute__((target("popcnt"))) static uint64_t popcount_words_hw(const uint64_t* p, size_t n) {
+    uint64_t c0 = 0, c1 = 0;
+    size_t i = 0;
+    for (; i + 2 <= n; i += 2) { c0 += (uint64_t)__builtin_popcountll(p[i]); c1 += (uint64_t)__builtin_popcountll(p[i + 1]); }
+    if (i < n) c0 += (uint64_t)__builtin_popcountll(p[i]);
+    return c0 + c1;
+}
+static uint64_t popcount_words(const uint64_t* p, size_t n) {
+    static const bool hw = __builtin_cpu_supports("popcnt");
+    return hw ? popcount_words_hw(p, n) : popcount_words_portable(p, n);
+}
+#else
+static uint64_t popcount_words(const uint64_t* p, size_t n) { return popcount_words_portable(p, n); }
+#endif
+
+// every frame's bitmap against its rank delta, and no bit at or beyond element E (the tail of the last real word, the padding
+// words): a bitmap with more bits than the frame has values makes the kernel read past the values that travelled with the piece
+static int check_sparse_bitmaps(const SparseBatch& sp, uint32_t n) {
+    const uint32_t E = (uint32_t)sp.E, W = (uint32_t)sp.W, full = E / 32, tail = E % 32;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t* const b = sp.bits + (size_t)i * W;
+        const uint64_t stored = popcount_words((const uint64_t*)b, W / 2), want = sp.vidx[i + 1] - sp.vidx[i];
+        uint32_t beyond = tail ? b[full] >> tail : 0;
+        for (uint32_t w = full + (tail ? 1 : 0); w < W; ++w) beyond |= b[w];
+        if (beyond) TH_FAIL(TH_EINVAL, "sparse batch: frame %u has bits set beyond its %u elements", i, E);
+        if (stored != want)
+            TH_FAIL(TH_EINVAL, "sparse batch: frame %u has %llu bits set, its ranks say %llu stored elements", i, (unsigned long long)stored,
+                    (unsigned long long)want);
+    }
+    return TH_OK;
+}
+
 int th_predict_sparse_async(th_model* m, const void* blob, size_t blob_bytes, float* probs_out, unsigned flags, int* ticket) {
     if (!m || !ticket || !blob) TH_FAIL(TH_EINVAL, "null argument");
     if (flags & TH_PREDICT_IN_DEVICE) TH_FAIL(TH_EINVAL, "a sparse batch is host memory");
@@ -2144,8 +2186,13 @@ int th_predict_sparse_async(th_model* m, const void* blob, size_t blob_bytes, fl
     if (esz != 4 || (int64_t)E != (int64_t)in.D * in.H * in.W * in.C)
         TH_FAIL(TH_EINVAL, "sparse batch: %u elements of %u bytes per frame, the model reads %d float32", E, esz, in.D * in.H * in.W * in.C);
     if (W < (E + 31) / 32 || W % 4) TH_FAIL(TH_EINVAL, "sparse batch: %u bitmap words per frame for %u elements", W, E);
+    if (W > (uint32_t)kSpMaxWords)
+        TH_FAIL(TH_EINVAL, "sparse batch: %u bitmap words per frame, frames travel sparse with at most %d words (%d elements)", W, kSpMaxWords,
+                kSpMaxWords * 32);
+    // (n32 < 2^32 and W <= 4096: the offsets cannot wrap; the value count is bounded by a division, not by a sum that can)
     const size_t o_vidx = 32, o_bits = (o_vidx + ((size_t)n32 + 1) * 8 + 15) / 16 * 16, o_val = o_bits + (size_t)n32 * W * 4;
-    if (blob_bytes < o_val + nval * 4) TH_FAIL(TH_EINVAL, "sparse batch: %zu bytes, its header describes %zu", blob_bytes, o_val + (size_t)nval * 4);
+    if (blob_bytes < o_val || nval > (blob_bytes - o_val) / 4)
+        TH_FAIL(TH_EINVAL, "sparse batch: %zu bytes, its header describes %u frames and %llu values", blob_bytes, n32, (unsigned long long)nval);
     SparseBatch sp;
     sp.vidx = (const uint64_t*)(b + o_vidx); sp.bits = (const uint32_t*)(b + o_bits); sp.values = (const float*)(b + o_val);
     sp.E = (int)E; sp.W = (int)W;
@@ -2153,6 +2200,7 @@ int th_predict_sparse_async(th_model* m, const void* blob, size_t blob_bytes, fl
                                                                    (unsigned long long)(sp.vidx[n32] - sp.vidx[0]), (unsigned long long)nval);
     for (uint32_t i = 0; i < n32; ++i)
         if (sp.vidx[i + 1] < sp.vidx[i] || sp.vidx[i + 1] - sp.vidx[i] > E) TH_FAIL(TH_EINVAL, "sparse batch: frame %u has an impossible stored-element count", i);
+    if (int rc = check_sparse_bitmaps(sp, n32)) return rc;
     if (n32 > 0 && !probs_out) TH_FAIL(TH_EINVAL, "null argument");
     std::lock_guard<std::mutex> lock(m->mu);
     int rc = predict_async_locked(m, blob, TH_F32, n32, probs_out, flags, ticket, &sp);

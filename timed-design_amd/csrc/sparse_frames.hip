@@ -12,7 +12,6 @@
 namespace {
 
 constexpr int kSpThreads = 256;
-constexpr int kSpMaxWords = 4096;             // words of bitmap per frame held in LDS (131 072 elements; an aposteriori frame has 1 737)
 
 __global__ void __launch_bounds__(kSpThreads) k_sparse_expand(const uint32_t* __restrict__ bits, const uint64_t* __restrict__ vidx,
                                                               const float* __restrict__ values, float* __restrict__ out, int E,

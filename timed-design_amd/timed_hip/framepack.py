@@ -23,6 +23,9 @@ rate (222 KB per frame).  ``sparsify(stem)`` / ``pack_dataset(..., sparse=True)`
 the bitmap and the values cross PCIe — ~25 KB per frame — and the dense frame is rebuilt on the device in front of the first
 layer); ``predict.py`` does so by itself when the files are there (``TIMED_SPARSE=0`` keeps the dense rows).  ``.frames.npy`` may
 be deleted from a pack that has the sparse files (``batch`` then expands on the host).
+The sparse files belong to the frames they were made from: ``pack_dataset`` removes those of an older pack on the stem,
+``sparsify`` completes the triple with the rank file last, and ``FramePack`` takes them only beside float32 frames (or none) whose
+first, middle and last frame they expand to, byte for byte — anything else is ``ValueError("... inconsistent sparse transport files")``.
 
 ``pack_dataset`` converts an aposteriori HDF5 file once (host side, any HDF5 reader); afterwards
 ``FramePack.batch(lo, hi)`` is a zero-copy memory-mapped slice that goes straight to ``th_predict``.
@@ -69,11 +72,15 @@ def pack_stem(path) -> Optional[str]:
 
 def sparsify(stem, rows_per_pass: int = 2048) -> Tuple[int, int]:
     """Write the sparse transport files of a float32 pack next to its dense frames (or replace older ones).  Returns
-    (dense bytes, sparse bytes).  Vectorised NumPy, one pass over the memory-mapped frames."""
+    (dense bytes, sparse bytes).  Vectorised NumPy, one pass over the memory-mapped frames.  The rank file makes the triple
+    complete: an older one goes first and the new one appears last, under its final name in one step, so a run that is
+    interrupted leaves no triple that loads."""
     stem = pack_stem(stem) or os.fspath(stem)
     frames = np.load(stem + ".frames.npy", mmap_mode="r")
     if frames.dtype != np.float32:
         raise ValueError(f"{stem}: sparse transport is for float32 (Gaussian) packs, this one holds {frames.dtype}")
+    if os.path.exists(stem + ".sparse.rank.npy"):
+        os.remove(stem + ".sparse.rank.npy")
     n = frames.shape[0]
     E = int(np.prod(frames.shape[1:]))
     W = ((E + 31) // 32 + 3) // 4 * 4
@@ -93,7 +100,9 @@ def sparsify(stem, rows_per_pass: int = 2048) -> Tuple[int, int]:
         values[int(rank[lo]):int(rank[lo + len(x)])] = x[mask]
     bits.flush(); values.flush()
     del bits, values
-    np.save(stem + ".sparse.rank.npy", rank)
+    with open(stem + ".sparse.rank.npy.tmp", "wb") as f:
+        np.save(f, rank)
+    os.replace(stem + ".sparse.rank.npy.tmp", stem + ".sparse.rank.npy")
     return n * E * 4, n * W * 4 + (n + 1) * 8 + int(rank[-1]) * 4
 
 
@@ -103,6 +112,9 @@ def pack_dataset(hdf5_path, out_stem, filter_list: Sequence[str] = (), remove_bl
     sparse transport files of a Gaussian (float32) dataset."""
     from design_utils import utils  # local import: design_utils imports timed_hip lazily too
     out_stem = os.fspath(out_stem)
+    for s in SPARSE_SUFFIXES:                        # an older pack's sparse files describe other frames
+        if os.path.exists(out_stem + s):
+            os.remove(out_stem + s)
     flat_map, _ = utils.create_flat_dataset_map(hdf5_path, list(filter_list), remove_blacklist_silently)
     n = len(flat_map)
     with utils.open_frame_dataset(hdf5_path) as ds:
@@ -157,8 +169,8 @@ class FramePack:
         self.frames = np.load(stem + ".frames.npy", mmap_mode="r") if os.path.exists(stem + ".frames.npy") else None
         self.labels = np.load(stem + ".labels.npy")
         self.flat_map = _read_map(stem + ".map.txt")
-        self.sparse = None          # (bits [N, W], rank [N + 1], values): the sparse transport files, when present
-        if all(os.path.exists(stem + s) for s in SPARSE_SUFFIXES):
+        self.sparse = None          # (bits [N, W], rank [N + 1], values): the sparse transport files of float32 frames, when present
+        if all(os.path.exists(stem + s) for s in SPARSE_SUFFIXES) and (self.frames is None or self.frames.dtype == np.float32):
             bits = np.load(stem + ".sparse.bits.npy", mmap_mode="r")
             rank = np.load(stem + ".sparse.rank.npy")
             values = np.load(stem + ".sparse.values.npy", mmap_mode="r")
@@ -167,6 +179,8 @@ class FramePack:
                     or int(rank[-1]) > len(values) or bits.dtype != np.uint32 or values.dtype != np.float32):
                 raise ValueError(f"{stem}: inconsistent sparse transport files")
             self.sparse = (bits, rank.astype(np.uint64), values)
+            if self.frames is not None and not self._sparse_matches_frames():
+                raise ValueError(f"{stem}: inconsistent sparse transport files (they do not expand to the frames of .frames.npy)")
         n_frames = self.frames.shape[0] if self.frames is not None else self.sparse[0].shape[0]
         if len(self.flat_map) != n_frames or self.labels.shape[0] != n_frames:
             raise ValueError(f"{stem}: inconsistent pack (map {len(self.flat_map)}, frames {n_frames})")
@@ -185,6 +199,21 @@ class FramePack:
         if self.frames is None:
             return self.sparse_batch(lo, hi).dense(), self.labels[lo:hi].astype(float)
         return self.frames[lo:hi], self.labels[lo:hi].astype(float)
+
+    def _sparse_matches_frames(self) -> bool:
+        """the first, the middle and the last frame expanded on the host, against the dense file byte for byte: sparse files
+        left over from other frames of the same shape (a replaced .frames.npy) do not pass"""
+        n = self.sparse[0].shape[0]
+        if self.frames.shape[0] != n or tuple(self.frames.shape[1:]) != self.frame_dims:
+            return False
+        for i in sorted({0, n // 2, n - 1} if n else ()):
+            try:
+                got = self.sparse_batch(i, i + 1).dense()
+            except (ValueError, IndexError):         # bitmap and rank disagree
+                return False
+            if got.tobytes() != np.asarray(self.frames[i]).tobytes():
+                return False
+        return True
 
     def sparse_batch(self, lo: int, hi: int):
         """Rows [lo, hi) in the sparse transport form (engine.SparseFrames): views of the memory-mapped files, nothing is copied"""
