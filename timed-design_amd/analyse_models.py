@@ -41,9 +41,10 @@ import csv
 import sys
 from pathlib import Path
 
-from analyse_properties import find_structures
 from timed_hip import lddt as lddt_module
 from timed_hip import superpose
+from timed_hip.pdbio import find_structures
+from timed_hip.textio import float_repr as _fmt
 
 SCORE_COLUMNS = ["label", "reference", "model", "n_valid", "n_kept", "cycles_run", "rmsd_kept", "rmsd_all", "rmsd_fit_all", "gdt_1", "gdt_2",
                  "gdt_4", "gdt_8", "mean_gdt", "sequence_identity", "unpaired_reference", "unpaired_model", "error"]
@@ -67,10 +68,6 @@ def read_pairs(path):
             ref, model = (p if p.is_absolute() else path.parent / p for p in (Path(row[0]), Path(row[1])))
             out.append((row[2] if len(row) > 2 and row[2] else row[1], ref, model))
     return out
-
-
-def _fmt(v: float) -> str:
-    return repr(float(v))
 
 
 def write_lddt(out, todo, scores):
@@ -101,23 +98,15 @@ def main(args):
         todo = [(label, reference, path) for label, path in find_structures(args.path_to_models)]
     if not todo:
         sys.exit("no pair to score: no *.pdb / *.pdb1 / *.ent (.gz) file under --path_to_models, or an empty --pairs file")
+    if args.lddt and not (args.lddt_radius > 0 and args.lddt_radius < float("inf")):
+        sys.exit(f"--lddt_radius {args.lddt_radius} is not a positive finite number")
     stats = {}
-    sides = [(ref, model) for _, ref, model in todo]
-    if args.lddt:                                                          # both scores from one parse of every file
-        if not (args.lddt_radius > 0 and args.lddt_radius < float("inf")):
-            sys.exit(f"--lddt_radius {args.lddt_radius} is not a positive finite number")
-        paths = list(dict.fromkeys(side for pair in sides for side in pair))
-        parsed = dict(zip(paths, superpose._load_layouts(paths, "CA", args.workers)))
-        # a file that could not be read stays a path: each score reports the error itself
-        sides = [tuple(side if isinstance(parsed[side], str) else parsed[side] for side in pair) for pair in sides]
-    results = superpose.superpose(sides, pair_by=args.pair_by, cycles=args.cycles, cutoff=args.cutoff,
-                                  device=args.device, workers=args.workers, stats=stats)
+    prepared = superpose.prepare([(ref, model) for _, ref, model in todo], args.pair_by, "CA", args.workers)     # read and paired once for both scores
+    results = superpose.superpose(prepared, cycles=args.cycles, cutoff=args.cutoff, device=args.device, stats=stats)
     out = Path(args.path_to_output)
     out.mkdir(parents=True, exist_ok=True)
     if args.lddt:
-        write_lddt(out, todo, lddt_module.lddt(sides, pair_by=args.pair_by, radius=args.lddt_radius, device=args.device, workers=args.workers,
-                                               stats=stats))
-        stats["files_parsed"] = len(paths)
+        write_lddt(out, todo, lddt_module.lddt(prepared, radius=args.lddt_radius, device=args.device, stats=stats))
     with open(out / "model_scores.csv", "w", newline="") as fs, open(out / "residue_deviation.csv", "w", newline="") as fr:
         ws, wr = csv.writer(fs), csv.writer(fr)
         ws.writerow(SCORE_COLUMNS)

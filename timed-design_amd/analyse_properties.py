@@ -20,47 +20,13 @@ sample / rank columns — the ``structure`` column is the file's path relative t
 import argparse
 import csv
 import sys
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
 
-from timed_hip import structure
-
-PDB_SUFFIXES = (".pdb", ".pdb1", ".ent")
-
-
-def is_pdb_name(name: str) -> bool:
-    name = name.lower()
-    if name.endswith(".gz"):
-        name = name[:-3]
-    return name.endswith(PDB_SUFFIXES)
-
-
-def find_structures(entries):
-    """[(label, path)]: a file as it is (labelled by its name), a directory searched recursively for *.pdb, *.pdb1, *.ent, each
-    optionally .gz (labelled by the path below the directory), in sorted order"""
-    found = []
-    for entry in entries:
-        entry = Path(entry)
-        if entry.is_dir():
-            found += [(str(p.relative_to(entry)), p) for p in sorted(entry.rglob("*")) if p.is_file() and is_pdb_name(p.name)]
-        elif entry.is_file():
-            found.append((entry.name, entry))
-        else:
-            raise FileNotFoundError(f"No structure file or directory at {entry}")
-    return found
-
-
-def stem_of(label: str) -> str:
-    name = Path(label).name
-    if name.lower().endswith(".gz"):
-        name = name[:-3]
-    return name.rsplit(".", 1)[0]
-
-
-def _fmt(v: float) -> str:
-    return repr(float(v))
+from timed_hip import batching, structure
+from timed_hip.pdbio import PDB_SUFFIXES, find_structures, is_pdb_name, stem_of  # noqa: F401  (their home; kept importable from here)
+from timed_hip.textio import float_repr as _fmt
 
 
 def main(args):
@@ -78,8 +44,7 @@ def main(args):
     def parse(item):
         model = structure.first_model(item[1])
         return model, structure.layout(model, args.atom_filter_function, include_hetero=True, all_chains=args.all_chains)
-    with ThreadPoolExecutor(max_workers=max(1, args.workers)) as pool:
-        parsed = list(pool.map(parse, found))
+    parsed = batching.parse_each(parse, found, args.workers)
     stats = {}
     results = structure.packing_density_layouts([l for _, l in parsed], radius=args.radius, device=args.device,
                                                 budget_bytes=int(args.batch_mb * (1 << 20)), stats=stats)
@@ -117,7 +82,7 @@ CLI_FLAGS = (
                                          "ca (the reference's substring test: atoms named C and CA), backbone (N CA C O), calpha (CA alone)")),
     ("--radius", dict(type=float, default=7.0, help="contact radius in Angstrom (default 7, Weiss 2007)")),
     ("--path_to_output", dict(type=str, default="properties", help="directory for residue_properties.csv and structure_properties.csv")),
-    ("--workers", dict(type=int, default=8, help="host threads that read and parse the files")),
+    ("--workers", dict(type=int, default=8, help="host threads that read and parse the files (at most 16)")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
     ("--all_chains", dict(default=False, action="store_true", help="report the residues of every chain, not only the first")),
     ("--batch_mb", dict(type=float, default=256.0, help="atom-array megabytes per GPU submission (default 256)")),

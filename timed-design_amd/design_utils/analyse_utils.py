@@ -307,9 +307,7 @@ def tag_pdb_with_rot(workers: int, path_to_pdb, pdb_codes, device: int = 0) -> t
     ``pdb_to_assemblies[pdb4][chain].sequence`` is what the reference reads from it.  The files are parsed on ``workers`` host
     threads (at most 16) and ALL structures are tagged on the GPU together (timed_hip.structure.tag_rotamers; the rule is this
     project's own, PARITY UNPINNED AGAINST AMPAL, see timed_hip/structure.py)."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    from timed_hip import structure
+    from timed_hip import batching, structure
     found = []
     for code in pdb_codes:
         code = str(code)
@@ -318,8 +316,7 @@ def tag_pdb_with_rot(workers: int, path_to_pdb, pdb_codes, device: int = 0) -> t
             print(f"Could not find {tried}")
         else:
             found.append((code, path))
-    with ThreadPoolExecutor(max_workers=max(1, min(int(workers), 16))) as pool:
-        layouts = list(pool.map(lambda item: structure.rotamer_layout(structure.first_model(item[1])), found))
+    layouts = batching.parse_each(lambda item: structure.rotamer_layout(structure.first_model(item[1])), found, workers)
     results_dict, pdb_to_assemblies = {}, {}
     for (code, _), tagged in zip(found, structure.tag_rotamers(layouts, device=device)):
         chains = chains_of(tagged)

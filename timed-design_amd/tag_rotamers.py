@@ -17,19 +17,17 @@ import argparse
 import csv
 import json
 import sys
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
-from analyse_properties import find_structures, stem_of
-from timed_hip import structure
+from timed_hip import batching, structure
+from timed_hip.pdbio import find_structures, stem_of
 
 
 def main(args):
     found = find_structures(args.path_to_pdb)
     if not found:
         sys.exit(f"no *.pdb / *.pdb1 / *.ent (.gz) file under {args.path_to_pdb}")
-    with ThreadPoolExecutor(max_workers=max(1, min(args.workers, 16))) as pool:
-        layouts = list(pool.map(lambda item: structure.rotamer_layout(structure.first_model(item[1])), found))
+    layouts = batching.parse_each(lambda item: structure.rotamer_layout(structure.first_model(item[1])), found, args.workers)
     stats = {}
     tagged = structure.tag_rotamers(layouts, device=args.device, ala_gly_class=not args.no_ala_gly_class, stats=stats)
     out = Path(args.path_to_output)

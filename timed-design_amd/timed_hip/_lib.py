@@ -134,6 +134,11 @@ def check(rc: int) -> None:
         raise TimedHipError(rc, load().th_last_error().decode(errors="replace"))
 
 
+def ptr(a):
+    """the data of a NumPy array as a void pointer; None stays None (NULL: an optional argument left out)"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
 def device_count() -> int:
     n = C.c_int(0)
     rc = load().th_device_count(C.byref(n))

@@ -13,6 +13,7 @@ import typing as t
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 
 RESIDUES = "ACDEFGHIKLMNPQRSTVWY"
 N_RES = 20
@@ -87,9 +88,6 @@ def analyse_probs(matrix, true_res, col_res, device: int = 0, rows: bool = True)
     rank = np.empty(n, np.int8) if rows else None
     ent = np.empty(n, np.float64) if rows else None
     tot = Totals()
-
-    def ptr(x):
-        return None if x is None else x.ctypes.data_as(C.c_void_p)
     _lib.check(_lib.load().th_analyse_probs(int(device), ptr(a), _DTYPES[a.dtype], n, k, ptr(owners), ptr(truth), ptr(pred),
                                             ptr(rank), ptr(ent), C.byref(tot)))
     return Analysis(pred, rank, ent, np.ctypeslib.as_array(tot.confusion).copy(), np.ctypeslib.as_array(tot.rank_hist).copy(),
@@ -265,9 +263,6 @@ def analyse_classes(matrix, true_class, device: int = 0, auc: bool = True, rows:
     scored = np.zeros(kk, np.int64)
     u2 = np.zeros((kk, kk), np.int64) if auc else None
     cnt = ClassCounts()
-
-    def ptr(x):
-        return None if x is None else x.ctypes.data_as(C.c_void_p)
     _lib.check(_lib.load().th_analyse_classes(int(device), ptr(a), _DTYPES[a.dtype], n, k, ptr(truth), ptr(pred), ptr(rank),
                                               ptr(conf), ptr(hist), ptr(scored), ptr(u2), C.byref(cnt)))
     return ClassAnalysis(pred, rank, conf, hist, scored, u2, int(cnt.n_labelled), int(cnt.n_nonfinite), int(cnt.n_scored))

@@ -21,14 +21,14 @@ its models (the reference plots that prediction in ``plot_af2IDDT_vs_position``)
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib, pdbio, structure
-from .superpose import PAIR_BY, AtomLayout, _load_layouts, pair_positions
+from ._lib import ptr
+from .superpose import _load_layouts, pair_positions, prepare, score_pairs  # noqa: F401  (the first two: read and paired exactly as there)
 
 RADIUS = 15.0
 THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
@@ -59,9 +59,6 @@ def lddt_arrays(ref_xyz, mob_xyz, offsets, radius: float = RADIUS, thresholds: S
     residue = np.empty((total, 5), np.int32)
     pair = np.empty((n_pairs, 6), np.int64)
     ms = C.c_double(0.0)
-
-    def ptr(a):
-        return a.ctypes.data_as(C.c_void_p)
     _lib.check(_lib.load().th_lddt(int(device), ptr(ref_xyz), ptr(mob_xyz), total, ptr(offsets), n_pairs, float(radius), ptr(limits),
                                    ptr(residue), ptr(pair), C.byref(ms) if timing is not None else None))
     if timing is not None:
@@ -104,49 +101,20 @@ def lddt(pairs: Sequence[Tuple], pair_by: str = "position", atom: str = "CA", ra
          device: int = 0, workers: int = 8, budget_bytes: int = structure.BATCH_BYTES, stats: Optional[dict] = None) -> List[LddtResult]:
     """Every ``(reference, model)`` pair — paths of PDB files (plain or gzipped), ``pdbio.Model`` objects or ``AtomLayout`` objects, as
     for ``superpose.superpose`` — scored under the rule of the module docstring.  One GPU call per batch; batches are cut by
-    ``structure.cut_batches`` under ``budget_bytes`` (68 bytes per position: its coordinates and counts, nothing per pair of
+    ``batching.cut_batches`` under ``budget_bytes`` (68 bytes per position: its coordinates and counts, nothing per pair of
     positions).  A pair that cannot be scored carries its ``error`` and does not stop the others.  ``stats`` receives
-    ``submissions``, ``kernel_ms`` and ``files_parsed``."""
-    if pair_by not in PAIR_BY:
-        raise ValueError(f"pair_by {pair_by!r} not in {PAIR_BY}")
-    pairs = list(pairs)
-    flat = _load_layouts([side for pair in pairs for side in pair[:2]], atom, workers)
-    results: List[Optional[LddtResult]] = [None] * len(pairs)
-    ready = []
-    for k in range(len(pairs)):
-        ref, mod = flat[2 * k], flat[2 * k + 1]
-        broken = [side for side in (ref, mod) if isinstance(side, str)]
-        if broken:
-            results[k] = _failed("; ".join(broken))
-            continue
-        ours, theirs, error = pair_positions(ref, mod, pair_by)
-        if error:
-            results[k] = _failed(error)
-            continue
-        ready.append((k, ref, mod, ours, theirs))
-    # cut_batches counts in atoms of structure._ATOM_BYTES: a pair's positions, in bytes, rounded up to whole atoms
-    runs = structure.cut_batches([-(-len(item[3]) * _POSITION_BYTES // structure._ATOM_BYTES) for item in ready], budget_bytes)
-    timing = {}
-    for lo, hi in runs:
-        part = ready[lo:hi]
-        offsets = np.zeros(len(part) + 1, np.int64)
-        np.cumsum([len(item[3]) for item in part], out=offsets[1:])
-        ref_xyz = np.concatenate([ref.xyz[ours] for _, ref, _, ours, _ in part])
-        mob_xyz = np.concatenate([mod.xyz[theirs] for _, _, mod, _, theirs in part])
-        got = lddt_arrays(ref_xyz, mob_xyz, offsets, radius, thresholds, device, timing)
-        for j, (k, ref, mod, ours, theirs) in enumerate(part):
-            a, b = int(offsets[j]), int(offsets[j + 1])
-            rows, totals = got.residue[a:b], got.pair[j]
-            preserved, whole = fractions(totals[1:6])
-            n_i = rows[:, 0].copy()
-            with np.errstate(invalid="ignore", divide="ignore"):
-                lddt_i = np.where(n_i > 0, rows[:, 1:5].sum(axis=1) / (4.0 * n_i), np.nan)
-            bfactor = np.array([mod.residues[t].bfactors.get(atom, float("nan")) for t in theirs], dtype=np.float64)
-            results[k] = LddtResult(None, int(totals[0]), int(totals[1]), preserved, whole, lddt_i, n_i, [ref.residues[i] for i in ours],
-                                    len(ref.residues) - len(ours), len(mod.residues) - len(theirs), bfactor)
-    if stats is not None:
-        stats["submissions"] = stats.get("submissions", 0) + len(runs)
-        stats["kernel_ms"] = stats.get("kernel_ms", 0.0) + timing.get("kernel_ms", 0.0)
-        stats["files_parsed"] = stats.get("files_parsed", 0) + len({os.fspath(s) for pair in pairs for s in pair[:2]
-                                                                     if not isinstance(s, (AtomLayout, pdbio.Model))})
-    return results
+    ``submissions``, ``kernel_ms`` and ``files_parsed``.  ``pairs`` may be what ``superpose.prepare`` returned."""
+    prepared = prepare(pairs, pair_by, atom, workers)
+
+    def result(got, j, a, b, ref, mod, ours, theirs):
+        rows, totals = got.residue[a:b], got.pair[j]
+        preserved, whole = fractions(totals[1:6])
+        n_i = rows[:, 0].copy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lddt_i = np.where(n_i > 0, rows[:, 1:5].sum(axis=1) / (4.0 * n_i), np.nan)
+        bfactor = np.array([mod.residues[t].bfactors.get(prepared.atom, float("nan")) for t in theirs], dtype=np.float64)
+        return LddtResult(None, int(totals[0]), int(totals[1]), preserved, whole, lddt_i, n_i, [ref.residues[i] for i in ours],
+                          len(ref.residues) - len(ours), len(mod.residues) - len(theirs), bfactor)
+    return score_pairs(prepared, budget_bytes, stats, _POSITION_BYTES,
+                       lambda ref_xyz, mob_xyz, offsets, timing: lddt_arrays(ref_xyz, mob_xyz, offsets, radius, thresholds, device, timing),
+                       result, _failed)

@@ -3,14 +3,47 @@ gzipped (the reference ships tests/testing_files/1ubq.pdb1.gz and passes ``is_pd
 Only what voxelisation needs: coordinates, atom / residue names, chain, residue number (+ insertion code), element,
 model number.  Alternate locations: the first one seen for an atom name within a residue wins (blank or 'A').
 The temperature factor (columns 61-66; AlphaFold2 writes pLDDT there) is kept per atom for timed_hip.structure.
+``find_structures`` / ``stem_of``: which files of a directory the command-line programs take for structures, and their labels.
 """
 from __future__ import annotations
 
 import gzip
 from dataclasses import dataclass, field
+from pathlib import Path
 from typing import Dict, List, Tuple
 
 import numpy as np
+
+PDB_SUFFIXES = (".pdb", ".pdb1", ".ent")
+
+
+def is_pdb_name(name: str) -> bool:
+    name = name.lower()
+    if name.endswith(".gz"):
+        name = name[:-3]
+    return name.endswith(PDB_SUFFIXES)
+
+
+def find_structures(entries):
+    """[(label, path)]: a file as it is (labelled by its name), a directory searched recursively for *.pdb, *.pdb1, *.ent, each
+    optionally .gz (labelled by the path below the directory), in sorted order"""
+    found = []
+    for entry in entries:
+        entry = Path(entry)
+        if entry.is_dir():
+            found += [(str(p.relative_to(entry)), p) for p in sorted(entry.rglob("*")) if p.is_file() and is_pdb_name(p.name)]
+        elif entry.is_file():
+            found.append((entry.name, entry))
+        else:
+            raise FileNotFoundError(f"No structure file or directory at {entry}")
+    return found
+
+
+def stem_of(label: str) -> str:
+    name = Path(label).name
+    if name.lower().endswith(".gz"):
+        name = name[:-3]
+    return name.rsplit(".", 1)[0]
 
 
 @dataclass

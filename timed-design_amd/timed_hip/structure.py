@@ -49,13 +49,14 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import _lib, pdbio
+from . import _lib, batching, pdbio
+from ._lib import ptr
 
 ATOM_FILTERS = ("all", "ca", "backbone", "calpha")
 _BACKBONE = ("N", "CA", "C", "O")
-BATCH_BYTES = 256 << 20            # host bytes of atom arrays handed to one th_packing_density call
-_ATOM_BYTES = 3 * 8 + 4 + 1 + 4    # xyz, group, selected, density
-TAG_NO_ALA_GLY = 1                 # th_tag_rotamers flag bit 0: ALA and GLY stay unlabelled
+BATCH_BYTES = batching.BATCH_BYTES  # host bytes of atom arrays handed to one th_packing_density call
+_ATOM_BYTES = 3 * 8 + 4 + 1 + 4     # xyz, group, selected, density
+TAG_NO_ALA_GLY = 1                  # th_tag_rotamers flag bit 0: ALA and GLY stay unlabelled
 
 
 def atom_selected(name: str, atom_filter: str) -> bool:
@@ -137,7 +138,7 @@ def contact_numbers(xyz, offsets, radius: float = 7.0, group=None, selected=None
                     atoms: bool = True, timing: Optional[dict] = None):
     """One th_packing_density call.  ``xyz`` [total, 3] float64, ``offsets`` [S + 1]; ``group`` / ``selected`` [total] with
     ``n_groups`` residues (or none).  Returns (int32 [total] or None when ``atoms`` is false, float64 [n_groups]).  ``timing``: a
-    dict that receives ``kernel_ms``."""
+    dict whose ``kernel_ms`` grows by the device time of the kernel."""
     xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
     if offsets.size < 1:
@@ -151,14 +152,11 @@ def contact_numbers(xyz, offsets, radius: float = 7.0, group=None, selected=None
     density = np.empty(total, np.int32) if atoms else None
     residue = np.empty(int(n_groups), np.float64)
     ms = C.c_double(0.0)
-
-    def ptr(a):
-        return None if a is None else a.ctypes.data_as(C.c_void_p)
     _lib.check(_lib.load().th_packing_density(int(device), ptr(xyz), total, ptr(offsets), offsets.size - 1, float(radius),
                                               ptr(group) if n_groups else None, ptr(selected) if n_groups else None, int(n_groups),
                                               ptr(density), ptr(residue) if n_groups else None, C.byref(ms) if timing is not None else None))
     if timing is not None:
-        timing["kernel_ms"] = ms.value
+        timing["kernel_ms"] = timing.get("kernel_ms", 0.0) + ms.value
     return density, residue
 
 
@@ -172,37 +170,31 @@ class StructureDensity:
 
 def cut_batches(sizes: Sequence[int], budget_bytes: int = BATCH_BYTES) -> List[Tuple[int, int]]:
     """[lo, hi) runs of consecutive structures whose atom arrays fit ``budget_bytes`` (a structure above it goes alone)."""
-    runs, lo, used = [], 0, 0
-    for k, n in enumerate(sizes):
-        need = int(n) * _ATOM_BYTES
-        if k > lo and used + need > budget_bytes:
-            runs.append((lo, k))
-            lo, used = k, 0
-        used += need
-    if len(sizes) > lo:
-        runs.append((lo, len(sizes)))
-    return runs
+    return batching.cut_batches(sizes, budget_bytes, _ATOM_BYTES)
+
+
+def _part_starts(part) -> Tuple[np.ndarray, np.ndarray]:
+    """Where each layout of one batch starts in the batch's flat arrays: (first atom, first residue), [len(part) + 1] int64 each."""
+    atom_lo, res_lo = np.zeros(len(part) + 1, np.int64), np.zeros(len(part) + 1, np.int64)
+    np.cumsum([len(l.xyz) for l in part], out=atom_lo[1:])
+    np.cumsum([len(l.residues) for l in part], out=res_lo[1:])
+    return atom_lo, res_lo
 
 
 def packing_density_layouts(layouts: Sequence[Layout], radius: float = 7.0, device: int = 0, budget_bytes: int = BATCH_BYTES,
                             stats: Optional[dict] = None) -> List[StructureDensity]:
-    """The layouts through th_packing_density in as few calls as ``budget_bytes`` allows.  ``stats`` receives ``submissions``."""
+    """The layouts through th_packing_density in as few calls as ``budget_bytes`` allows.  ``stats`` receives ``submissions`` and
+    ``kernel_ms``."""
     out: List[StructureDensity] = []
-    runs = cut_batches([len(l.xyz) for l in layouts], budget_bytes)
-    for lo, hi in runs:
-        part = layouts[lo:hi]
-        offsets = np.zeros(len(part) + 1, np.int64)
-        np.cumsum([len(l.xyz) for l in part], out=offsets[1:])
-        res_lo = np.zeros(len(part) + 1, np.int64)
-        np.cumsum([len(l.residues) for l in part], out=res_lo[1:])
-        xyz = np.concatenate([l.xyz for l in part]) if part else np.zeros((0, 3))
+
+    def submit(part, timing):
+        offsets, res_lo = _part_starts(part)
         group = np.concatenate([np.where(l.group >= 0, l.group + res_lo[k], -1) for k, l in enumerate(part)]).astype(np.int32)
-        selected = np.concatenate([l.selected for l in part])
-        density, residue = contact_numbers(xyz, offsets, radius, group, selected, int(res_lo[-1]), device)
+        density, residue = contact_numbers(np.concatenate([l.xyz for l in part]), offsets, radius, group,
+                                           np.concatenate([l.selected for l in part]), int(res_lo[-1]), device, timing=timing)
         for k, l in enumerate(part):
             out.append(StructureDensity(density[offsets[k]:offsets[k + 1]].copy(), residue[res_lo[k]:res_lo[k + 1]].copy(), l.residues, l))
-    if stats is not None:
-        stats["submissions"] = stats.get("submissions", 0) + len(runs)
+    batching.run_batches(layouts, [len(l.xyz) for l in layouts], budget_bytes, _ATOM_BYTES, submit, stats)
     return out
 
 
@@ -291,9 +283,6 @@ def rotamer_classes(xyz, atom_name, res_offsets, res_type, device: int = 0, ala_
     cls = np.empty(n_res, np.int16)
     angles = np.empty((n_res, 4), np.float64) if chi else None
     ms = C.c_double(0.0)
-
-    def ptr(a):
-        return None if a is None else a.ctypes.data_as(C.c_void_p)
     _lib.check(_lib.load().th_tag_rotamers(int(device), ptr(xyz), ptr(atom_name), xyz.shape[0], ptr(res_offsets), ptr(res_type), n_res,
                                            0 if ala_gly_class else TAG_NO_ALA_GLY, ptr(cls), ptr(angles),
                                            C.byref(ms) if timing is not None else None))
@@ -321,22 +310,15 @@ def tag_rotamer_layouts(layouts: Sequence[RotamerLayout], device: int = 0, ala_g
     """The layouts through th_tag_rotamers in as few calls as ``budget_bytes`` allows (cut_batches, as packing_density_layouts).
     ``stats`` receives ``submissions`` and ``kernel_ms``."""
     out: List[StructureRotamers] = []
-    runs = cut_batches([len(l.xyz) for l in layouts], budget_bytes)
-    timing = {} if stats is not None else None
-    for lo, hi in runs:
-        part = layouts[lo:hi]
-        atom_lo = np.zeros(len(part) + 1, np.int64)
-        np.cumsum([len(l.xyz) for l in part], out=atom_lo[1:])
-        res_lo = np.zeros(len(part) + 1, np.int64)
-        np.cumsum([len(l.residues) for l in part], out=res_lo[1:])
+
+    def submit(part, timing):
+        atom_lo, res_lo = _part_starts(part)
         offsets = np.concatenate([l.res_offsets[:-1] + atom_lo[k] for k, l in enumerate(part)] + [atom_lo[-1:]])
         cls, chi = rotamer_classes(np.concatenate([l.xyz for l in part]), np.concatenate([l.atom_name for l in part]), offsets,
                                    np.concatenate([l.res_type for l in part]), device, ala_gly_class, timing=timing)
         for k, l in enumerate(part):
             out.append(StructureRotamers(l.residues, cls[res_lo[k]:res_lo[k + 1]].copy(), chi[res_lo[k]:res_lo[k + 1]].copy()))
-    if stats is not None:
-        stats["submissions"] = stats.get("submissions", 0) + len(runs)
-        stats["kernel_ms"] = stats.get("kernel_ms", 0.0) + timing.get("kernel_ms", 0.0)
+    batching.run_batches(layouts, [len(l.xyz) for l in layouts], budget_bytes, _ATOM_BYTES, submit, stats)
     return out
 
 

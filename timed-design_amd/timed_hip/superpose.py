@@ -19,17 +19,18 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from concurrent.futures import ThreadPoolExecutor
-from dataclasses import dataclass
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
+from dataclasses import dataclass, field
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import _lib, pdbio, structure
+from . import _lib, batching, pdbio, structure
+from ._lib import ptr
 
 PAIR_BY = ("position", "number")
 GDT_CUTOFFS = (1.0, 2.0, 4.0, 8.0)
 _POSITION_BYTES = 2 * 3 * 8 + 8 + 1        # both coordinate lists, distance, kept byte
+_CHARGED_BYTES = 2 * structure._ATOM_BYTES  # what a position is charged against the budget: two atoms, more than it takes
 
 
 class Superposed(NamedTuple):
@@ -59,9 +60,6 @@ def superpose_arrays(ref_xyz, mob_xyz, offsets, cycles: int = 5, cutoff: float =
     counts = np.empty((n_pairs, 7), np.int32)
     moves = np.empty((n_pairs, 3, 4), np.float64) if transform else None
     ms = C.c_double(0.0)
-
-    def ptr(a):
-        return None if a is None else a.ctypes.data_as(C.c_void_p)
     _lib.check(_lib.load().th_superpose(int(device), ptr(ref_xyz), ptr(mob_xyz), total, ptr(offsets), n_pairs, int(cycles), float(cutoff),
                                         ptr(dist), ptr(kept), ptr(rmsd), ptr(counts), ptr(moves), C.byref(ms) if timing is not None else None))
     if timing is not None:
@@ -147,22 +145,15 @@ def pair_positions(reference: AtomLayout, model: AtomLayout, pair_by: str = "pos
 def _load_layouts(items, atom: str, workers: int) -> List[Optional[Union[AtomLayout, str]]]:
     """Every distinct file is read once (a native shared by a thousand models too), on host threads; a file that cannot be read
     becomes the error text of the pairs that name it."""
-    paths = {}
-    for item in items:
-        if not isinstance(item, (AtomLayout, pdbio.Model)):
-            paths.setdefault(os.fspath(item), None)
+    paths = list(dict.fromkeys(os.fspath(item) for item in items if not isinstance(item, (AtomLayout, pdbio.Model))))
 
     def parse(path):
         try:
             return atom_layout(structure.first_model(path), atom)
         except (OSError, EOFError, ValueError) as e:
             return f"{path}: {e}"
-    if paths:
-        with ThreadPoolExecutor(max_workers=max(1, min(int(workers), 16))) as pool:
-            for path, lay in zip(list(paths), pool.map(parse, list(paths))):
-                paths[path] = lay
-    models = {}
-    out = []
+    paths = dict(zip(paths, batching.parse_each(parse, paths, workers)))
+    models, out = {}, []
     for item in items:
         if isinstance(item, AtomLayout):
             out.append(item)
@@ -175,51 +166,76 @@ def _load_layouts(items, atom: str, workers: int) -> List[Optional[Union[AtomLay
     return out
 
 
+@dataclass
+class Prepared:
+    """What prepare() returns, and what superpose() and lddt.lddt() take in place of raw pairs."""
+    pairs: list                        # per pair (reference layout, model layout, indices into each), or the text of its error
+    files: int                         # distinct files read
+    atom: str
+    counted: list = field(default_factory=list)        # the stats dicts that hold ``files`` already
+
+
+def prepare(pairs: Sequence[Tuple], pair_by: str = "position", atom: str = "CA", workers: int = 8) -> Prepared:
+    """Read every distinct file of the ``(reference, model)`` pairs once and pair the positions of each pair once, for any number
+    of scorers: ``superpose(prepared, ...)`` and ``lddt.lddt(prepared, ...)`` then read and pair nothing (their ``pair_by``,
+    ``atom`` and ``workers`` are not looked at), and of the scorers that share one ``stats`` dict the first adds ``files_parsed``.
+    What prepare() returned comes back as it is."""
+    if isinstance(pairs, Prepared):
+        return pairs
+    if pair_by not in PAIR_BY:
+        raise ValueError(f"pair_by {pair_by!r} not in {PAIR_BY}")
+    sides = [side for pair in pairs for side in pair[:2]]
+    flat = _load_layouts(sides, atom, workers)
+    out = []
+    for ref, mod in zip(flat[0::2], flat[1::2]):
+        broken = [side for side in (ref, mod) if isinstance(side, str)]
+        if broken:
+            out.append("; ".join(broken))
+            continue
+        ours, theirs, error = pair_positions(ref, mod, pair_by)
+        out.append(error or (ref, mod, ours, theirs))
+    return Prepared(out, len({os.fspath(s) for s in sides if not isinstance(s, (AtomLayout, pdbio.Model))}), atom)
+
+
+def score_pairs(prepared: Prepared, budget_bytes: int, stats: Optional[dict], position_bytes: int, arrays: Callable, result: Callable,
+                failed: Callable) -> list:
+    """The driver superpose() and lddt.lddt() share: the pairs that can be scored go in batches of ``position_bytes`` per position
+    under ``budget_bytes``, one ``arrays(ref_xyz, mob_xyz, offsets, timing)`` call each; a pair's result is
+    ``result(got, j, a, b, ref, mod, ours, theirs)`` — pair j of the call, positions [a, b) of its flat arrays — or
+    ``failed(error text)``.  ``stats`` receives ``submissions``, ``kernel_ms`` and ``files_parsed``."""
+    results = [failed(item) if isinstance(item, str) else None for item in prepared.pairs]
+    ready = [(k,) + item for k, item in enumerate(prepared.pairs) if not isinstance(item, str)]
+
+    def submit(part, timing):
+        offsets = np.zeros(len(part) + 1, np.int64)
+        np.cumsum([len(item[3]) for item in part], out=offsets[1:])
+        ref_xyz = np.concatenate([ref.xyz[ours] for _, ref, _, ours, _ in part])
+        mob_xyz = np.concatenate([mod.xyz[theirs] for _, _, mod, _, theirs in part])
+        got = arrays(ref_xyz, mob_xyz, offsets, timing)
+        for j, (k, ref, mod, ours, theirs) in enumerate(part):
+            results[k] = result(got, j, int(offsets[j]), int(offsets[j + 1]), ref, mod, ours, theirs)
+    batching.run_batches(ready, [len(item[3]) for item in ready], budget_bytes, position_bytes, submit, stats)
+    if stats is not None and not any(seen is stats for seen in prepared.counted):
+        prepared.counted.append(stats)
+        stats["files_parsed"] = stats.get("files_parsed", 0) + prepared.files
+    return results
+
+
 def superpose(pairs: Sequence[Tuple], pair_by: str = "position", atom: str = "CA", cycles: int = 5, cutoff: float = 2.0, device: int = 0,
               transform: bool = False, workers: int = 8, budget_bytes: int = structure.BATCH_BYTES, stats: Optional[dict] = None) -> List[PairResult]:
     """Every ``(reference, model)`` pair — paths of PDB files (plain or gzipped), ``pdbio.Model`` objects or ``AtomLayout`` objects —
     superposed under the rule of the module docstring.  One GPU call per batch; batches are cut by ``structure.cut_batches`` under
     ``budget_bytes`` (a position counts as two atoms: it has two coordinate lists).  A pair that cannot be scored carries its
-    ``error`` and does not stop the others.  ``stats`` receives ``submissions``, ``kernel_ms`` and ``files_parsed``."""
-    if pair_by not in PAIR_BY:
-        raise ValueError(f"pair_by {pair_by!r} not in {PAIR_BY}")
-    pairs = list(pairs)
-    flat = _load_layouts([side for pair in pairs for side in pair[:2]], atom, workers)
-    results: List[Optional[PairResult]] = [None] * len(pairs)
-    ready = []                                                             # (pair index, reference layout, its indices, model xyz)
-    for k in range(len(pairs)):
-        ref, mod = flat[2 * k], flat[2 * k + 1]
-        broken = [side for side in (ref, mod) if isinstance(side, str)]
-        if broken:
-            results[k] = _failed("; ".join(broken))
-            continue
-        ours, theirs, error = pair_positions(ref, mod, pair_by)
-        if error:
-            results[k] = _failed(error)
-            continue
-        ready.append((k, ref, mod, ours, theirs))
-    runs = structure.cut_batches([2 * len(item[3]) for item in ready], budget_bytes)
-    timing = {}
-    for lo, hi in runs:
-        part = ready[lo:hi]
-        offsets = np.zeros(len(part) + 1, np.int64)
-        np.cumsum([len(item[3]) for item in part], out=offsets[1:])
-        ref_xyz = np.concatenate([ref.xyz[ours] for _, ref, _, ours, _ in part])
-        mob_xyz = np.concatenate([mod.xyz[theirs] for _, _, mod, _, theirs in part])
-        got = superpose_arrays(ref_xyz, mob_xyz, offsets, cycles, cutoff, device, transform, timing)
-        for j, (k, ref, mod, ours, theirs) in enumerate(part):
-            a, b = int(offsets[j]), int(offsets[j + 1])
-            counts = got.counts[j]
-            gdt, mean_gdt = gdt_fractions(counts)
-            residues = [ref.residues[i] for i in ours]
-            same = sum(ref.residues[i].name == mod.residues[t].name for i, t in zip(ours, theirs))
-            results[k] = PairResult(None, int(counts[0]), int(counts[1]), int(counts[2]), float(got.rmsd[j, 0]), float(got.rmsd[j, 1]),
-                                    float(got.rmsd[j, 2]), gdt, mean_gdt, same / len(ours) if len(ours) else float("nan"),
-                                    got.dist[a:b].copy(), got.kept[a:b].copy(), residues, len(ref.residues) - len(ours),
-                                    len(mod.residues) - len(theirs), got.transform[j].copy() if transform else None)
-    if stats is not None:
-        stats["submissions"] = stats.get("submissions", 0) + len(runs)
-        stats["kernel_ms"] = stats.get("kernel_ms", 0.0) + timing.get("kernel_ms", 0.0)
-        stats["files_parsed"] = stats.get("files_parsed", 0) + len({os.fspath(s) for pair in pairs for s in pair[:2]
-                                                                     if not isinstance(s, (AtomLayout, pdbio.Model))})
-    return results
+    ``error`` and does not stop the others.  ``stats`` receives ``submissions``, ``kernel_ms`` and ``files_parsed``.  ``pairs`` may
+    be what ``prepare`` returned."""
+    def result(got, j, a, b, ref, mod, ours, theirs):
+        counts = got.counts[j]
+        gdt, mean_gdt = gdt_fractions(counts)
+        same = sum(ref.residues[i].name == mod.residues[t].name for i, t in zip(ours, theirs))
+        return PairResult(None, int(counts[0]), int(counts[1]), int(counts[2]), float(got.rmsd[j, 0]), float(got.rmsd[j, 1]),
+                          float(got.rmsd[j, 2]), gdt, mean_gdt, same / len(ours) if len(ours) else float("nan"), got.dist[a:b].copy(),
+                          got.kept[a:b].copy(), [ref.residues[i] for i in ours], len(ref.residues) - len(ours),
+                          len(mod.residues) - len(theirs), got.transform[j].copy() if transform else None)
+    return score_pairs(prepare(pairs, pair_by, atom, workers), budget_bytes, stats, _CHARGED_BYTES,
+                       lambda ref_xyz, mob_xyz, offsets, timing: superpose_arrays(ref_xyz, mob_xyz, offsets, cycles, cutoff, device, transform, timing),
+                       result, _failed)

@@ -89,6 +89,11 @@ def _blocks(a: np.ndarray, device=None, scratch: "TextScratch | None" = None):
         yield memoryview(buf)[:got]
 
 
+def float_repr(v) -> str:
+    """a float64 as the CSV writers of the analysis programs spell it: the shortest text that reads back to the same value"""
+    return repr(float(v))
+
+
 def format_csv(matrix: np.ndarray, device=None) -> bytes:
     """'%.18e' / ',' / '\\n' text of a 2-D float16/32/64 matrix (a 1-D array is one value per line, as np.savetxt)."""
     return b"".join(bytes(m) for m in _blocks(_check(matrix), device))
