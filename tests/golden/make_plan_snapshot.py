@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Generate tests/golden/plan_snapshot.json — runs ONLY on the GPU box (plans are made at load, on the device).
 
-Pins what the load-time planner (csrc/runtime.hip, plan) produces: for every (model, load flags, knob set) of the corpus below,
+Pins what the load-time planner (csrc/planner.hip, plan) produces: for every (model, load flags, knob set) of the corpus below,
 each plan step's label, own FLOPs, issued FLOPs, bytes and direct-form FLOPs per frame, and the model's cost() totals.  All of
 these are host arithmetic on shapes, so tests/test_gpu_plan_snapshot.py asserts exact equality.  Loads run with TH_GUARD=0:
 the guard keeps its own tests.

@@ -1,4 +1,4 @@
-"""The per-process device block cache behind th_model_load / th_model_free (csrc/runtime.hip): blocks a closed model
+"""The per-process device block cache behind th_model_load / th_model_free (csrc/devcache.hip): blocks a closed model
 gives back are parked for the next load (exact-size reuse), at most min(24 GB, an eighth of the device's memory) per device, the
 blocks parked longest ago leave first, th_dev_trim empties it, and every allocator of the library trims it before it reports
 TH_ENOMEM (th_malloc_retry)."""

@@ -1,4 +1,4 @@
-"""The load-time guard (csrc/runtime.hip, guard_check; include/timed_hip.h th_model_guard_info) and the per-handle knobs.
+"""The load-time guard (csrc/guard.hip, guard_check; include/timed_hip.h th_model_guard_info) and the per-handle knobs.
 
 Every th_model_load checks the plan it built — Cook-Toom / Winograd layers, the bf16x3-split GEMMs — against a direct fp32-MFMA
 plan of the same pack on four internally generated frames; logits must agree to 1e-5 x max(1, max |logit|), otherwise fast

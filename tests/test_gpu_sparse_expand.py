@@ -1,4 +1,4 @@
-"""k_sparse_expand (csrc/sparse_frames.hip) off the 21^3 geometry, and th_predict_sparse_async's refusals (csrc/runtime.hip).
+"""k_sparse_expand (csrc/sparse_frames.hip) off the 21^3 geometry, and th_predict_sparse_async's refusals (csrc/predict.hip).
 
 The reference of every comparison is the input itself: frames that travelled sparse are fetched back from the device and compared
 with the frames as BYTES, so no tolerance is involved.  The model is Flatten -> Dense(20) -> Softmax directly on the input: no

@@ -244,3 +244,8 @@ def test_legacy_rand_replays_numpys_global_generator():
     np.random.seed(5); np.random.randn(1); a = (np.random.rand(10000), np.random.randn(3))
     np.random.seed(5); np.random.randn(1); b = (su._legacy_rand(10000), np.random.randn(3))
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+def test_runtime_units_are_built():
+    import __graft_entry__
+    assert {"devcache.hip", "planner.hip", "guard.hip", "predict.hip"} <= set(__graft_entry__.HIP_SOURCES)

@@ -87,7 +87,7 @@ int th_knobs_read(ThKnobs* k);                  // the process environment, now 
 inline const ThKnobs& th_knobs_of(const ThKnobs* k) { static const ThKnobs dflt; return k ? *k : dflt; }
 
 // hipMalloc for every allocator inside the library: when the device is out of memory the blocks parked in the model block
-// cache (runtime.hip: freed arenas kept for the next load) are returned to HIP and the allocation is tried once more — a dead
+// cache (devcache.hip: freed arenas kept for the next load) are returned to HIP and the allocation is tried once more — a dead
 // block in the cache must never be the reason a decode, a text formatter or a sampler runs out of memory.
 hipError_t th_malloc_retry_impl(void** p, size_t bytes);
 template <class T> inline hipError_t th_malloc_retry(T** p, size_t bytes) { return th_malloc_retry_impl(reinterpret_cast<void**>(p), bytes); }
@@ -127,7 +127,7 @@ struct PostOps {
     const float* shift[TH_MAX_POST] = {nullptr, nullptr, nullptr, nullptr};
     // every op is monotone non-decreasing (ReLU/ELU/LeakyReLU with alpha >= 0, sigmoid, tanh, BN-affine with
     // scale >= 0 on every channel): max-pooling then commutes with the whole chain, so a kernel may pool the raw
-    // accumulators first and run the chain on 1/8 of the values (set by the planner, runtime.hip)
+    // accumulators first and run the chain on 1/8 of the values (set by the planner, planner.hip)
     int monotone = 0;
 };
 // elementwise prologue applied to the conv input when it is staged (BN->ReLU->Conv chains)
