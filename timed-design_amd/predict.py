@@ -12,7 +12,9 @@ aposteriori ``.hdf5``, a frame pack, or a PDB file (``.pdb[.gz]`` / ``.pdb1[.gz]
 timed_hip.voxeliser — parity unpinned against aposteriori).  Outputs (reference README.md:119-131): <model>.csv, <model>.fasta, <model>.txt,
 dataset.fasta, datasetmap.txt, encoded_labels.csv, plus <model>_rot.csv in rotamer mode.
 
-How a run is organised (all of it invisible in the files, which are byte-identical to a batch-by-batch run):
+How a run is organised (all of it invisible in the files, which are byte-identical to a batch-by-batch run; the
+pipeline itself — call groups, loader, staging, the loader / submitter / writer loop — is timed_hip/pipeline.py, which has no
+counterpart in the reference):
   * consecutive reference batches are grouped into GPU calls of about ``frames_per_call`` frames;
   * a loader thread builds group g+1 (reference load_batch, utils.py:487-530) while the GPU computes group g and the
     main thread formats and appends the outputs of group g-1 (th_predict_async / th_predict_wait);
@@ -30,16 +32,14 @@ predict.py:123 — the UI and scripts expect the real name); the consensus files
 import argparse
 import os
 import sys
-import threading
-from collections import deque
 from concurrent.futures import ThreadPoolExecutor
-from math import ceil
 from pathlib import Path
 
 import numpy as np
 
 from design_utils import utils as du
 from timed_hip import engine, textio
+from timed_hip.pipeline import GroupLoader, _RowsOnDevice, _ToDevice, call_spans, row_groups, run_groups
 
 N_RESIDUE_CLASSES, N_ROTAMER_CLASSES = 20, 338
 
@@ -165,270 +165,6 @@ def _assemble_shard_files(files, gather, rank, world):
     gather.barrier()                                        # rank 0 reads the assembled files from here on
 
 
-def _row_groups(n_rows, batch_size, start_batch, frames_per_call):
-    """[lo, hi) row ranges, each a whole number of reference batches (so resuming at ``start_batch`` lines up)"""
-    per_call = max(1, int(frames_per_call) // max(1, batch_size)) * batch_size
-    first = start_batch * batch_size
-    groups, lo = [], first
-    # a run of several large calls starts with a quarter- and a half-size one: the GPU gets its first frames after a quarter of
-    # a group's load time instead of a whole one (the first load and the last forward pass are the two stages nothing overlaps)
-    ramp = [per_call // 4, per_call // 2] if per_call >= 1024 and n_rows - first > per_call else []
-    for size in ramp:
-        size = size // batch_size * batch_size
-        if size >= batch_size and lo + size < n_rows:
-            groups.append((lo, lo + size))
-            lo += size
-    groups += [(a, min(a + per_call, n_rows)) for a in range(lo, n_rows, per_call)]
-    return groups
-
-
-def _is_sparse(X) -> bool:
-    return type(X).__name__ == "SparseFrames"
-
-
-def _models_take_sparse(models) -> bool:
-    """every model of the round-robin is a HIP engine handle (or the sharded wrapper around one): only those read SparseFrames"""
-    for m in models:
-        inner = getattr(m, "sparse_ok", None)
-        if inner is None:
-            inner = hasattr(m, "_predict_async_sparse")
-        if not inner:
-            return False
-    return True
-
-
-def _run_groups(models, dataset_path, flat_dataset_map, groups, consume, gpu_decode=False):
-    """Pipeline over the call groups, three stages on three threads:
-         loader thread   load_batch of group g+1 (reference utils.py:487-530)
-         this thread     th_predict_async of group g, round-robin over ``models`` (the host->device copy of pageable
-                         frames blocks here while the kernels of group g-1 run)
-         writer thread   ``consume(probs, labels)`` for group g-1, strictly in group order (formats and appends)
-    An exception in any stage surfaces here."""
-    if not groups:
-        return
-    depth = 2 * len(models)
-
-    # Batches of an .hdf5 dataset are built in a small ring of reused buffers: a fresh 0.2-0.5 GB NumPy batch costs more
-    # in first-touch page faults than its inflation does.  The first ``ring_size`` full-size batches simply become the
-    # ring (no extra allocation); a buffer is reused only after the ticket that read it has completed: at most 3 groups
-    # per model are outstanding (below) + the one being loaded + one spare.  Pageable memory on purpose: host->device
-    # copies from it already run at the PCIe rate here, and page-locking 1 GB costs more than a short run takes
-    # (th_host_alloc exists for callers that keep their buffers).  Frame packs hand out memory-mapped rows instead.
-    ring = []
-    from timed_hip import framepack
-    plain_h5 = not framepack.is_pack(dataset_path) and not framepack.is_structure(dataset_path)
-    # a float32 pack with sparse transport files (framepack.sparsify): the loader hands out SparseFrames batches — a tenth of the
-    # bytes cross PCIe, the device rebuilds the dense frames (th_predict_sparse_async).  TIMED_SPARSE=0: the dense rows as before
-    sparse_pack = None
-    if framepack.is_pack(dataset_path) and os.environ.get("TIMED_SPARSE", "1") != "0" and getattr(models[0], "device", None) is not None:
-        fp = du._frame_pack(dataset_path)
-        if fp.sparse is not None and _models_take_sparse(models):
-            sparse_pack = fp
-    # loader threads: two on GPU-inflated datasets (see below), one elsewhere.  The ring is sized for ALL of them: when the device
-    # decode falls back to the host reader mid-run (an unsupported file, TH_ENOMEM), both loaders keep filling host buffers, and
-    # a ring sized for one would hand group k + 2 the slot of a group whose ticket may still be outstanding (ADVICE r4)
-    n_loaders = max(1, int(os.environ.get("TIMED_LOADERS", "2" if (gpu_decode and plain_h5) else "1")))
-    ring_size = 3 * len(models) + 1 + n_loaders
-    max_rows = max(hi - lo for lo, hi in groups)
-    use_ring = len(groups) > ring_size and plain_h5
-    full_seen = [0]                    # full-size groups loaded so far: they take the ring's slots in turn (ramp-up groups are smaller)
-
-    load_seconds = [0.0]
-
-    def load(k):
-        import time
-        t0 = time.perf_counter()
-        try:
-            return _load(k)
-        finally:
-            load_seconds[0] += time.perf_counter() - t0
-
-    decode_on_gpu = [bool(gpu_decode) and plain_h5]
-
-    host_lock = threading.Lock()       # the host reader's buffer ring is filled by one loader at a time
-
-    # Memory-mapped rows of a frame pack go through a ring of page-locked buffers (engine.StagingRing): the copy to the device
-    # then runs at the PCIe rate instead of the rate at which the driver pins pages it has never seen.  3 groups per model
-    # outstanding + the one waiting to be submitted + the one being filled.  TIMED_STAGING=0 hands out the mapped rows as before.
-    staging = [None]
-
-    sparse_ring = [None]
-
-    def _stage_sparse(X):
-        # a sparse batch (views of the memory-mapped transport files) is assembled into ONE page-locked blob: rank table, bitmaps, values
-        if sparse_ring[0] is False:
-            return X, None
-        if sparse_ring[0] is None:
-            sparse_ring[0] = False
-            try:
-                from timed_hip import _lib, engine
-                cpus = int(_lib.load().th_host_cpus())
-                ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1") or 1))
-                threads = int(os.environ.get("TIMED_STAGING_THREADS", str(max(1, min(8, (cpus - 2) // ranks_here)))))
-                if os.environ.get("TIMED_STAGING", "1") != "0":
-                    sparse_ring[0] = engine.BlobRing(3 * len(models) + 2, threads)
-            except Exception:
-                sparse_ring[0] = False
-            if sparse_ring[0] is False:
-                return X, None
-        got, slot = sparse_ring[0].stage(X)
-        return got, (None if slot is None else ("sparse", slot))
-
-    def _stage(X):
-        if _is_sparse(X):
-            return _stage_sparse(X)
-        if staging[0] is False or not isinstance(X, np.memmap) or getattr(models[0], "device", None) is None:
-            return X, None
-        if staging[0] is None:
-            staging[0] = False
-            try:
-                from timed_hip import _lib, engine
-                cpus = int(_lib.load().th_host_cpus())
-                ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1") or 1))          # one process per GPU shares the host's cores
-                threads = int(os.environ.get("TIMED_STAGING_THREADS", str(min(8, (cpus - 2) // ranks_here))))
-                if os.environ.get("TIMED_STAGING", "1") != "0" and threads >= 2 and len(groups) > 2:
-                    staging[0] = du.take_staging_ring(3 * len(models) + 2, max_rows, X.shape[1:], X.dtype, threads)
-            except Exception:
-                staging[0] = False
-            if staging[0] is False:
-                return X, None
-        return staging[0].stage(X)
-
-    def _load(k):
-        X, y = _load_rows(k)
-        X, slot = _stage(X)
-        return X, y, slot
-
-    def _load_rows(k):
-        lo, hi = groups[k]
-        if sparse_pack is not None:
-            rows = sparse_pack.contiguous_rows(flat_dataset_map[lo:hi])
-            if rows is not None:
-                return sparse_pack.sparse_batch(*rows), sparse_pack.labels[rows[0]:rows[1]].astype(float)
-        if decode_on_gpu[0]:
-            # gzip .hdf5: the chunks of this group are inflated ON the GPU that will predict it (th_h5_decode_device) — the
-            # frames never exist on the host; a dataset that cannot take the path (other filters, a layout h5lite does not read ...) says so
-            # once and the host reader takes over
-            got = du.load_batch_device(dataset_path, flat_dataset_map[lo:hi], device=models[k % len(models)].device)
-            if got is not None:
-                return got
-            decode_on_gpu[0] = False
-        with host_lock:
-            # full-size groups take the ring's slots in turn, starting with the FIRST full-size group (the smaller ramp-up groups
-            # in front of it, and the ragged last one, get buffers of their own)
-            slot = None
-            if use_ring and hi - lo == max_rows:
-                slot = full_seen[0] % ring_size
-                full_seen[0] += 1
-            # float32 frames: the rounding Keras applies to load_batch's float64 anyway, done while the chunks are placed
-            X, y = du.load_batch(dataset_path, flat_dataset_map[lo:hi], dtype=np.float32,
-                                 out=ring[slot] if slot is not None and slot < len(ring) else None)
-            if slot is not None and len(ring) == slot and isinstance(X, np.ndarray) and X.base is None and len(X) == max_rows:
-                ring.append(X)
-            return X, y
-
-    write_seconds = [0.0, 0.0]
-
-    def finish(ticket, labels, slot=None):
-        import time
-        t0 = time.perf_counter()
-        probs = ticket.result()
-        if isinstance(slot, tuple):
-            sparse_ring[0].release(slot[1])
-        elif slot is not None:
-            staging[0].release(slot)
-        t1 = time.perf_counter()
-        consume(probs, labels)
-        write_seconds[0] += t1 - t0
-        write_seconds[1] += time.perf_counter() - t1
-
-    pending = deque()          # tickets submitted to a GPU, oldest first
-    writing = deque()          # futures of the writer thread, oldest first
-    # three Python threads share the interpreter lock; with the default 5 ms switch interval the submitter can sit behind
-    # the writer for longer than a whole group takes on the GPU (4.6 ms per 1024 frames)
-    switch = sys.getswitchinterval()
-    sys.setswitchinterval(2e-4)
-    completed = False
-    try:
-        # Two loaders on GPU-inflated datasets: the host part of batch g+2 (object headers, B-trees, descriptors, ~6 ms of Python
-        # per 4096 frames) and its pageable upload run while the inflate kernels of batch g+1 hold the decoder's scratch set.
-        # Measured on 40 k gzip float64 frames (tools/trace_predict_e2e.py): the loop takes 0.229 s with one loader, 0.178 s with
-        # two — 17.8 ms per 4096 frames, which is the inflate kernels (8 ms) plus the CNN (10.3 ms) one after the other on the
-        # GPU — and 0.19 s with three.  (When the CNN took twice as long the second loader bought nothing.)  One loader elsewhere:
-        # the host reader fills its ring under a lock anyway, and frame packs hand out mapped rows.
-        _pump(models, groups, load, finish, pending, writing, depth, loaders=n_loaders)
-        completed = True
-    finally:
-        sys.setswitchinterval(switch)
-        if staging[0]:
-            for ticket, *_rest in pending:           # after an error: nothing may still be copying out of a slot
-                try:
-                    ticket.result()
-                except Exception:
-                    pass
-            if completed:
-                du.give_back_staging_ring(staging[0])    # kept for the next call; du.release_device_memory() (the CLI, at its end) closes it
-            else:
-                staging[0].close()
-        if sparse_ring[0]:
-            if not completed:
-                for ticket, *_rest in pending:
-                    try:
-                        ticket.result()
-                    except Exception:
-                        pass
-            sparse_ring[0].close()
-    if os.environ.get("TIMED_PIPELINE_TRACE"):
-        print(f"[pipeline] load_batch calls took {load_seconds[0]:.3f} s in the loader thread(s); the writer thread waited {write_seconds[0]:.3f} s "
-              f"for results and spent {write_seconds[1]:.3f} s formatting / appending", file=sys.stderr)
-        if decode_on_gpu[0] and any(du._LOAD_TRACE):
-            a = du._LOAD_TRACE
-            print(f"[pipeline] load_batch_device: group links {a[0]:.3f} s, object headers (resolve_many) {a[1]:.3f} s, device buffer {a[2]:.3f} s, "
-                  f"B-trees + upload + inflate {a[3]:.3f} s", file=sys.stderr)
-            a[:] = [0.0] * 4
-    del ring[:]
-
-
-def _pump(models, groups, load, finish, pending, writing, depth, loaders=1):
-    trace = os.environ.get("TIMED_PIPELINE_TRACE")
-    if trace:
-        import time
-        t_load = t_wait = t_submit = 0.0
-        clock = time.perf_counter
-    with ThreadPoolExecutor(max_workers=loaders, thread_name_prefix="load_batch") as loader, \
-            ThreadPoolExecutor(max_workers=1, thread_name_prefix="write_outputs") as writer:
-        ahead = deque(loader.submit(load, j) for j in range(min(loaders, len(groups))))     # groups being loaded, in order
-        for k in range(len(groups)):
-            if trace:
-                t0 = clock()
-            X, y, *extra = ahead.popleft().result()
-            if k + loaders < len(groups):
-                ahead.append(loader.submit(load, k + loaders))
-            if trace:
-                t1 = clock(); t_load += t1 - t0
-            # a model has 4 tickets (th_predict_async): at most 3 consecutive groups per model are outstanding here,
-            # 2 on the GPU queue and 1 with the writer
-            while len(pending) + len(writing) >= 3 * len(models):
-                if not writing:
-                    writing.append(writer.submit(finish, *pending.popleft()))
-                writing.popleft().result()
-            if trace:
-                t2 = clock(); t_wait += t2 - t1
-            pending.append((models[k % len(models)].predict_async(X), y, *extra))
-            del X
-            if trace:
-                t_submit += clock() - t2
-            if len(pending) >= depth:
-                writing.append(writer.submit(finish, *pending.popleft()))
-        while pending:
-            writing.append(writer.submit(finish, *pending.popleft()))
-        while writing:
-            writing.popleft().result()
-    if trace:
-        print(f"[pipeline] {len(groups)} groups: waiting for the loader {t_load:.3f} s, for the writer/GPU {t_wait:.3f} s, "
-              f"submitting (incl. pageable host->device copies) {t_submit:.3f} s", file=sys.stderr)
-
-
 def _distributed_context(gather):
     """(rank, world, local_rank, gather): world > 1 when launched one process per GPU (torch.distributed.run)."""
     from timed_hip import distributed as td
@@ -539,9 +275,8 @@ def load_dataset_and_predict(
                 else:
                     files = _OutputFiles(index, model_name, flat_dataset_map, path_to_output, predict_rotamers, codec,
                                          resume=start_batch > 0, device=getattr(handles[0], "device", None))
-                    _run_groups(handles, dataset_path, flat_dataset_map,
-                                _row_groups(len(flat_dataset_map), batch_size, start_batch, frames_per_call), files.append,
-                                gpu_decode=gpu_decode)
+                    groups = row_groups(len(flat_dataset_map), batch_size, start_batch, frames_per_call)
+                    run_groups(handles, GroupLoader(handles, dataset_path, flat_dataset_map, groups, gpu_decode), files.append)
             finally:
                 if files is not None:
                     files.close()
@@ -677,7 +412,7 @@ def _predict_sharded(model, gather, rank, world, dataset_path, flat_dataset_map,
     counts = td.shard_counts(n, world)
     lo, hi = td.shard_bounds(n, world)[rank]
     shard = flat_dataset_map[row0 + lo: row0 + hi]
-    groups = [(a, min(a + max(1, int(frames_per_call)), len(shard))) for a in range(0, len(shard), max(1, int(frames_per_call)))]
+    groups = call_spans(0, len(shard), max(1, int(frames_per_call)))      # (no ramp-up, and not in whole reference batches)
     own_transport = gather is None
     if own_transport:
         if os.environ.get("TIMED_GATHER", "rccl") == "host":
@@ -689,39 +424,21 @@ def _predict_sharded(model, gather, rank, world, dataset_path, flat_dataset_map,
         if isinstance(gather, td.RcclGather):
             width = model.n_classes
             d_local = engine.DeviceBuffer(max(1, len(shard) * width * 4), model.device)
-
-            class _RowsOnDevice:      # a ticket whose rows sit in d_local: result() brings them to the host for formatting
-                def __init__(self, ticket, row, rows):
-                    self.ticket, self.row, self.rows = ticket, row, rows
-
-                def result(self):
-                    self.ticket.result()
-                    return d_local.download((self.rows, width), np.float32, offset=self.row * width * 4)
-
-            class _ToDevice:          # the model facade _run_groups drives: outputs land in d_local at the shard row
-                sparse_ok = True          # predict_async_device reads SparseFrames batches too
-
-                def __init__(self):
-                    self.row = 0
-                    self.device = model.device
-
-                def predict_async(self, X):
-                    t = _RowsOnDevice(model.predict_async_device(X, d_local.ptr + self.row * width * 4), self.row, len(X))
-                    self.row += len(X)
-                    return t
-            _run_groups([_ToDevice()], dataset_path, shard, groups, files.append, gpu_decode=gpu_decode)
+            to_device = _ToDevice(model, d_local, width)         # outputs land in d_local at the shard row
+            run_groups([to_device], GroupLoader([to_device], dataset_path, shard, groups, gpu_decode), files.append)
             d_all = engine.DeviceBuffer(max(1, n * width * 4), model.device) if rank == 0 else None
             gather.gather_rows_device(d_local.ptr, counts, width, 0, d_all.ptr if d_all else 0)
             probs = d_all.download((n, width), np.float32) if rank == 0 else None
         else:                     # host transport (distributed.HostGather; tests/_gloo_transport.GlooGather): rows are on the host already
             local = np.zeros((len(shard), model.n_classes), dtype=np.float32)
-            cursor = [0]
+            cursor = 0
 
             def keep(p, y):
-                local[cursor[0]:cursor[0] + len(y)] = p
-                cursor[0] += len(y)
+                nonlocal cursor
+                local[cursor:cursor + len(y)] = p
+                cursor += len(y)
                 files.append(p, y)
-            _run_groups([model], dataset_path, shard, groups, keep, gpu_decode=gpu_decode)
+            run_groups([model], GroupLoader([model], dataset_path, shard, groups, gpu_decode), keep)
             probs = gather.gather_rows(local, counts, 0)
         _assemble_shard_files(files, gather, rank, world)
     finally:

@@ -63,11 +63,8 @@ class HipFrameModel:
         raise ValueError(f"{path}: neither a THPK0001 pack nor an HDF5 (.h5) Keras model")
 
     # ---- Keras-compatible surface --------------------------------------------------------------
-    def predict(self, X, batch_size: Optional[int] = None, verbose=0, logits: bool = False, **_ignored) -> np.ndarray:
-        """X[B,D,H,W,C] -> float32 [B,n_classes].  ``batch_size``/``verbose`` are accepted for
-        signature compatibility with ``Model.predict``; chunking is internal."""
-        if isinstance(X, SparseFrames):
-            return self.predict_async(X, logits=logits).result()
+    def _host_frames(self, X):
+        """(C-contiguous ndarray of an accepted dtype, its TH_* dtype code) of a batch handed over as anything np.asarray takes"""
         X = np.asarray(X)
         if X.ndim != 5 or tuple(X.shape[1:]) != self.input_shape:
             raise ValueError(f"expected frames of shape (B, {', '.join(map(str, self.input_shape))}), got {X.shape}")
@@ -75,7 +72,14 @@ class HipFrameModel:
         if dt is None:
             X = X.astype(np.float32)
             dt = _lib.TH_F32
-        X = np.ascontiguousarray(X)
+        return np.ascontiguousarray(X), dt
+
+    def predict(self, X, batch_size: Optional[int] = None, verbose=0, logits: bool = False, **_ignored) -> np.ndarray:
+        """X[B,D,H,W,C] -> float32 [B,n_classes].  ``batch_size``/``verbose`` are accepted for
+        signature compatibility with ``Model.predict``; chunking is internal."""
+        if isinstance(X, SparseFrames):
+            return self.predict_async(X, logits=logits).result()
+        X, dt = self._host_frames(X)
         n = X.shape[0]
         width = self.logits_width if logits else self.n_classes
         out = np.empty((n, width), dtype=np.float32)
@@ -87,11 +91,9 @@ class HipFrameModel:
     __call__ = predict
 
     def predict_async(self, X, logits: bool = False) -> "PendingPrediction":
-        if isinstance(X, DeviceFrames):
-            return self.predict_async_frames_on_device(X, logits=logits)
         if isinstance(X, SparseFrames):
             return self._predict_async_sparse(X, None, logits=logits)
-        return self._predict_async_host(X, logits=logits)
+        return self._submit(X, None, logits)
 
     def _predict_async_sparse(self, X: "SparseFrames", d_out, logits: bool = False) -> "PendingPrediction":
         """A batch in the sparse transport form (SparseFrames: bitmap + stored values, timed_hip/framepack.py): a tenth of the
@@ -111,6 +113,31 @@ class HipFrameModel:
                                                      C.c_void_p(d_out) if d_out is not None else out.ctypes.data, flags, C.byref(ticket)))
         return PendingPrediction(self, ticket.value, (X, blob), out)
 
+    def _submit(self, X, d_out, logits: bool) -> "PendingPrediction":
+        """The one dense th_predict_async call.  ``X``: host frames (an ndarray of any accepted dtype or anything np.asarray takes:
+        copied to the device) or DeviceFrames on this model's device (nothing is copied).  ``d_out`` None: the rows come back in a
+        new host array; a device address: they are left there (TH_PREDICT_OUT_DEVICE) and ``result()`` returns None."""
+        flags = _lib.TH_PREDICT_LOGITS if logits else 0
+        if isinstance(X, DeviceFrames):
+            if tuple(X.shape[1:]) != self.input_shape or X.device != self.device:
+                raise ValueError(f"expected frames of shape (B, {', '.join(map(str, self.input_shape))}) on device {self.device}, "
+                                 f"got {X.shape} on device {X.device}")
+            src, dt = C.c_void_p(X.ptr), _DTYPES[np.dtype(X.dtype)]
+            flags |= _lib.TH_PREDICT_IN_DEVICE
+        else:
+            X, dt = self._host_frames(X)
+            src = X.ctypes.data
+        n = X.shape[0]
+        if d_out is None:
+            out = np.empty((n, self.logits_width if logits else self.n_classes), dtype=np.float32)
+            dst = out.ctypes.data
+        else:
+            out, dst = None, C.c_void_p(d_out)
+            flags |= _lib.TH_PREDICT_OUT_DEVICE
+        ticket = C.c_int(-1)
+        _lib.check(self._lib.th_predict_async(self._h, src, dt, n, dst, flags, C.byref(ticket)))
+        return PendingPrediction(self, ticket.value, X, out)        # X is held until result(): the copy reads it
+
     def _predict_async_host(self, X, logits: bool = False) -> "PendingPrediction":
         """Queue ``X`` (copy to the device, kernels, copy of the probabilities back) and return at once; the
         returned handle's ``result()`` blocks until that batch is done and gives the float32 [B, n_classes] array.
@@ -118,60 +145,20 @@ class HipFrameModel:
         next batch, format the previous one) then runs under the GPU's work — reference predict.py:125-155 is strictly
         sequential.  ``X`` is held by the handle until ``result()``; batches built in ``pinned_empty`` memory are
         fetched by the DMA engine without blocking this call."""
-        X = np.asarray(X)
-        if X.ndim != 5 or tuple(X.shape[1:]) != self.input_shape:
-            raise ValueError(f"expected frames of shape (B, {', '.join(map(str, self.input_shape))}), got {X.shape}")
-        dt = _DTYPES.get(X.dtype)
-        if dt is None:
-            X = X.astype(np.float32)
-            dt = _lib.TH_F32
-        X = np.ascontiguousarray(X)
-        n = X.shape[0]
-        out = np.empty((n, self.logits_width if logits else self.n_classes), dtype=np.float32)
-        ticket = C.c_int(-1)
-        _lib.check(self._lib.th_predict_async(self._h, X.ctypes.data, dt, n, out.ctypes.data,
-                                              _lib.TH_PREDICT_LOGITS if logits else 0, C.byref(ticket)))
-        return PendingPrediction(self, ticket.value, X, out)
+        return self._submit(X, None, logits)
 
     def predict_async_device(self, X, d_out: int) -> "PendingPrediction":
         """As predict_async, but the probability rows are left in device memory at address ``d_out`` (this model's
         device, room for len(X) * n_classes floats) — e.g. a shard buffer that th_comm_gather_rows sends over xGMI.
-        ``result()`` returns None once the rows are there."""
+        ``result()`` returns None once the rows are there.  DeviceFrames (GPU-inflated .hdf5 batches) are read where they are."""
         if isinstance(X, SparseFrames):
             return self._predict_async_sparse(X, d_out)
-        if isinstance(X, DeviceFrames):          # frames on the device already (GPU-inflated .hdf5 batches): nothing is copied
-            if tuple(X.shape[1:]) != self.input_shape or X.device != self.device:
-                raise ValueError(f"device frames of shape {X.shape} on device {X.device} do not fit this model")
-            ticket = C.c_int(-1)
-            _lib.check(self._lib.th_predict_async(self._h, C.c_void_p(X.ptr), _DTYPES[np.dtype(X.dtype)], X.shape[0], C.c_void_p(d_out),
-                                                  _lib.TH_PREDICT_OUT_DEVICE | _lib.TH_PREDICT_IN_DEVICE, C.byref(ticket)))
-            return PendingPrediction(self, ticket.value, X, None)
-        X = np.asarray(X)
-        if X.ndim != 5 or tuple(X.shape[1:]) != self.input_shape:
-            raise ValueError(f"expected frames of shape (B, {', '.join(map(str, self.input_shape))}), got {X.shape}")
-        dt = _DTYPES.get(X.dtype)
-        if dt is None:
-            X = X.astype(np.float32)
-            dt = _lib.TH_F32
-        X = np.ascontiguousarray(X)
-        ticket = C.c_int(-1)
-        _lib.check(self._lib.th_predict_async(self._h, X.ctypes.data, dt, X.shape[0], C.c_void_p(d_out),
-                                              _lib.TH_PREDICT_OUT_DEVICE, C.byref(ticket)))
-        return PendingPrediction(self, ticket.value, X, None)
+        return self._submit(X, d_out, False)
 
     def predict_async_frames_on_device(self, frames: "DeviceFrames", logits: bool = False) -> "PendingPrediction":
         """As predict_async for a batch that is in this device's memory already (DeviceFrames, e.g. from
         design_utils.utils.load_batch_device: frames inflated on the GPU): no host->device copy at all."""
-        if tuple(frames.shape[1:]) != self.input_shape:
-            raise ValueError(f"expected frames of shape (B, {', '.join(map(str, self.input_shape))}), got {frames.shape}")
-        if frames.device != self.device:
-            raise ValueError(f"frames live on device {frames.device}, the model on {self.device}")
-        n = frames.shape[0]
-        out = np.empty((n, self.logits_width if logits else self.n_classes), dtype=np.float32)
-        ticket = C.c_int(-1)
-        _lib.check(self._lib.th_predict_async(self._h, C.c_void_p(frames.ptr), _DTYPES[np.dtype(frames.dtype)], n, out.ctypes.data,
-                                              _lib.TH_PREDICT_IN_DEVICE | (_lib.TH_PREDICT_LOGITS if logits else 0), C.byref(ticket)))
-        return PendingPrediction(self, ticket.value, frames, out)
+        return self._submit(frames, None, logits)
 
     @property
     def logits_width(self) -> int:
@@ -394,11 +381,19 @@ class SparseFrames:
         return cls(bits, rank, flat[mask], frames.shape[1:])
 
 
-class BlobRing:
-    """Page-locked byte buffers for sparse batches between a memory-mapped pack and th_predict_sparse_async — StagingRing's
-    counterpart for variable-size blobs: a slot grows (and is re-registered) when a batch does not fit."""
+class _PinnedRing:
+    """Slots of page-locked host memory between a memory-mapped dataset and the GPU.  ``stage(X)`` takes the next free slot (it
+    waits for one), has the subclass fill it and returns (staged batch, slot); the caller gives the slot back with
+    ``release(slot)`` once the prediction that read it has completed.  A batch the ring does not take comes back as (X, None).
 
-    def __init__(self, slots: int, threads: int = 8):
+    A slot is ordinary memory made resident by its first fill (the copy threads fault it in side by side) and page-locked
+    afterwards by registering it, 5 ms per 227 MB — hipHostMalloc of the same slot takes 45 ms.  If registration fails (no
+    device, limits) the ring is switched off: staging through pageable memory would only add a copy.
+
+    A subclass supplies ``_capacity(X)`` — None when this batch does not go through the ring, else (bytes the batch needs, bytes
+    to give a slot that has fewer) — and ``_fill(block, X)``, which builds the batch in the slot's bytes and returns its staged form."""
+
+    def __init__(self, slots: int, threads: int, thread_name: str):
         import queue
         from concurrent.futures import ThreadPoolExecutor
         self._lib = _lib.load()
@@ -408,104 +403,37 @@ class BlobRing:
         for i in range(slots):
             self._free.put(i)
         self._threads = max(1, int(threads))
-        self._pool = ThreadPoolExecutor(max_workers=self._threads, thread_name_prefix="stage_sparse")
+        self._pool = ThreadPoolExecutor(max_workers=self._threads, thread_name_prefix=thread_name)
         self.enabled = True
 
-    def stage(self, X: SparseFrames):
-        if not self.enabled or len(X) == 0:
+    def stage(self, X):
+        want = self._capacity(X) if self.enabled else None
+        if want is None:
             return X, None
-        need = X.blob_bytes
+        need, room = want
         slot = self._free.get()
         try:
             a = self._arrays[slot]
             if a is None or a.nbytes < need:
-                if a is not None and self._pinned[slot]:
-                    self._lib.th_host_unregister(C.c_void_p(a.ctypes.data))
-                    self._pinned[slot] = False
-                raw = np.empty(need + need // 8 + 4096 + 16, np.uint8)
-                off = (-raw.ctypes.data) % 16
-                a = self._arrays[slot] = raw[off:]
-            blob = X.blob(out=a, pool=self._pool, threads=self._threads)
+                self._unpin(slot)
+                raw = np.empty(room + 16, np.uint8)
+                a = self._arrays[slot] = raw[(-raw.ctypes.data) % 16:]
+            staged = self._fill(a, X)
             if not self._pinned[slot]:
                 if self._lib.th_host_register(C.c_void_p(a.ctypes.data), a.nbytes) != 0:
-                    self.enabled = False
+                    self.enabled = False            # hand out the caller's batches from here on
                     self._free.put(slot)
                     return X, None
                 self._pinned[slot] = True
-            return X.staged(blob), slot
+            return staged, slot
         except BaseException:
             self._free.put(slot)
             raise
 
-    def release(self, slot) -> None:
-        if slot is not None:
-            self._free.put(slot)
-
-    def close(self) -> None:
-        if self._pool is None:
-            return
-        self._pool.shutdown(wait=True)
-        self._pool = None
-        for i, a in enumerate(self._arrays):
-            if a is not None and self._pinned[i]:
-                self._lib.th_host_unregister(C.c_void_p(a.ctypes.data))
-                self._pinned[i] = False
-        self._arrays = [None] * len(self._arrays)
-        self.enabled = False
-
-
-class StagingRing:
-    """A ring of page-locked host buffers between a memory-mapped dataset and th_predict_async (no reference counterpart: the
-    reference hands Keras freshly built NumPy batches, utils.py:487-530).  ``stage(rows)`` copies the rows into the next free
-    slot with a few threads (NumPy copies release the interpreter lock) and returns (staged array, slot); the caller gives the
-    slot back with ``release(slot)`` once the prediction that read it has completed.
-
-    Why: a host->device copy straight from never-touched mapped pages runs at 165-177 k float32 frames/s on this box (the
-    driver pins every new page on its way), from the same pages a second time or from page-locked memory at 238-248 k =
-    the PCIe rate (tools/exp_h2d_pack.py).  A slot is ordinary memory made resident by its first fill (the copy threads fault it
-    in side by side) and page-locked afterwards with th_host_register, 5 ms per 227 MB — hipHostMalloc of the same slot takes
-    45 ms.  If registration fails (no device, limits) the ring is switched off: ``stage`` returns (rows, None)."""
-
-    def __init__(self, slots: int, rows: int, frame_shape, dtype, threads: int = 8):
-        import queue
-        from concurrent.futures import ThreadPoolExecutor
-        self._lib = _lib.load()
-        self._shape = (int(rows),) + tuple(int(d) for d in frame_shape)
-        self._dtype = np.dtype(dtype)
-        self._arrays = [None] * slots
-        self._pinned = [False] * slots
-        self._free = queue.SimpleQueue()
-        for i in range(slots):
-            self._free.put(i)
-        self._threads = max(1, int(threads))
-        self._pool = ThreadPoolExecutor(max_workers=self._threads, thread_name_prefix="stage_frames")
-        self.enabled = True
-
-    def stage(self, rows: np.ndarray):
-        n = len(rows)
-        if not self.enabled or n == 0 or n > self._shape[0] or rows.dtype != self._dtype or tuple(rows.shape[1:]) != self._shape[1:]:
-            return rows, None
-        slot = self._free.get()
-        try:
-            a = self._arrays[slot]
-            if a is None:
-                a = self._arrays[slot] = np.empty(self._shape, self._dtype)
-            dst = a[:n]
-            cuts = [n * i // self._threads for i in range(self._threads + 1)]
-            jobs = [self._pool.submit(np.copyto, dst[lo:hi], rows[lo:hi]) for lo, hi in zip(cuts[:-1], cuts[1:]) if hi > lo]
-            for j in jobs:
-                j.result()
-            if not self._pinned[slot]:
-                if self._lib.th_host_register(C.c_void_p(a.ctypes.data), a.nbytes) != 0:
-                    # staging through pageable memory would only add a copy: hand out the caller's rows from here on
-                    self.enabled = False
-                    self._free.put(slot)
-                    return rows, None
-                self._pinned[slot] = True
-            return dst, slot
-        except BaseException:
-            self._free.put(slot)
-            raise
+    def _unpin(self, slot) -> None:
+        if self._pinned[slot]:
+            self._lib.th_host_unregister(C.c_void_p(self._arrays[slot].ctypes.data))
+            self._pinned[slot] = False
 
     def release(self, slot) -> None:
         if slot is not None:
@@ -517,12 +445,56 @@ class StagingRing:
             return
         self._pool.shutdown(wait=True)
         self._pool = None
-        for i, a in enumerate(self._arrays):
-            if a is not None and self._pinned[i]:
-                self._lib.th_host_unregister(C.c_void_p(a.ctypes.data))
-                self._pinned[i] = False
+        for slot in range(len(self._arrays)):
+            self._unpin(slot)
         self._arrays = [None] * len(self._arrays)
         self.enabled = False
+
+
+class BlobRing(_PinnedRing):
+    """Page-locked byte buffers for sparse batches between a memory-mapped pack and th_predict_sparse_async — StagingRing's
+    counterpart for variable-size blobs: a slot grows (and is re-registered) when a batch does not fit."""
+
+    def __init__(self, slots: int, threads: int = 8):
+        super().__init__(slots, threads, "stage_sparse")
+
+    def _capacity(self, X: SparseFrames):
+        need = X.blob_bytes
+        return (need, need + need // 8 + 4096) if len(X) else None
+
+    def _fill(self, block, X: SparseFrames):
+        return X.staged(X.blob(out=block, pool=self._pool, threads=self._threads))
+
+
+class StagingRing(_PinnedRing):
+    """A ring of page-locked host buffers between a memory-mapped dataset and th_predict_async (no reference counterpart: the
+    reference hands Keras freshly built NumPy batches, utils.py:487-530).  ``stage(rows)`` copies the rows into the next free
+    slot with a few threads (NumPy copies release the interpreter lock).
+
+    Why: a host->device copy straight from never-touched mapped pages runs at 165-177 k float32 frames/s on this box (the
+    driver pins every new page on its way), from the same pages a second time or from page-locked memory at 238-248 k =
+    the PCIe rate (tools/exp_h2d_pack.py)."""
+
+    def __init__(self, slots: int, rows: int, frame_shape, dtype, threads: int = 8):
+        super().__init__(slots, threads, "stage_frames")
+        self._shape = (int(rows),) + tuple(int(d) for d in frame_shape)
+        self._dtype = np.dtype(dtype)
+        self._nbytes = int(np.prod(self._shape)) * self._dtype.itemsize
+
+    def _capacity(self, rows: np.ndarray):
+        n = len(rows)
+        if n == 0 or n > self._shape[0] or rows.dtype != self._dtype or tuple(rows.shape[1:]) != self._shape[1:]:
+            return None
+        return self._nbytes, self._nbytes
+
+    def _fill(self, block, rows: np.ndarray):
+        n = len(rows)
+        dst = block[:self._nbytes].view(self._dtype).reshape(self._shape)[:n]
+        cuts = [n * i // self._threads for i in range(self._threads + 1)]
+        jobs = [self._pool.submit(np.copyto, dst[lo:hi], rows[lo:hi]) for lo, hi in zip(cuts[:-1], cuts[1:]) if hi > lo]
+        for j in jobs:
+            j.result()
+        return dst
 
 
 def pinned_empty(shape, dtype=np.float32):
