@@ -63,6 +63,7 @@ SWEEP = [
     ((7, 7, 7), 6, 16, 5, "same", None, "relu", 2),             # 5x5x5 kernel (125 taps)
     ((8, 6, 7), 12, 40, (3, 1, 3), "same", None, "elu", 3),     # anisotropic kernel
     ((2, 2, 2), 96, 16, 3, "same", None, "none", 17),           # tiny volume (DenseCPD block 3)
+    ((4, 4, 4), 24, 20, 3, "same", "max", "elu_bn", 3),         # Cout 17..20 + pool: not the side-channel conv_n16 -> k_conv_mfma, pooled
 ]
 
 
@@ -90,6 +91,10 @@ def test_fused_conv_block_per_element(gpu, shape, cin, cout, k, padding, pool, p
     frames = _frames(n, shape, cin, seed=n)
     labels = _check(cfg, weights, frames)
     assert any("conv_" in l for l in labels), labels               # an MFMA kernel ran, not the direct fallback
+    # the last SWEEP row, (4, 4, 4) 24 -> 20 with a max-pool: conv_n16 is tried first per pool value, its side-channel variant does
+    # not pool, so the layer must stay on k_conv_mfma WITH its pool (and not lose the pool to land on conv_n16)
+    if k == 3 and cin > 8 and 16 < cout <= 20 and pool == "max":
+        assert any("k_conv_mfma<" in l and "pool1" in l for l in labels), labels
     _check(cfg, weights, frames, flags=_lib.TH_LOAD_NO_MFMA)        # and the generic path agrees too
     _check(cfg, weights, frames, chunk=2)                           # ragged chunks
 

@@ -71,10 +71,7 @@ struct ThKnobs {
     int first_int = 1;         // TH_FIRST_INT: uint8 / bool frames on the one-piece form of conv_first_b3 (0: the general six-product kernel)
     int no_pool_first = 0;     // TH_NO_POOL_FIRST: act / BN before the max-pool even when the chain is monotone
     int no_tail_fuse = 0;      // TH_NO_TAIL_FUSE: keep GAP / Dense / Softmax as separate launches
-    int conv_nogeo = 0, n16_nogeo = 0, conv_noxc = 0, conv_notail = 0, conv_nozmajor = 0, conv_nocompact = 0, conv_nopw = 0;
-    int conv_bmode = 0;        // TH_CONV_BMODE: 1 dbuf, 2 stream8, 3 no16
-    int n16_resident = 0;
-    int pw_nopipe = 0, pw_noepi = 0;
+    int conv_notail = 0, n16_resident = 0;
     int wf_resident = 0, wf_noblk = 0;
     long long wino_piece = 0;
     int wino_b3var = 2, wino_nomid = 0;
@@ -184,20 +181,16 @@ struct ConvMfmaPlan {
     int FB = 1, ZB = 0, nzb = 1;  // frames / conv z-planes per workgroup, z bricks per frame
     int Zp = 0, Hp = 0, Wp = 0;   // staged (haloed) brick extent
     int rows_pf = 0;              // GEMM rows per frame-brick (multiple of 32)
-    int bres = 0;                 // all taps' weights resident in LDS (3: the k_conv_n16 weight ring)
-    int ncu = 0;                  // CUs of the model's device: the persistent kernels (k_conv_n16, k_conv_first_b3) size their grid by it
     size_t lds_bytes = 0;
     size_t tab_off = 0;           // byte offset of the row tables inside the LDS allocation
     size_t wpk_floats = 0;        // size of the prepacked weight image
     double exec_flops = 0;        // MFMA FLOPs actually issued per frame
-    int first_wino = 0;           // first-layer kernel only: F(2,3) along x (k_conv_first_w), rows are x pairs
-    double own_flops = 0;         // first_wino: the algorithm's own multiply-adds x 2 per frame (4 points per x pair and (dz, dy) tap)
     int geo = 0;                  // > 0: the kernel instantiation with Hp = Wp = geo at compile time (tap offsets as immediates)
-    const ThKnobs* knobs = nullptr;   // the owning model's A/B knobs (launch-time ones: resident, ...)
+    const ThKnobs* knobs = nullptr;   // the owning model's A/B knobs
     std::string label;
 };
 // choose a tiling for this convolution; returns false when the MFMA kernel does not apply
-// (stride/dilation != 1, nothing fits in LDS, ...)
+// (dilation != 1, nothing fits in LDS, ...)
 bool conv_mfma_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool,
                     const ThKnobs& kn, ConvMfmaPlan* plan);
 // a narrower instantiation for the last Cout block of a layer planned on 128-column blocks (see conv_mfma.hip); on success
@@ -209,6 +202,26 @@ void conv_mfma_pack_weights(const ConvMfmaPlan& p, const ConvGeom& g, int Cin, i
                             float* dst);
 int launch_conv_mfma(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, TView out, ConvGeom g, int Cin,
                      int Cout, const float* wpk, const float* bias, PreOp pre, PostOps post);
+
+// ---- the 16-wide brick kernel (conv_n16.hip): 3x3x3, stride 1, Cin > 8, Cout <= 16, or 17..20 unpooled ----
+struct ConvN16Plan {
+    int variant = -1, xc = 0;     // 0: one 8-wave workgroup per CU, 1: two 4-wave ones, 2: as 1 with output channels 16..16+xc-1 on 4x4x1 MFMA blocks
+    int pool = 0;                 // 0 none, 1 max 2x2x2, 2 avg 2x2x2
+    int FB = 1, ZB = 0, nzb = 1;  // frames / conv z-planes per workgroup trip, z slabs per frame
+    int Zp = 0, Hp = 0, Wp = 0;   // staged (haloed) extent
+    int Dc = 0, Hc = 0, Wc = 0;   // conv-output extent that is computed (even-trimmed when pooled)
+    int rows_pf = 0, nchunks = 0; // GEMM rows per frame (multiple of 16), 16-channel input chunks
+    int geo = 0;                  // > 0: the instantiation with Hp = Wp = geo at compile time
+    int ncu = 0;                  // CUs of the model's device: the persistent grid is sized by it
+    size_t lds_bytes = 0, wpk_floats = 0;
+    double exec_flops = 0;        // MFMA FLOPs issued per frame (16 columns)
+    const ThKnobs* knobs = nullptr;   // launch-time ones: TH_N16_RESIDENT
+    std::string label;
+};
+bool conv_n16_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvN16Plan* plan);
+void conv_n16_pack_weights(const ConvN16Plan& p, int Cin, int Cout, const float* w_keras, float* dst);
+int launch_conv_n16(hipStream_t s, int64_t n, const ConvN16Plan& p, TView in, TView out, ConvGeom g, int Cin, int Cout, const float* wpk,
+                    const float* bias, PreOp pre, PostOps post);
 
 // ---- Cook-Toom / Winograd convolution for 3x3x3 'same' layers on 5^3 volumes (conv_wino.hip) ----
 struct ConvWinoPlan {
@@ -279,20 +292,36 @@ constexpr int kSpMaxWords = 4096;             // words of bitmap per frame held 
 int launch_sparse_expand(hipStream_t s, int64_t n, const uint32_t* bits, const uint64_t* vidx, const float* values, float* out, int E, int W);
 
 // ---- first-layer convolution (conv_first.hip): Cin <= 8, Cout <= 32, 3x3x3, reads the caller's frames ----
-std::string conv_first_label(const ConvMfmaPlan& p, int Cin, const PostOps& post);
+struct ConvFirstPlan {
+    int nnb = 0;                  // passes of 32 output channels
+    int pool = 0;                 // 0 none, 1 max 2x2x2, 2 avg 2x2x2
+    int Dc = 0, Hc = 0, Wc = 0;   // conv-output extent that is computed (even-trimmed when pooled)
+    int ZB = 0, nzb = 1;          // conv z-planes per workgroup, z bricks per frame
+    int Zp = 0, Hp = 0, Wp = 0;   // staged (haloed) brick extent
+    int rows_pf = 0;              // GEMM rows per brick (multiple of 32)
+    int first_wino = 0;           // F(2,3) along x (k_conv_first_w), rows are x pairs
+    int ncu = 0;                  // CUs of the model's device: k_conv_first_b3 is persistent and sizes its grid by it
+    size_t lds_bytes = 0, tab_off = 0;   // tab_off: byte offset of the row tables inside the LDS allocation
+    size_t wpk_floats = 0;        // one 32-column pass
+    double exec_flops = 0;        // MFMA FLOPs actually issued per frame
+    double own_flops = 0;         // first_wino: the algorithm's own multiply-adds x 2 per frame (4 points per x pair and (dz, dy) tap)
+    const ThKnobs* knobs = nullptr;
+    std::string label;
+};
+std::string conv_first_label(const ConvFirstPlan& p, int Cin, const PostOps& post);
 bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& out_conv, const ConvGeom& g, int Cout, int pool,
-                     const ThKnobs& kn, ConvMfmaPlan* plan);
+                     const ThKnobs& kn, ConvFirstPlan* plan);
 void conv_first_pack_weights(int Cin, int Cout, const float* w_keras, float* dst);
 void conv_first_w_pack_weights(int Cin, int Cout, const float* w_keras, float* dst);    // plans with first_wino set
-int launch_conv_first(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const void* frames, int dtype, int Din, int Hin,
+int launch_conv_first(hipStream_t s, int64_t n, const ConvFirstPlan& p, const void* frames, int dtype, int Din, int Hin,
                       int Win, int Cin, TView out, ConvGeom g, int Cout, const float* wpk, const float* bias, PostOps post);
 // the same layer on the bf16 pipe with split operands (conv_first_b3.hip): 21^3 x (5..6) frames, 'same', max-pool before a monotone chain
-bool conv_first_b3_ok(const ConvMfmaPlan& p, int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, const PostOps& post);
+bool conv_first_b3_ok(const ConvFirstPlan& p, int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, const PostOps& post);
 size_t conv_first_b3_wpk_floats();
 double conv_first_b3_exec_flops();
 std::string conv_first_b3_label(int nnb);
 void conv_first_b3_pack_weights(int Cin, int Cout, const float* w_keras, float* dst);
-int launch_conv_first_b3(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const void* frames, int dtype, int Cin, TView out, int Cout,
+int launch_conv_first_b3(hipStream_t s, int64_t n, const ConvFirstPlan& p, const void* frames, int dtype, int Cin, TView out, int Cout,
                          const float* wpk, const float* bias, PostOps post);
 
 // 5x5x5 'same' convolution on the model input, <= 8 channels -> <= 16 filters, 2^3 max-pool behind it (conv_first5.hip): ProDCoNN's stem
@@ -304,11 +333,20 @@ void conv_first5_pack_weights(int Cin, int Cout, const float* w_keras, float* ds
 int launch_conv_first5(hipStream_t s, int64_t n, const ThKnobs* knobs, int ncu, const void* frames, int dtype, int Cin, TView out, int Cout,
                        const float* wpk, const float* bias, PostOps post);
 
-// ---- pointwise (1x1x1) streaming convolution (conv_pointwise.hip); plan.cfg in [300, 309) ----
-bool conv_pw_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvMfmaPlan* plan);
-void conv_pw_pack_weights(const ConvMfmaPlan& p, int Cin, int Cout, const float* w_keras, float* dst);
-std::string conv_pw_label(const ConvMfmaPlan& p, bool out_blk, const PostOps& post);
-int launch_conv_pw(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, TView out, int Cin, int Cout, const float* wpk,
+// ---- pointwise (1x1x1) streaming convolution (conv_pointwise.hip) ----
+struct ConvPwPlan {
+    int kmi = -1, nti = -1;       // which instantiation: index of the K8 bound (4, 8, 16) and of the 32-column tile count (1, 2, 4)
+    int K8 = 0;                   // 8-channel input slots (Cin rounded up)
+    int pool = 0;                 // 0 none, 1 max 2x2x2, 2 avg 2x2x2
+    size_t lds_bytes = 0, wpk_floats = 0;
+    double exec_flops = 0;        // MFMA FLOPs issued per frame
+    const ThKnobs* knobs = nullptr;
+    std::string label;
+};
+bool conv_pw_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvPwPlan* plan);
+void conv_pw_pack_weights(const ConvPwPlan& p, int Cin, int Cout, const float* w_keras, float* dst);
+std::string conv_pw_label(const ConvPwPlan& p, bool out_blk, const PostOps& post);
+int launch_conv_pw(hipStream_t s, int64_t n, const ConvPwPlan& p, TView in, TView out, int Cin, int Cout, const float* wpk,
                    const float* bias, PreOp pre, PostOps post);
 
 // ---- sampler (sampler.hip) -----------------------------------------------------------------

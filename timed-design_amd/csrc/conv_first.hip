@@ -577,7 +577,7 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 }  // namespace
 
 bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& oc, const ConvGeom& g, int Cout, int pool,
-                     const ThKnobs& kn, ConvMfmaPlan* p) {
+                     const ThKnobs& kn, ConvFirstPlan* p) {
     if (g.kd != 3 || g.kh != 3 || g.kw != 3) return false;
     if (g.sd != 1 || g.sh != 1 || g.sw != 1 || g.dd != 1 || g.dh != 1 || g.dw != 1) return false;
     // the kernel holds the weights of 32 output channels in registers; a wider first layer (33 .. 128 filters) runs it once per
@@ -585,8 +585,7 @@ bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& oc, const 
     // where the generic brick kernel, which the layer would otherwise fall to, takes 11 — tools/plan_report.py, timed_w40)
     if (Cin < 1 || Cin > 8 || Cout > 128) return false;
     if (pool && (oc.D < 2 || oc.H < 2 || oc.W < 2)) return false;
-    p->cfg = 100;  // marks the first-layer kernel
-    p->CI = 8; p->CS = 8; p->BN = 32; p->nnb = (Cout + 31) / 32; p->nchunks = 1; p->pool = pool; p->bres = 1; p->FB = 1;
+    p->nnb = (Cout + 31) / 32; p->pool = pool;
     p->Dc = pool ? (oc.D / 2) * 2 : oc.D;
     p->Hc = pool ? (oc.H / 2) * 2 : oc.H;
     p->Wc = pool ? (oc.W / 2) * 2 : oc.W;
@@ -594,8 +593,7 @@ bool conv_first_plan(int Din, int Hin, int Win, int Cin, const TView& oc, const 
     p->Wp = p->Wc + 2;
     // F(2,3) along x (k_conv_first_w): 'same' padding, an even number of computed columns; rows are x pairs
     p->knobs = &kn;
-    const bool no_wino = !kn.first_wino;
-    const bool wino = !no_wino && g.pz == 1 && g.py == 1 && g.px == 1 && p->Wc % 2 == 0 && p->Wc >= 2;
+    const bool wino = kn.first_wino && g.pz == 1 && g.py == 1 && g.px == 1 && p->Wc % 2 == 0 && p->Wc >= 2;
     p->first_wino = wino ? 1 : 0;
     auto rows_for = [&](int zb) {
         if (wino) return round_up(pool ? 4 * ((zb / 2) * (p->Hc / 2) * (p->Wc / 2)) : zb * p->Hc * (p->Wc / 2), 32);
@@ -666,13 +664,13 @@ void conv_first_w_pack_weights(int Cin, int Cout, const float* w, float* dst) {
 namespace {
 // the instantiation a plan runs with a given epilogue chain: pool-first (PMODE 3) when the chain is monotone, the
 // compile-time geometry when there is one for this frame size
-FirstKernel pick_first_kernel(const ConvMfmaPlan& p, int nst, const PostOps& post, int* pmode, int* geo) {
+FirstKernel pick_first_kernel(const ConvFirstPlan& p, int nst, const PostOps& post, int* pmode, int* geo) {
     const ThKnobs& kn = th_knobs_of(p.knobs);
     const bool no_pool_first = kn.no_pool_first != 0;   // A/B comparisons and tests
     *pmode = (p.pool == 1 && post.monotone && !no_pool_first) ? 3 : p.pool;
     *geo = 0;
     FirstKernel k = p.first_wino ? kFirstWKernels[nst - 1][*pmode] : kFirstKernels[nst - 1][*pmode];
-    if (p.Hp == p.Wp && p.Hc == p.Hp - 2 && p.Wc == p.Wp - 2 && !kn.conv_nogeo) {
+    if (p.Hp == p.Wp && p.Hc == p.Hp - 2 && p.Wc == p.Wp - 2) {
         if (p.first_wino) {
             for (const FirstGeo& ge : kFirstWGeo)
                 if (ge.nst == nst && ge.pmode == *pmode && ge.geo == p.Hp) { k = ge.k; *geo = ge.geo; }
@@ -686,7 +684,7 @@ FirstKernel pick_first_kernel(const ConvMfmaPlan& p, int nst, const PostOps& pos
 }  // namespace
 
 // the plan's label with the kernel that launch_conv_first will actually run for this epilogue chain (as rocprofv3 prints it)
-std::string conv_first_label(const ConvMfmaPlan& p, int Cin, const PostOps& post) {
+std::string conv_first_label(const ConvFirstPlan& p, int Cin, const PostOps& post) {
     int pmode, geo;
     pick_first_kernel(p, (Cin + 1) / 2, post, &pmode, &geo);
     std::string l = p.label;
@@ -700,7 +698,7 @@ std::string conv_first_label(const ConvMfmaPlan& p, int Cin, const PostOps& post
     return l;
 }
 
-int launch_conv_first(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const void* frames, int dtype, int Din, int Hin,
+int launch_conv_first(hipStream_t s, int64_t n, const ConvFirstPlan& p, const void* frames, int dtype, int Din, int Hin,
                       int Win, int Cin, TView out, ConvGeom g, int Cout, const float* wpk, const float* bias, PostOps post) {
     ConvFirstArgs a;
     std::memset(&a, 0, sizeof a);

@@ -474,7 +474,7 @@ const FirstB3Dbg kFirstB3Dbg[] = {{1, k_conv_first_b3<1>}, {2, k_conv_first_b3<2
 }  // namespace
 
 // does the split kernel serve this first layer (the planner asks before it packs the weights)?
-bool conv_first_b3_ok(const ConvMfmaPlan& p, int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, const PostOps& post) {
+bool conv_first_b3_ok(const ConvFirstPlan& p, int Din, int Hin, int Win, int Cin, int Cout, const ConvGeom& g, const PostOps& post) {
     const ThKnobs& kn = th_knobs_of(p.knobs);
     if (!kn.first_split || !p.first_wino || kn.no_pool_first) return false;
     if (Din != kFD || Hin != kFD || Win != kFD || (Cin != 5 && Cin != 6) || Cout < 1 || Cout > 32) return false;
@@ -529,7 +529,7 @@ void conv_first_b3_pack_weights(int Cin, int Cout, const float* w, float* dst_f)
         }
 }
 
-int launch_conv_first_b3(hipStream_t s, int64_t n, const ConvMfmaPlan& p, const void* frames, int dtype, int Cin, TView out, int Cout,
+int launch_conv_first_b3(hipStream_t s, int64_t n, const ConvFirstPlan& p, const void* frames, int dtype, int Cin, TView out, int Cout,
                          const float* wpk, const float* bias, PostOps post) {
     if (n <= 0) return TH_OK;
     ConvFirstB3Args a;

@@ -59,10 +59,7 @@ constexpr size_t kPwLdsLimit = 64 * 1024;
 
 }  // namespace
 
-// plan encoding (ConvMfmaPlan): cfg = 300 + 3*kmax_index + nt_index, CI = 8*K8 (padded Cin), BN = 32*NT, bres = 4
-bool conv_pw_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvMfmaPlan* p) {
-    if (kn.conv_nopw) return false;                             // A/B comparisons against conv_mfma
-    p->knobs = &kn;
+bool conv_pw_plan(const TView&, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvPwPlan* p) {
     if (g.kd != 1 || g.kh != 1 || g.kw != 1) return false;
     if (g.sd != 1 || g.sh != 1 || g.sw != 1 || g.dd != 1 || g.dh != 1 || g.dw != 1) return false;
     if (pool && (oc.D < 2 || oc.H < 2 || oc.W < 2)) return false;
@@ -73,33 +70,27 @@ bool conv_pw_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin, 
     const int kmi = K8 <= 4 ? 0 : (K8 <= 8 ? 1 : 2);
     const size_t lds = (size_t)K8 * NT * 64 * 16 + (size_t)K8 * 8 * 2 * 4;
     if (lds > kPwLdsLimit) return false;
-    p->cfg = 300 + 3 * kmi + nti;
-    p->CI = K8 * 8; p->CS = 0; p->BN = 32 * NT; p->nnb = 1; p->nchunks = 1; p->pool = pool; p->bres = 4;
-    p->Dc = pool ? (oc.D / 2) * 2 : oc.D;
-    p->Hc = pool ? (oc.H / 2) * 2 : oc.H;
-    p->Wc = pool ? (oc.W / 2) * 2 : oc.W;
-    p->FB = 1; p->ZB = p->Dc; p->nzb = 1; p->Zp = p->Dc; p->Hp = p->Hc; p->Wp = p->Wc;
-    p->rows_pf = p->Dc * p->Hc * p->Wc;
+    p->knobs = &kn;
+    p->kmi = kmi; p->nti = nti; p->K8 = K8; p->pool = pool;
     p->lds_bytes = lds;
-    p->tab_off = 0;
     p->wpk_floats = (size_t)K8 * NT * 256;
-    p->exec_flops = 2.0 * (double)p->rows_pf * (double)(32 * NT) * (double)(K8 * 8);
+    const int rows_pf = pool ? (oc.D / 2) * 2 * ((oc.H / 2) * 2) * ((oc.W / 2) * 2) : oc.D * oc.H * oc.W;   // even-trimmed when pooled
+    p->exec_flops = 2.0 * (double)rows_pf * (double)(32 * NT) * (double)(K8 * 8);
     char buf[224];
     // the pipelined kernel when the layer allows it (launch_conv_pw falls back to k_conv_pw for unaligned or > 4 GiB views)
-    const bool pipe = !kn.pw_nopipe && kPw2[kmi][nti][pool] && Cin % 8 == 0 && K8 <= kPwKmax[kmi];
+    const bool pipe = kPw2[kmi][nti][pool] && Cin % 8 == 0 && K8 <= kPwKmax[kmi];
     const int kmax = (pipe && K8 > 8 && K8 <= 12 && nti <= 1) ? 12 : kPwKmax[kmi];
     snprintf(buf, sizeof buf, "conv_pw<k%d,nt%d,pool%d> K8=%d lds%zuK (streaming 1x1x1, weights in LDS%s) [k_conv_pw%s<%d,%d,%d%s>]",
              kmax, NT, pool, K8, lds / 1024, pipe ? ", next tile prefetched, buffer addressing" : "", pipe ? "2" : "",
              kmax, NT, pool, pipe ? ",0,0" : "");
     p->label = buf;
-    (void)in;
     return true;
 }
 
 // Keras [1,1,1,Cin,Cout] -> fragment order [kk][ntile][h][j][q] with ci = kk*8 + 4h + q, co = ntile*32 + j
-void conv_pw_pack_weights(const ConvMfmaPlan& p, int Cin, int Cout, const float* w, float* dst) {
+void conv_pw_pack_weights(const ConvPwPlan& p, int Cin, int Cout, const float* w, float* dst) {
     std::memset(dst, 0, p.wpk_floats * sizeof(float));
-    const int K8 = p.CI / 8, NT = p.BN / 32;
+    const int K8 = p.K8, NT = kPwNt[p.nti];
     for (int kk = 0; kk < K8; ++kk)
         for (int nt = 0; nt < NT; ++nt) {
             float* frag = dst + ((size_t)kk * NT + nt) * 256;
@@ -116,31 +107,29 @@ void conv_pw_pack_weights(const ConvMfmaPlan& p, int Cin, int Cout, const float*
 }
 
 // the "BN-affine -> ReLU" instantiation exists for this plan and chain (launch_conv_pw and the step label agree through this)
-static bool pw_relu_epi(const ConvMfmaPlan& p, int K8, const PostOps& post) {
-    const int idx = p.cfg - 300, kmi = idx / 3, nti = idx % 3;
+static bool pw_relu_epi(const ConvPwPlan& p, const PostOps& post) {
     const bool relu_chain = post.n == 2 && post.type[0] == POP_AFFINE && post.type[1] == POP_ACT && post.act[1] == ACT_RELU;
-    if (p.pool != 0 || !relu_chain || th_knobs_of(p.knobs).pw_noepi) return false;
-    return conv_pw2_extra(0, 2, kmi, nti, (K8 > 8 && K8 <= 12 && nti <= 1) ? 1 : 0) != nullptr;
+    if (p.pool != 0 || !relu_chain) return false;
+    return conv_pw2_extra(0, 2, p.kmi, p.nti, (p.K8 > 8 && p.K8 <= 12 && p.nti <= 1) ? 1 : 0) != nullptr;
 }
 // the plan's label with the template arguments of the instantiation that runs (chunk-blocked output, epilogue chain)
-std::string conv_pw_label(const ConvMfmaPlan& p, bool out_blk, const PostOps& post) {
+std::string conv_pw_label(const ConvPwPlan& p, bool out_blk, const PostOps& post) {
     std::string l = p.label;
     const size_t k = l.rfind(",0,0>]");
     if (k == std::string::npos) return l;
     l[k + 1] = out_blk ? '1' : '0';
-    l[k + 3] = pw_relu_epi(p, p.CI / 8, post) ? '2' : '0';
+    l[k + 3] = pw_relu_epi(p, post) ? '2' : '0';
     return l;
 }
 
-int launch_conv_pw(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, TView out, int Cin, int Cout, const float* wpk,
+int launch_conv_pw(hipStream_t s, int64_t n, const ConvPwPlan& p, TView in, TView out, int Cin, int Cout, const float* wpk,
                    const float* bias, PreOp pre, PostOps post) {
-    const int idx = p.cfg - 300;
-    if (idx < 0 || idx >= 9 || p.bres != 4) TH_FAIL(TH_EINVAL, "conv_pw: bad plan");
-    const int kmi = idx / 3, nti = idx % 3;
+    const int kmi = p.kmi, nti = p.nti;
+    if (kmi < 0 || kmi >= 3 || nti < 0 || nti >= 3) TH_FAIL(TH_EINVAL, "conv_pw: bad plan");
     if (n <= 0) return TH_OK;
     ConvPwArgs a;
     std::memset(&a, 0, sizeof a);
-    a.in = in.p; a.in_fs = in.fs; a.in_cs = in.cs; a.in_coff = in.coff; a.Cin = Cin; a.K8 = p.CI / 8;
+    a.in = in.p; a.in_fs = in.fs; a.in_cs = in.cs; a.in_coff = in.coff; a.Cin = Cin; a.K8 = p.K8;
     a.vec_ok = (in.cs % 4 == 0 && in.coff % 4 == 0 && in.fs % 4 == 0 && ((uintptr_t)in.p % 16) == 0) ? 1 : 0;
     a.V = in.D * in.H * in.W; a.H = in.H; a.W = in.W;
     a.in_dense = (in.fs == (int64_t)a.V * in.cs) ? 1 : 0;
@@ -162,14 +151,13 @@ int launch_conv_pw(hipStream_t s, int64_t n, const ConvMfmaPlan& p, TView in, TV
     // the pipelined buffer-addressing kernel when the views allow it (see k_conv_pw2)
     const int64_t in_span = ((n - 1) * in.fs + (int64_t)(a.V - 1) * in.cs + in.coff + Cin) * 4;
     const int64_t out_span = ((n - 1) * out.fs + (out_v - 1) * out.cs + out.coff + Cout) * 4;
-    const bool no_pw2 = th_knobs_of(p.knobs).pw_nopipe != 0;   // A/B comparisons
-    if (!no_pw2 && kPw2[kmi][nti][p.pool] && a.vec_ok && Cin % 8 == 0 && a.K8 <= kPwKmax[kmi] && in_span < 0xfffffff0LL &&
+    if (kPw2[kmi][nti][p.pool] && a.vec_ok && Cin % 8 == 0 && a.K8 <= kPwKmax[kmi] && in_span < 0xfffffff0LL &&
         out_span < 0xfffffff0LL) {
         a.in_bytes = (unsigned)in_span; a.out_bytes = (unsigned)out_span;
         k = (a.K8 > 8 && a.K8 <= 12 && nti <= 1) ? kPw2_12[nti][p.pool] : kPw2[kmi][nti][p.pool];
         const int slot12 = (a.K8 > 8 && a.K8 <= 12 && nti <= 1) ? 1 : 0;
         if (out.blk) k = (PwKernel)conv_pw2_extra(1, 0, kmi, nti, slot12);
-        if (pw_relu_epi(p, a.K8, post)) {
+        if (pw_relu_epi(p, post)) {
             const int bk = out.blk ? 1 : 0;
             PwKernel kr = (PwKernel)conv_pw2_extra(bk, 2, kmi, nti, slot12);
             if (kr) k = kr;

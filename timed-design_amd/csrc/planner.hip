@@ -226,14 +226,17 @@ struct ConvFusion {
 };
 
 // the kernel family that runs a Conv3D / Dense layer
-enum class Kern { None, Wino, WfSplit, Wf, First5, First, Pointwise, Gl, Mfma, Direct, DenseGemm, Dense };
+enum class Kern { None, Wino, WfSplit, Wf, First5, First, Pointwise, Gl, N16, Mfma, Direct, DenseGemm, Dense };
 
 // one Conv3D / Dense step: what it absorbs, and the kernel that runs it — decided once, read by every pass after the decision
 struct LayerPlan {
     ConvFusion f;
     ConvGeom g{};                 // Conv3D: the geometry on the input it reads (f.src)
-    Kern family = Kern::None;     // fusion pass: First5 / First / Pointwise / Mfma with `mp` (None: no MFMA-family plan)
-    ConvMfmaPlan mp;
+    Kern family = Kern::None;     // fusion pass: First5 / First / Pointwise / N16 / Mfma, each with its own plan (None: no MFMA-family plan)
+    ConvFirstPlan fp;             // First
+    ConvPwPlan pw;                // Pointwise
+    ConvN16Plan np;               // N16
+    ConvMfmaPlan mp;              // Mfma
     bool wf = false;              // conv_wfused serves the layer, with `wfp`
     ConvWfPlan wfp;
     Kern kind = Kern::None;       // what runs it (choose_kernel)
@@ -251,7 +254,7 @@ struct LayerPlan {
 // the minimal-filtering and split-operand forms: what the load-time guard checks against a direct plan
 bool fast_form(const LayerPlan& L) {
     return L.kind == Kern::Wino || L.kind == Kern::Wf || L.kind == Kern::WfSplit || L.kind == Kern::First5 ||
-           (L.kind == Kern::First && (L.mp.first_wino || L.b3));
+           (L.kind == Kern::First && (L.fp.first_wino || L.b3));
 }
 
 struct Planner {
@@ -329,8 +332,8 @@ ConvFusion fuse_chain(const Planner& P, int i) {
     return f;
 }
 
-// the MFMA family of convolution i, in this order: first5 -> first -> pointwise -> mfma.  The fused pool is dropped when the
-// kernel that takes the layer cannot pool it.
+// the MFMA family of convolution i, in this order: first5 -> first -> pointwise -> n16 -> mfma.  The brick kernels (n16, mfma) are
+// tried with the fused pool first and then without it; the pool is dropped when the kernel that takes the layer cannot pool it.
 void choose_family(const Planner& P, int i, LayerPlan& L) {
     ConvFusion& f = L.f;
     const Node& n = P.N[i];
@@ -339,23 +342,18 @@ void choose_family(const Planner& P, int i, LayerPlan& L) {
     const TView iv = shape_of(src), ov = shape_of(n);
     const int pool = P.pool_mode(f);
     const bool stem = P.use_mfma && P.fuse && f.src == P.m->input_node && f.pre.empty();
-    ConvMfmaPlan& mp = L.mp;
     Kern& k = L.family;
-    if (stem && pool == 1 && conv_first5_ok(src.D, src.H, src.W, src.C, n.C, g, 1, P.kn)) {
-        // ProDCoNN's 5x5x5 stem: direct form on the bf16 pipe, input split once at staging (conv_first5.hip)
-        mp = ConvMfmaPlan();
-        mp.pool = 1; mp.nnb = 1;
-        mp.knobs = &P.kn;
-        mp.exec_flops = conv_first5_exec_flops();
-        mp.label = conv_first5_label();
-        k = Kern::First5;
-    }
-    if (k == Kern::None && stem && conv_first_plan(src.D, src.H, src.W, src.C, ov, g, n.C, pool, P.kn, &mp)) k = Kern::First;
-    if (k == Kern::None && P.use_mfma && g.kd * g.kh * g.kw == 1 && conv_pw_plan(iv, ov, g, src.C, n.C, pool, P.kn, &mp))
+    // ProDCoNN's 5x5x5 stem: direct form on the bf16 pipe, input split once at staging (conv_first5.hip)
+    if (stem && pool == 1 && conv_first5_ok(src.D, src.H, src.W, src.C, n.C, g, 1, P.kn)) k = Kern::First5;
+    if (k == Kern::None && stem && conv_first_plan(src.D, src.H, src.W, src.C, ov, g, n.C, pool, P.kn, &L.fp)) k = Kern::First;
+    if (k == Kern::None && P.use_mfma && g.kd * g.kh * g.kw == 1 && conv_pw_plan(iv, ov, g, src.C, n.C, pool, P.kn, &L.pw))
         k = Kern::Pointwise;
+    auto brick = [&](int pl) {    // one pool value: the 16-wide kernel's variants, then the 32-wide kernel's configurations
+        return conv_n16_plan(iv, ov, g, src.C, n.C, pl, P.kn, &L.np) ? Kern::N16 : conv_mfma_plan(iv, ov, g, src.C, n.C, pl, P.kn, &L.mp) ? Kern::Mfma : Kern::None;
+    };
     if (k == Kern::None && P.use_mfma) {
-        if (f.pool >= 0 && conv_mfma_plan(iv, ov, g, src.C, n.C, pool, P.kn, &mp)) k = Kern::Mfma;
-        else if (conv_mfma_plan(iv, ov, g, src.C, n.C, 0, P.kn, &mp)) { k = Kern::Mfma; f.pool = -1; }
+        if (f.pool >= 0) k = brick(pool);
+        if (k == Kern::None && (k = brick(0)) != Kern::None) f.pool = -1;
     }
     if (k == Kern::None) f.pool = -1;
 }
@@ -471,7 +469,7 @@ void blocked_pass(Planner& P) {
         if (nprod != 1) continue;
         const LayerPlan& pp = P.layers.at(prod);
         if (pp.wf) continue;                                        // (the producer itself runs on conv_wfused: channels-last stores only)
-        if (!((pp.family == Kern::Pointwise && pp.mp.pool == 0) || (pp.family == Kern::First && pp.mp.nnb == 1))) continue;
+        if (!((pp.family == Kern::Pointwise && pp.pw.pool == 0) || (pp.family == Kern::First && pp.fp.nnb == 1))) continue;
         bool shared = false;                                        // nobody else may alias the buffer (Flatten / Identity views)
         for (int k = 0; k < (int)N.size(); ++k) if (k != src && N[k].buf == sn.buf && N[k].materialised) shared = true;
         if (shared) continue;
@@ -497,7 +495,7 @@ int build_epilogue(Planner& P, int i, LayerPlan& L) {
     return TH_OK;
 }
 
-// in this order: wino -> wfs -> wf -> first5 -> first -> pointwise -> gl -> mfma -> direct.  After the chunk-blocked pass: the
+// in this order: wino -> wfs -> wf -> first5 -> first -> pointwise -> gl -> n16 / mfma -> direct.  After the chunk-blocked pass: the
 // wfs and gl kernels read `blk`.
 int choose_kernel(Planner& P, int i, LayerPlan& L) {
     th_model* m = P.m;
@@ -519,17 +517,18 @@ int choose_kernel(Planner& P, int i, LayerPlan& L) {
     else if (L.wf) L.kind = Kern::Wf;
     else if (L.family == Kern::First5 || L.family == Kern::First || L.family == Kern::Pointwise) L.kind = L.family;
     else if (conv_gl_wanted(P.kn.conv_gl, g, n.D * n.H * n.W) && L.f.pool < 0 && !sn.blk && !P.N[L.f.last].blk &&
-             (L.family == Kern::None || L.mp.bres != 3) &&          // (the 16-wide kernel keeps its layers: 42 against 62 us on DenseCPD's 2^3 ones)
+             L.family != Kern::N16 &&                               // (the 16-wide kernel keeps its layers: 42 against 62 us on DenseCPD's 2^3 ones)
              conv_gl_ok(Cin, Cout, sn.cs, sn.coff, (int64_t)m->bufs[sn.buf].floats_per_frame))
         L.kind = Kern::Gl;
+    else if (L.family == Kern::N16) L.kind = Kern::N16;
     else if (L.family == Kern::Mfma) {
         L.kind = Kern::Mfma;
         // heterogeneous Cout blocks: the last, mostly empty 128-column block on a narrower instantiation
         L.tailed = conv_mfma_plan_tail(iv, ov, g, Cin, Cout, L.mp.pool, L.mp, P.kn, &L.tp, &L.cout_main);
     } else L.kind = Kern::Direct;
     // the aposteriori case (21^3 frames, pool before a monotone chain) runs on the bf16 pipe with split operands
-    if (L.kind == Kern::First) L.b3 = conv_first_b3_ok(L.mp, sn.D, sn.H, sn.W, Cin, std::min(Cout, 32), g, L.po);
-    L.mp.ncu = L.tp.ncu = L.wfp.ncu = L.sp.ncu = m->ncu;
+    if (L.kind == Kern::First) L.b3 = conv_first_b3_ok(L.fp, sn.D, sn.H, sn.W, Cin, std::min(Cout, 32), g, L.po);
+    L.fp.ncu = L.np.ncu = L.wfp.ncu = L.sp.ncu = m->ncu;
     return TH_OK;
 }
 
@@ -655,13 +654,13 @@ int emit_wf(const ConvArgs& c, const LayerPlan& L, Step& st) {
     return TH_OK;
 }
 
-int emit_first5(const ConvArgs& c, const LayerPlan& L, Step& st) {
+int emit_first5(const Planner& P, const ConvArgs& c, Step& st) {
     float* dw;
     if (int rc = upload_packed(c.M, conv_first5_wpk_floats(), [&](float* d) { conv_first5_pack_weights(c.Cin, c.Cout, c.hw, d); }, &dw))
         return rc;
-    st.exec_flops = L.mp.exec_flops;
-    st.label = conv_label(c, L.mp.label, false, false);
-    const ThKnobs* kn = L.mp.knobs;
+    st.exec_flops = conv_first5_exec_flops();
+    st.label = conv_label(c, conv_first5_label(), false, false);
+    const ThKnobs* kn = &P.kn;
     st.run = [=](hipStream_t s, int64_t cnt) {
         return launch_conv_first5(s, cnt, kn, c.M->ncu, c.M->cur_in, c.M->cur_dtype, c.Cin, c.out(), c.Cout, dw, c.bias, c.po);
     };
@@ -671,24 +670,24 @@ int emit_first5(const ConvArgs& c, const LayerPlan& L, Step& st) {
 // the first layer on the caller's frames (conv_first.hip, conv_first_b3.hip): one launch per block of 32 output channels, each
 // with its own weight columns, bias and per-channel epilogue vectors
 int emit_first(const ConvArgs& c, const LayerPlan& L, Step& st) {
-    const ConvMfmaPlan mp = L.mp;
+    const ConvFirstPlan fp = L.fp;
     const bool b3 = L.b3;
-    if (mp.first_wino) {
+    if (fp.first_wino) {
         st.direct_flops = st.flops;
-        st.flops = mp.own_flops;
+        st.flops = fp.own_flops;
     }
-    st.exec_flops = b3 ? conv_first_b3_exec_flops() * mp.nnb : mp.exec_flops;
-    st.label = conv_label(c, b3 ? conv_first_b3_label(mp.nnb) : conv_first_label(mp, c.Cin, c.po), false, c.node(c.dst).blk);
-    if (mp.nnb > 1) st.label = label_note(st.label, (" x" + std::to_string(mp.nnb) + " passes of 32 columns").c_str());
+    st.exec_flops = b3 ? conv_first_b3_exec_flops() * fp.nnb : fp.exec_flops;
+    st.label = conv_label(c, b3 ? conv_first_b3_label(fp.nnb) : conv_first_label(fp, c.Cin, c.po), false, c.node(c.dst).blk);
+    if (fp.nnb > 1) st.label = label_note(st.label, (" x" + std::to_string(fp.nnb) + " passes of 32 columns").c_str());
     struct Pass { int c0, cn; float* dw; const float* bias; PostOps po; };
     std::vector<Pass> passes;
     const size_t ktaps = (size_t)c.g.kd * c.g.kh * c.g.kw * c.Cin;
     for (int c0 = 0; c0 < c.Cout; c0 += 32) {
         Pass ps{c0, std::min(32, c.Cout - c0), nullptr, c.bias ? c.bias + c0 : nullptr, post_from(c.po, c0)};
         const std::vector<float> wcol = weight_columns(c.hw, ktaps, c.Cout, c0, ps.cn);
-        const int rc = upload_packed(c.M, b3 ? conv_first_b3_wpk_floats() : mp.wpk_floats, [&](float* d) {
+        const int rc = upload_packed(c.M, b3 ? conv_first_b3_wpk_floats() : fp.wpk_floats, [&](float* d) {
             if (b3) conv_first_b3_pack_weights(c.Cin, ps.cn, wcol.data(), d);
-            else if (mp.first_wino) conv_first_w_pack_weights(c.Cin, ps.cn, wcol.data(), d);
+            else if (fp.first_wino) conv_first_w_pack_weights(c.Cin, ps.cn, wcol.data(), d);
             else conv_first_pack_weights(c.Cin, ps.cn, wcol.data(), d);
         }, &ps.dw);
         if (rc) return rc;
@@ -701,8 +700,8 @@ int emit_first(const ConvArgs& c, const LayerPlan& L, Step& st) {
             TView ov = c.out();
             if (passes.size() > 1) { ov.coff += ps.c0; ov.C = ps.cn; }
             th_model* M = c.M;
-            const int r = b3 ? launch_conv_first_b3(s, cnt, mp, M->cur_in, M->cur_dtype, c.Cin, ov, ps.cn, ps.dw, ps.bias, ps.po)
-                             : launch_conv_first(s, cnt, mp, M->cur_in, M->cur_dtype, iD, iH, iW, c.Cin, ov, c.g, ps.cn, ps.dw, ps.bias, ps.po);
+            const int r = b3 ? launch_conv_first_b3(s, cnt, fp, M->cur_in, M->cur_dtype, c.Cin, ov, ps.cn, ps.dw, ps.bias, ps.po)
+                             : launch_conv_first(s, cnt, fp, M->cur_in, M->cur_dtype, iD, iH, iW, c.Cin, ov, c.g, ps.cn, ps.dw, ps.bias, ps.po);
             if (r) return r;
         }
         return (int)TH_OK;
@@ -711,13 +710,13 @@ int emit_first(const ConvArgs& c, const LayerPlan& L, Step& st) {
 }
 
 int emit_pointwise(const ConvArgs& c, const LayerPlan& L, Step& st) {
-    const ConvMfmaPlan mp = L.mp;
+    const ConvPwPlan pw = L.pw;
     float* dw;
-    if (int rc = upload_packed(c.M, mp.wpk_floats, [&](float* d) { conv_pw_pack_weights(mp, c.Cin, c.Cout, c.hw, d); }, &dw)) return rc;
+    if (int rc = upload_packed(c.M, pw.wpk_floats, [&](float* d) { conv_pw_pack_weights(pw, c.Cin, c.Cout, c.hw, d); }, &dw)) return rc;
     const bool blk = c.node(c.dst).blk != 0;
-    st.exec_flops = mp.exec_flops;
-    st.label = conv_label(c, conv_pw_label(mp, blk, c.po), false, blk);
-    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_pw(s, cnt, mp, c.in(), c.out(), c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
+    st.exec_flops = pw.exec_flops;
+    st.label = conv_label(c, conv_pw_label(pw, blk, c.po), false, blk);
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_pw(s, cnt, pw, c.in(), c.out(), c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
     return TH_OK;
 }
 
@@ -730,6 +729,16 @@ int emit_gl(const ConvArgs& c, Step& st) {
     st.exec_flops = conv_gl_exec_flops(c.g, c.Cin, c.Cout, n.D * n.H * n.W);
     st.label = conv_label(c, conv_gl_label(c.Cout), false, false);
     st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_gl(s, cnt, c.in(), c.out(), c.g, c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
+    return TH_OK;
+}
+
+int emit_n16(const ConvArgs& c, const LayerPlan& L, Step& st) {
+    const ConvN16Plan np = L.np;
+    float* dw;
+    if (int rc = upload_packed(c.M, np.wpk_floats, [&](float* d) { conv_n16_pack_weights(np, c.Cin, c.Cout, c.hw, d); }, &dw)) return rc;
+    st.exec_flops = np.exec_flops;
+    st.label = conv_label(c, np.label, false, false);
+    st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_n16(s, cnt, np, c.in(), c.out(), c.g, c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
     return TH_OK;
 }
 
@@ -852,10 +861,11 @@ int emit_layer(Planner& P, int i) {
         case Kern::Wino: return emit_wino(P, c, L, st);
         case Kern::WfSplit: rc = emit_wfs(c, L, st); break;
         case Kern::Wf: rc = emit_wf(c, L, st); break;
-        case Kern::First5: rc = emit_first5(c, L, st); break;
+        case Kern::First5: rc = emit_first5(P, c, st); break;
         case Kern::First: rc = emit_first(c, L, st); break;
         case Kern::Pointwise: rc = emit_pointwise(c, L, st); break;
         case Kern::Gl: rc = emit_gl(c, st); break;
+        case Kern::N16: rc = emit_n16(c, L, st); break;
         case Kern::Mfma: rc = emit_mfma(c, L, st); break;
         case Kern::DenseGemm: case Kern::Dense: rc = emit_dense(c, L, st); break;
         default: rc = emit_direct(c, st); break;

@@ -59,21 +59,9 @@ int th_knobs_read(ThKnobs* k) {
     KNOCK("TH_FIRST_DBG", first_dbg);
     flag("TH_NO_POOL_FIRST", &k->no_pool_first);
     flag("TH_NO_TAIL_FUSE", &k->no_tail_fuse);
-    flag("TH_CONV_NOGEO", &k->conv_nogeo);
-    flag("TH_N16_NOGEO", &k->n16_nogeo);
-    flag("TH_CONV_NOXC", &k->conv_noxc);
     flag("TH_CONV_NOTAIL", &k->conv_notail);
-    flag("TH_CONV_NOZMAJOR", &k->conv_nozmajor);
-    flag("TH_CONV_NOCOMPACT", &k->conv_nocompact);
-    flag("TH_CONV_NOPW", &k->conv_nopw);
-    if (const char* e = getenv("TH_CONV_BMODE")) {
-        k->conv_bmode = !std::strcmp(e, "dbuf") ? 1 : !std::strcmp(e, "stream8") ? 2 : !std::strcmp(e, "no16") ? 3 : 0;
-        if (k->conv_bmode) note("TH_CONV_BMODE", e);
-    }
     KNOCK("TH_CONV_DBG", conv_dbg);
     num("TH_N16_RESIDENT", &k->n16_resident, 0, 1 << 20);
-    flag("TH_PW_NOPIPE", &k->pw_nopipe);
-    flag("TH_PW_NOEPI", &k->pw_noepi);
     KNOCK("TH_PW_DBG", pw_dbg);
     num("TH_WF_RESIDENT", &k->wf_resident, 0, 1 << 20);
     KNOCK("TH_WF_DBG", wf_dbg);
