@@ -611,6 +611,31 @@ int th_voxelise(int device, const float* atoms_xyz, const int32_t* atom_channel,
                 const float* frames_rt, int64_t n_res, int voxels_per_side, float frame_edge_length, int n_channels, int gaussian,
                 void* out, int out_on_device);
 
+/* ---- batched voxeliser: the frames of many structures in one launch, with an optional weight per atom (the charge / polarity
+ * channel of timed_hip/voxeliser.py spec item 8).
+ *     *** PARITY UNPINNED AGAINST AMPAL AND APOSTERIORI ***  (the specification is this project's own reading, see voxeliser.py)
+ * Arrays as for th_voxelise, the atoms of all structures one after the other: structure s owns the atoms
+ * [atom_offsets[s], atom_offsets[s + 1]) (atom_offsets [n_structures + 1], from 0 to n_atoms, never decreasing; a structure may
+ * be empty or have no frame).  frames_rt [n_frames, 12] and frame_structure [n_frames]: frame r sees the atoms of structure
+ * frame_structure[r] and no others; frames may be listed in any order.  atom_weight [n_atoms] or NULL (every atom counts 1).
+ * Rule: with unit weights frame r is what th_voxelise gives for that structure's atoms alone and that frames_rt row.  A Gaussian
+ * contribution is acc = acc + weight * (w / total): the quotient, then the product, each rounded to float32, then added, in atom
+ * order, no fused multiply-add.  Multiplying by 1.0f is exact, so with atom_weight NULL or all ones the frames equal th_voxelise's
+ * byte for byte, Gaussian and boolean alike.  A frame's bytes do not depend on where the frame or its structure sits in the
+ * batch or on what else the batch holds (no float atomics).  At most 2048 encodable atoms inside one frame: beyond, the whole
+ * call fails with TH_EUNSUP and the count in th_last_error.
+ * The call works on a non-blocking stream of its own and waits for that stream only (no device-wide synchronise): a loader thread
+ * does not wait for kernels other threads have queued.  out: host memory, or device memory of `device` when out_on_device (nothing
+ * is downloaded then).  kernel_ms (may be NULL): the kernel's time from events on the call's stream.
+ * Refused before any HIP call, th_last_error naming th_voxelise_batch — TH_EINVAL: a NULL array where a count is non-zero;
+ * atom_offsets[0] != 0, a decreasing offset, a last offset != n_atoms; a frame_structure entry outside [0, n_structures);
+ * atom_weight with gaussian == 0 (boolean frames carry no weight); a weight that is not finite; voxels_per_side even or > 511;
+ * frame_edge_length not positive.  TH_EUNSUP: n_channels outside 1..8.  n_frames == 0: TH_OK, nothing is launched. */
+int th_voxelise_batch(int device, const float* atoms_xyz, const int32_t* atom_channel, const float* atom_sigma,
+                      const float* atom_weight, int64_t n_atoms, const int64_t* atom_offsets, int64_t n_structures,
+                      const float* frames_rt, const int32_t* frame_structure, int64_t n_frames, int voxels_per_side,
+                      float frame_edge_length, int n_channels, int gaussian, void* out, int out_on_device, double* kernel_ms);
+
 /* ---- multi-GPU reassembly (no reference counterpart: the reference is single-process) ----- */
 /* one process per GPU; rank 0 creates the id and ships it to the others out of band */
 #define TH_COMM_ID_BYTES 128

@@ -20,6 +20,26 @@ _N_CHI = {"ARG": 4, "ASN": 2, "ASP": 2, "CYS": 1, "GLN": 3, "GLU": 3, "HIS": 2, 
           "PHE": 2, "PRO": 2, "SER": 1, "THR": 1, "TRP": 2, "TYR": 2, "VAL": 1}
 side_chain_dihedrals = {res: list(range(n)) for res, n in _N_CHI.items()}
 
+# ---- residue properties (the sixth frame channel of TIMED_charge / TIMED_polar; timed_hip/voxeliser.py spec item 8) ----
+# PARITY UNPINNED AGAINST AMPAL AND APOSTERIORI.  The reference takes ``residue_charge`` and ``polarity_Zimmerman`` from
+# ampal.amino_acids (reference design_utils/utils.py:10-15), which is not available here.  What the reference itself pins is
+# only {0: "A", 1: "K", -1: "D"} (utils.py:86) and the polarity threshold of 20 (utils.py:95); both tables below agree with it.
+# Whether ampal's charge table puts C and Y at -1 is a recollection, not a checked fact.
+residue_charge = {
+    "A": 0, "C": -1, "D": -1, "E": -1, "F": 0, "G": 0, "H": +1, "I": 0, "K": +1, "L": 0, "M": 0, "N": 0, "P": 0, "Q": 0,
+    "R": +1, "S": 0, "T": 0, "V": 0, "W": 0, "Y": -1,
+}
+# Zimmerman, Eliezer & Simha (1968) polarity scale as commonly tabulated; only "below 20 or not" is ever used
+polarity_Zimmerman = {
+    "A": 0.0, "C": 1.48, "D": 49.7, "E": 49.9, "F": 0.35, "G": 0.0, "H": 51.6, "I": 0.13, "K": 49.5, "L": 0.13, "M": 1.43,
+    "N": 3.38, "P": 1.58, "Q": 3.53, "R": 52.0, "S": 1.67, "T": 1.66, "V": 0.13, "W": 2.1, "Y": 1.61,
+}
+POLARITY_THRESHOLD = 20                  # reference utils.py:95: polar (1) iff polarity_Zimmerman >= 20
+residue_polarity = {r: (0 if v < POLARITY_THRESHOLD else 1) for r, v in polarity_Zimmerman.items()}     # polar: R, D, E, H, K
+PROPERTIES = ("polarity", "charge")      # the reference's accepted_properties (utils.py:82)
+PROPERTY_VALUES = {"polarity": (0, 1), "charge": (-1, 0, 1)}
+PROPERTY_TABLE = {"polarity": residue_polarity, "charge": residue_charge}
+
 # Stand-in for aposteriori.config.UNCOMMON_RESIDUE_DICT (used at reference utils.py:381-385 to map a
 # non-standard residue label onto its parent amino acid while the dataset map is built).  aposteriori
 # 2.4.0 is not in the reference tree nor in this image, so its exact table is UNPINNED; this one holds

@@ -6,8 +6,9 @@ Written from scratch: HDF5 access goes through h5py when importable and the bund
 reader otherwise, amino-acid tables are local (design_utils/amino_acids.py), and the per-residue
 Python loops of the reference are vectorised where that cannot change the output.
 
-Out of scope here (UI helpers of the reference module): PDB property editing, BLOSUM lookup,
-alphanumeric map codes, rm_tree.
+Out of scope here (UI helpers of the reference module): BLOSUM lookup, alphanumeric map codes, rm_tree.  The
+reference's PDB property editing (modify_pdb_with_input_property) is replaced by property maps: ``open_structure_set``
+and timed_hip/voxeliser.py spec item 8; ``convert_seq_to_property`` keeps its name.
 """
 from __future__ import annotations
 
@@ -97,6 +98,10 @@ def create_flat_dataset_map(
     if framepack.is_pack(frame_dataset):  # packed dataset: the map was fixed when the pack was written
         fmap = [tuple(r) for r in _frame_pack(frame_dataset).flat_map.tolist()]     # the cached pack load_batch will use
         return fmap, {r[0] for r in fmap}
+    sset = structure_set_of(frame_dataset)
+    if sset is not None:                  # a folder of structures (or one structure with a property channel): frames are built per batch
+        fmap = [tuple(r) for r in sset.flat_map.tolist() if r[0][:4] not in filter_list]
+        return fmap, {r[0] for r in fmap}
     if framepack.is_structure(frame_dataset):   # a PDB file: voxelised on the GPU (row f-4), one frame per residue
         fmap = [tuple(str(x) for x in r) for r in _structure_pack(frame_dataset).flat_map if r[0][:4] not in filter_list]
         return fmap, {r[0] for r in fmap}
@@ -171,6 +176,9 @@ def flat_dataset_map_array(frame_dataset: Path, filter_list: t.Sequence[str] = (
     from timed_hip import framepack
     if framepack.is_pack(frame_dataset) and not filter_list:
         return _frame_pack(frame_dataset).flat_map
+    sset = None if filter_list or framepack.is_pack(frame_dataset) else structure_set_of(frame_dataset)
+    if sset is not None:
+        return sset.flat_map
     flat, _ = create_flat_dataset_map(frame_dataset, list(filter_list))
     return np.array(flat)
 
@@ -253,6 +261,9 @@ def load_batch(dataset_path: Path, data_point_batch: t.List[t.Tuple], dtype=None
     from timed_hip import framepack
     if framepack.is_pack(dataset_path):  # HDF5-free fast path (SURVEY f-1): memory-mapped rows, no per-residue reads
         return _frame_pack(dataset_path).load_batch(data_point_batch)
+    sset = structure_set_of(dataset_path)
+    if sset is not None:                 # voxelised now, by one th_voxelise_batch call; the frames come back to the host
+        return sset.load_batch(data_point_batch)
     if framepack.is_structure(dataset_path):
         return _structure_pack(dataset_path).load_batch(data_point_batch)
     # the native readers (th_h5_resolve + th_h5_read_chunked_as on host threads) work on the kept h5lite mapping of the file,
@@ -434,7 +445,7 @@ def load_batch_device(dataset_path: Path, data_point_batch, device: int = 0):
     GPU (libtimedhip th_h5_decode_device, one lane per chunk): only the compressed bytes cross PCIe — 8.7x fewer than the float64
     frames — and no host core spends a millisecond per frame in zlib."""
     from timed_hip import _lib, engine, framepack, h5lite
-    if framepack.is_pack(dataset_path) or framepack.is_structure(dataset_path):
+    if framepack.is_pack(dataset_path) or framepack.is_structure(dataset_path) or structure_set_of(dataset_path) is not None:
         return None
     n = len(data_point_batch)
     if n == 0:
@@ -546,6 +557,71 @@ def _frame_pack(path):
     if key not in _PACKS:
         _PACKS[key] = framepack.FramePack(path)
     return _PACKS[key]
+
+
+_SETS: dict = {}         # absolute path -> (what it was opened with, StructureSet): one set at a time
+
+
+def open_structure_set(path, property: t.Optional[str] = None, property_map=None):
+    """The structure set at ``path`` (timed_hip.structureset: a directory of structures, or one structure file when a property
+    channel is asked for), parsed and prepared once and kept until another one is opened.  create_flat_dataset_map,
+    flat_dataset_map_array and load_batch then serve ``path`` from it.  ``property``: None, "polarity" or "charge";
+    ``property_map``: {pdb_code: [ints]}, a list for a single structure, or the path of a JSON file that holds either."""
+    from timed_hip import structureset, voxeliser
+    if isinstance(property_map, (str, os.PathLike)):
+        property_map = voxeliser.read_property_map(property_map)
+    if property is not None:
+        property = property.lower()
+        assert property in voxeliser.PROPERTY_ATOM, f"Property {property} not found among {list(voxeliser.PROPERTY_ATOM)}"
+    if not structureset.is_structure_set(path, property):
+        raise ValueError(f"{path}: not a directory of structures" + ("" if property is None else " nor a structure file"))
+    key = os.path.abspath(os.fspath(path))
+    stamp = (property, repr(property_map), _tree_stamp(key))
+    kept = _SETS.get(key)
+    if kept is None or kept[0] != stamp:
+        _SETS.clear()
+        _SETS[key] = (stamp, structureset.StructureSet(key, property=property, property_map=property_map))
+    return _SETS[key][1]
+
+
+def forget_structure_set(path) -> None:
+    """drop the set open_structure_set keeps for ``path`` (a structure file is then a plain single-file dataset again)"""
+    _SETS.pop(os.path.abspath(os.fspath(path)), None)
+
+
+def _tree_stamp(key):
+    from timed_hip import pdbio
+    return tuple((str(p), os.path.getmtime(p)) for _label, p in pdbio.find_structures([key]))
+
+
+def structure_set_of(path):
+    """the structure set that serves ``path``: the one open_structure_set opened for it, else — for a directory — one without a
+    property channel; None for every other kind of dataset.  (Whether the files changed on disk is looked at by
+    open_structure_set only: this is called for every batch.)"""
+    try:
+        key = os.path.abspath(os.fspath(path))
+    except TypeError:
+        return None
+    kept = _SETS.get(key)
+    if kept is not None:
+        return kept[1]
+    if os.path.isdir(key):
+        return open_structure_set(key)
+    return None
+
+
+def convert_seq_to_property(seq: str, property: str) -> t.List[int]:
+    """reference utils.py:139-169: one integer per letter of ``seq`` — polarity 0 / 1 (Zimmerman polarity below 20 or not; a
+    non-standard letter is 0), charge -1 / 0 / +1 (an unknown letter raises KeyError, as the reference's lookup does).
+    PARITY UNPINNED AGAINST AMPAL AND APOSTERIORI: the tables are design_utils/amino_acids.py's, not ampal's."""
+    from .amino_acids import residue_charge, residue_polarity
+    accepted_properties = ["polarity", "charge"]
+    assert (
+        property.lower() in accepted_properties
+    ), f"Property {property} not found among {accepted_properties}"
+    if property.lower() == "polarity":
+        return [residue_polarity.get(r, 0) for r in seq]
+    return [residue_charge[r] for r in seq]
 
 
 # ---- rotamer codec ------------------------------------------------------------------------------------

@@ -192,6 +192,8 @@ def load_dataset_and_predict(
     gather=None,
     output_analysis: bool = False,
     output_auc: bool = False,
+    property: str = None,
+    property_map=None,
 ) -> (np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray):
     """reference predict.py:28-194 — same leading parameters and return tuple (flat_dataset_map, pdb_to_sequence,
     pdb_to_probability, pdb_to_real_sequence, pdb_to_consensus, pdb_to_consensus_prob).  ``start_batch`` keeps the
@@ -202,8 +204,27 @@ def load_dataset_and_predict(
     row-gather transport from ``timed_hip.distributed``; default: RCCL when WORLD_SIZE > 1) and ``output_analysis``
     (after each model's FASTA, rank 0 writes <model>_analysis.json, <model>_entropy.csv and <model>_per_structure.csv — see
     _write_analysis) and ``output_auc`` (20-class models with a 4-column map: rank 0 also writes <model>_auc.json — see
-    _write_auc; rotamer models are evaluated per class by analyse_rotamers.py)."""
+    _write_auc; rotamer models are evaluated per class by analyse_rotamers.py).
+
+    ``dataset_path`` may be a directory of structures (a *structure set*, timed_hip/structureset.py): every file is parsed once,
+    the frames of each call group are voxelised in HBM by one th_voxelise_batch call on the GPU that predicts the group.
+    ``property`` ("polarity" / "charge") adds the reference's sixth channel (TIMED_polar / TIMED_charge; voxeliser spec item 8,
+    PARITY UNPINNED AGAINST AMPAL AND APOSTERIORI) and also makes a single structure file a set; ``property_map``:
+    {pdb_code: [ints]}, a list for a single structure, or the path of a JSON file with either — one integer per frame in
+    dataset-map order; without it every residue carries the value of its own name."""
     path_to_output = Path(path_to_output)
+    from timed_hip import structureset
+    structure_set = None
+    if property_map is not None and property is None:
+        raise ValueError("a property map needs --property polarity or --property charge")
+    if structureset.is_structure_set(dataset_path, property):
+        if is_consensus:
+            raise ValueError("--is_structure_nmr: a structure set voxelises model 1 of every file only; NMR ensembles go through a single file")
+        structure_set = du.open_structure_set(dataset_path, property=property, property_map=property_map)
+    else:
+        du.forget_structure_set(dataset_path)          # (a file that an earlier call opened with a property)
+    if structure_set is None and property is not None:
+        raise ValueError(f"--property needs structures (a directory or a PDB file), {dataset_path} holds frames that exist already")
     if output_auc and predict_rotamers:
         raise ValueError("--output_auc scores the 20 residue classes; evaluate a rotamer model per class with analyse_rotamers.py")
     n_classes = N_ROTAMER_CLASSES if predict_rotamers else N_RESIDUE_CLASSES
@@ -261,6 +282,11 @@ def load_dataset_and_predict(
                     if h.n_classes != n_classes:
                         raise ValueError(f"{model_path}: the model has {h.n_classes} outputs, predict_rotamers="
                                          f"{predict_rotamers} needs {n_classes}")
+                    shape = getattr(h, "input_shape", None)
+                    if structure_set is not None and shape is not None and tuple(shape) != tuple(structure_set.frame_dims):
+                        raise ValueError(f"{model_path}: the model reads frames of {shape[-1]} channels {tuple(shape)}, the structures are "
+                                         f"voxelised with {structure_set.n_channels} {tuple(structure_set.frame_dims)}"
+                                         + (f" (--property {property} adds the sixth)" if property else " (a 6-channel model needs --property)"))
                 if rank == 0:
                     # <model>.txt depends on the map only: written on the side thread while the GPU works
                     srb = side.submit(du.convert_dataset_map_for_srb, flat_dataset_map, model_name, path_to_output)
@@ -452,7 +478,9 @@ def _predict_sharded(model, gather, rank, world, dataset_path, flat_dataset_map,
 # --frames_per_call are additions of this build.
 CLI_FLAGS = (
     ("--batch_size", dict(type=int, default=12, help="frames per reference batch; also the unit --start_batch-style resumes count in")),
-    ("--path_to_dataset", dict(type=str, help="aposteriori frame dataset (.hdf5) or frame pack")),
+    ("--path_to_dataset", dict(type=str, help="aposteriori frame dataset (.hdf5), frame pack, PDB file, or a directory of PDB files (voxelised on the GPU, group by group)")),
+    ("--property", dict(type=str, default=None, choices=["polarity", "charge"], help="structures only: add the property channel of TIMED_polar / TIMED_charge (6-channel models). PARITY UNPINNED AGAINST AMPAL AND APOSTERIORI")),
+    ("--path_to_property_map", dict(type=str, default=None, help="JSON {pdb_code: [ints]} (or a bare list for one structure): one value per frame in dataset-map order, {0,1} for polarity, {-1,0,1} for charge; default: each residue's own value")),
     ("--path_to_datasetmap", dict(type=str, default="datasetmap.txt", help="flat dataset map (.txt); created when missing")),
     ("--path_to_model", dict(type=str, help="Keras legacy .h5 model or converted .pack")),
     ("--path_to_blacklist", dict(type=str, default=None, help="directory of PDB lists to refuse (training-set structures)")),
@@ -506,7 +534,8 @@ def _main_predict(args, required, devices):
         predict_rotamers=args.predict_rotamers, is_consensus=args.is_structure_nmr,
         path_to_output=Path(args.path_to_output), device=getattr(args, "device", 0), devices=devices,
         frames_per_call=getattr(args, "frames_per_call", None), output_analysis=bool(getattr(args, "output_analysis", False)),
-        output_auc=bool(getattr(args, "output_auc", False)))
+        output_auc=bool(getattr(args, "output_auc", False)), property=getattr(args, "property", None),
+        property_map=getattr(args, "path_to_property_map", None))
 
 
 if __name__ == "__main__":

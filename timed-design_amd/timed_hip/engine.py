@@ -27,6 +27,8 @@ _DTYPES = {
 
 
 class HipFrameModel:
+    takes_device_frames = True      # predict_async reads DeviceFrames where they are (pipeline.GroupLoader asks)
+
     def __init__(self, pack_bytes: bytes, device: int = 0, flags: int = _lib.TH_LOAD_DEFAULT, name: str = "model"):
         self._lib = _lib.load()
         self._h = C.c_void_p()

@@ -52,12 +52,16 @@ def _models_take_sparse(models) -> bool:
 class GroupLoader:
     """``load(k)`` builds the batch of call group k: (frames, labels, release) — ``release`` gives a page-locked staging slot
     back once the prediction that read it has completed (None: nothing was staged).  Any loader thread may call it.  Sources,
-    in this order: a sparse pack's SparseFrames, the GPU inflater's DeviceFrames, the host reader's ndarray / mapped rows."""
+    in this order: a sparse pack's SparseFrames, a structure set's DeviceFrames (voxelised in HBM), the GPU inflater's DeviceFrames,
+    the host reader's ndarray / mapped rows."""
 
     def __init__(self, models, dataset_path, flat_dataset_map, groups, gpu_decode=False):
         self.models, self.dataset_path, self.flat_dataset_map, self.groups = models, dataset_path, flat_dataset_map, groups
-        plain_h5 = not framepack.is_pack(dataset_path) and not framepack.is_structure(dataset_path)
+        # a folder of structures (or one structure with a property channel): the frames of a group are built in HBM
+        self.structure_set = None if framepack.is_pack(dataset_path) else du.structure_set_of(dataset_path)
+        plain_h5 = not framepack.is_pack(dataset_path) and not framepack.is_structure(dataset_path) and self.structure_set is None
         on_device = getattr(models[0], "device", None) is not None
+        self._frames_born_on_device = self.structure_set is not None and all(getattr(m, "takes_device_frames", False) for m in models)
         # a float32 pack with sparse transport files (framepack.sparsify): the loader hands out SparseFrames batches — a tenth of the
         # bytes cross PCIe, the device rebuilds the dense frames (th_predict_sparse_async).  TIMED_SPARSE=0: the dense rows as before
         self.sparse_pack = None
@@ -120,6 +124,10 @@ class GroupLoader:
             span = self.sparse_pack.contiguous_rows(rows)
             if span is not None:
                 return self.sparse_pack.sparse_batch(*span), self.sparse_pack.labels[span[0]:span[1]].astype(float)
+        if self._frames_born_on_device:
+            # ONE th_voxelise_batch call on the GPU that will predict the group: the atoms of the structures these rows touch go
+            # up, the frames are written into a pooled device buffer and never cross PCIe.  The call waits for its own stream only
+            return self.structure_set.device_batch(rows, self.models[k % len(self.models)].device, du._DEVICE_POOL)
         if self.decode_on_gpu:
             # the chunks of this group are inflated ON the GPU that will predict it (th_h5_decode_device) — the frames never
             # exist on the host; a dataset that cannot take the path (other filters, a layout h5lite does not read ...) says so once
@@ -279,6 +287,10 @@ class _RowsOnDevice:
 class _ToDevice:
     """the model facade run_groups drives in a sharded run: the outputs of call after call land in ``d_local`` at the shard row"""
     sparse_ok = True          # predict_async_device reads SparseFrames batches too
+
+    @property
+    def takes_device_frames(self):
+        return getattr(self.model, "takes_device_frames", False)
 
     def __init__(self, model, d_local, width):
         self.model, self.d_local, self.width = model, d_local, width

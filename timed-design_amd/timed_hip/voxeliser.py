@@ -37,6 +37,21 @@ Specification
   7. One frame per residue that has N, CA, C and a standard (or mapped) name; label = one-hot over
      ``standard_amino_acids`` order; dataset-map rows (pdb_code, chain, residue number, label) in file order with
      residues sorted numerically per chain, as create_flat_dataset_map would list them.
+  8. Property channel (``property`` "polarity" or "charge": the sixth channel of the reference's TIMED_polar / TIMED_charge,
+     codecs CNOCBCAP / CNOCBCAQ, reference README.md:91, ui.py:734-746).
+         *** PARITY UNPINNED AGAINST AMPAL AND APOSTERIORI ***  The tables (design_utils/amino_acids.py) stand in for
+         ampal's, which is not available here; where aposteriori puts the property value, and with which width, is this
+         module's own reading like the rest of it.  The reference only pins A -> 0, K -> +1, D -> -1 (utils.py:86).
+     The atom encoder gains a last name, "P" or "Q" (channel 5 with the default encoder: C, N, O, CA, CB, Q).  Every residue
+     that has a CA and whose value v is not 0 contributes ONE extra atom at the CA's coordinates, in the property channel, with
+     carbon's sigma (0.5 x 1.70) and weight v, appended after the residue's own atoms; a value of 0 emits nothing.  A Gaussian
+     contribution of an atom of weight v is v * (w / total), the product rounded to float32 before it is added (item 6 is
+     v = 1).  Property channels need Gaussian frames.  v is the value of the residue's own name (charge: D, E, C, Y -1; K, R, H
+     +1; polarity: R, D, E, H, K 1; everything else 0) unless a PROPERTY MAP says otherwise: one integer per frame of the
+     structure in dataset-map order (item 7), from {0, 1} for polarity and {-1, 0, 1} for charge.  Residues that get no frame
+     always carry their own value.  The map replaces the reference's renaming of residues to ALA / LYS / ASP
+     (modify_pdb_with_input_property, utils.py:60-110): labels keep the native residues, backbone-only frames do not depend on
+     the name.
 """
 from __future__ import annotations
 
@@ -72,20 +87,83 @@ def residue_frame(n: np.ndarray, ca: np.ndarray, c: np.ndarray) -> Optional[np.n
     return np.stack([ex, ey, ez])
 
 
+PROPERTY_ATOM = {"polarity": "P", "charge": "Q"}       # the codec letters of the reference's CNOCBCAP / CNOCBCAQ
+
+
+def property_encoder(property: Optional[str], atom_encoder: Sequence[str] = DEFAULT_ENCODER) -> Tuple[str, ...]:
+    """the atom encoder with the property's name last (spec item 8); unchanged without a property"""
+    if property is None:
+        return tuple(atom_encoder)
+    if property not in PROPERTY_ATOM:
+        raise AssertionError(f"Property {property} not found among {list(PROPERTY_ATOM)}")
+    return tuple(atom_encoder) + (PROPERTY_ATOM[property],)
+
+
+def check_property_map(property: str, values, n_frames: int, name: str) -> np.ndarray:
+    """a property map of one structure as int64 [n_frames]; ValueError naming the structure and the two numbers otherwise"""
+    from design_utils.amino_acids import PROPERTY_VALUES
+    allowed = PROPERTY_VALUES[property]
+    arr = np.asarray(values)
+    if arr.ndim != 1 or arr.shape[0] != n_frames:
+        raise ValueError(f"{name}: the {property} map has {arr.size if arr.ndim == 1 else arr.shape} values, the structure has {n_frames} frames")
+    if arr.size and (arr.dtype.kind not in "iub" or not np.isin(arr, allowed).all()):
+        bad = next(i for i, v in enumerate(arr.tolist()) if v not in allowed or isinstance(v, float))
+        raise ValueError(f"{name}: the {property} map holds {arr[bad]} at frame {bad}; allowed values are {list(allowed)}")
+    return arr.astype(np.int64)
+
+
+def read_property_map(path):
+    """A property map file: a JSON object {pdb_code: [ints]} (structures that are not named keep their native values) or, for a
+    single structure, a bare JSON list.  Returned as it is; prepare_structure_with_property validates the values."""
+    import json
+    with open(path) as f:
+        got = json.load(f)
+    if not isinstance(got, (dict, list)):
+        raise ValueError(f"{path}: a property map is a JSON object {{pdb_code: [ints]}} or a JSON list")
+    return got
+
+
+def map_of(property_map, code: str):
+    """the map of structure ``code`` out of what read_property_map returns (None: native values)"""
+    if isinstance(property_map, dict):
+        return property_map.get(code)
+    return property_map
+
+
 def prepare_structure(model: pdbio.Model, encode_cb: bool = True, atom_encoder: Sequence[str] = DEFAULT_ENCODER,
                       uncommon: Optional[dict] = None):
     """Host-side preparation of one model: (atoms_xyz f32 [n,3], atom_channel i32 [n], atom_sigma f32 [n],
     frames_rt f32 [n_res,12], rows [(chain, number, three-letter label)])."""
-    from design_utils.amino_acids import UNCOMMON_RESIDUE_DICT, standard_amino_acids
+    xyz, ch, sg, _wt, frt, rows = _prepare(model, encode_cb, atom_encoder, uncommon, None, None, "")
+    return xyz, ch, sg, frt, rows
+
+
+def prepare_structure_with_property(model: pdbio.Model, property: Optional[str] = None, property_map=None, encode_cb: bool = True,
+                                    atom_encoder: Sequence[str] = DEFAULT_ENCODER, uncommon: Optional[dict] = None, name: str = "structure"):
+    """prepare_structure with the property atoms of spec item 8: (atoms_xyz, atom_channel, atom_sigma, atom_weight f32 [n],
+    frames_rt, rows).  ``atom_encoder`` is the encoder WITHOUT the property name (it is appended here); ``property_map``: one
+    integer per frame in the order of ``rows``, or None for every residue's own value.  Without a property the weights are all 1."""
+    return _prepare(model, encode_cb, atom_encoder, uncommon, property, property_map, name)
+
+
+def _prepare(model, encode_cb, atom_encoder, uncommon, property, property_map, name):
+    """the one loop behind prepare_structure and prepare_structure_with_property"""
+    from design_utils.amino_acids import PROPERTY_TABLE, UNCOMMON_RESIDUE_DICT, standard_amino_acids
     uncommon = UNCOMMON_RESIDUE_DICT if uncommon is None else uncommon
     standard = set(standard_amino_acids.values())
-    chan = {name: i for i, name in enumerate(atom_encoder)}
+    one_letter = {three: one for one, three in standard_amino_acids.items()}
+    atom_encoder = property_encoder(property, atom_encoder)
+    table = PROPERTY_TABLE[property] if property is not None else None
+    chan = {name_: i for i, name_ in enumerate(atom_encoder)}
     xyz: List[np.ndarray] = []
     ch: List[int] = []
     sg: List[float] = []
+    wt: List[float] = []
+    slot: dict = {}                       # id(residue) -> index of its property atom
     frames: List[np.ndarray] = []
     rows: List[Tuple[str, str, str]] = []
     per_chain: dict = {}
+    framed: list = []                     # the residues that get a frame, in the order of ``rows``
     for res in model.residues:
         label = res.name if res.name in standard else uncommon.get(res.name)
         if label is None or (res.hetero and res.name not in uncommon):
@@ -95,10 +173,15 @@ def prepare_structure(model: pdbio.Model, encode_cb: bool = True, atom_encoder: 
             R = residue_frame(res.atoms["N"], res.atoms["CA"], res.atoms["C"])
         for a in BACKBONE:
             if a in res.atoms and a in chan:
-                xyz.append(res.atoms[a]); ch.append(chan[a]); sg.append(SIGMA_SCALE * VDW_RADIUS[a[0]])
+                xyz.append(res.atoms[a]); ch.append(chan[a]); sg.append(SIGMA_SCALE * VDW_RADIUS[a[0]]); wt.append(1.0)
+        if R is not None and encode_cb and "CB" in chan:
+            xyz.append(res.atoms["CA"] + R.T @ CB_LOCAL); ch.append(chan["CB"]); sg.append(SIGMA_SCALE * VDW_RADIUS["C"]); wt.append(1.0)
+        if table is not None and "CA" in res.atoms:
+            # the residue's own value; a property map overwrites it below, once the frames have their order.  Zeros are dropped there
+            slot[id(res)] = len(xyz)
+            xyz.append(res.atoms["CA"]); ch.append(len(atom_encoder) - 1); sg.append(SIGMA_SCALE * VDW_RADIUS["C"])
+            wt.append(float(table[one_letter[label]]))
         if R is not None:
-            if encode_cb and "CB" in chan:
-                xyz.append(res.atoms["CA"] + R.T @ CB_LOCAL); ch.append(chan["CB"]); sg.append(SIGMA_SCALE * VDW_RADIUS["C"])
             per_chain.setdefault(res.chain, []).append((res, R, label))
     for chain, items in per_chain.items():
         def key(it):
@@ -107,8 +190,16 @@ def prepare_structure(model: pdbio.Model, encode_cb: bool = True, atom_encoder: 
         for res, R, label in sorted(items, key=key):
             frames.append(np.concatenate([R.reshape(9), res.atoms["CA"]]))
             rows.append((chain, res.number, label))
-    return (np.asarray(xyz, dtype=np.float32).reshape(-1, 3), np.asarray(ch, dtype=np.int32), np.asarray(sg, dtype=np.float32),
-            np.asarray(frames, dtype=np.float32).reshape(-1, 12), rows)
+            framed.append(res)
+    xyz_a = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    ch_a, sg_a, wt_a = np.asarray(ch, dtype=np.int32), np.asarray(sg, dtype=np.float32), np.asarray(wt, dtype=np.float32)
+    if table is not None:
+        if property_map is not None:
+            for res, v in zip(framed, check_property_map(property, property_map, len(framed), name).tolist()):
+                wt_a[slot[id(res)]] = v
+        keep = wt_a != 0                  # a value of 0 emits nothing
+        xyz_a, ch_a, sg_a, wt_a = xyz_a[keep], ch_a[keep], sg_a[keep], wt_a[keep]
+    return xyz_a, ch_a, sg_a, wt_a, np.asarray(frames, dtype=np.float32).reshape(-1, 12), rows
 
 
 def voxelise(atoms_xyz, atom_channel, atom_sigma, frames_rt, voxels_per_side: int = 21, frame_edge_length: float = 21.0,
@@ -132,14 +223,53 @@ def voxelise(atoms_xyz, atom_channel, atom_sigma, frames_rt, voxels_per_side: in
     return out
 
 
+def voxelise_batch(atoms_xyz, atom_channel, atom_sigma, atom_weight, atom_offsets, frames_rt, frame_structure, voxels_per_side: int = 21,
+                   frame_edge_length: float = 21.0, n_channels: int = 5, gaussian: bool = True, device: int = 0,
+                   d_out: Optional[int] = None, timing: Optional[dict] = None) -> Optional[np.ndarray]:
+    """The frames of many structures in one launch (th_voxelise_batch): structure s owns the atoms
+    [atom_offsets[s], atom_offsets[s + 1]) of the flat arrays, frame r is built from the atoms of structure frame_structure[r]
+    alone and the row frames_rt[r].  ``atom_weight``: float32 per atom, or None (every atom counts 1; the frames then equal
+    ``voxelise``'s byte for byte).  Returns frames [n_frames, V, V, V, C], or None when ``d_out`` (a device address with room
+    for them) is given.  ``timing``: a dict whose ``kernel_ms`` the call adds to."""
+    lib = _lib.load()
+    xyz = np.ascontiguousarray(atoms_xyz, dtype=np.float32)
+    chn = np.ascontiguousarray(atom_channel, dtype=np.int32)
+    sig = np.ascontiguousarray(atom_sigma, dtype=np.float32)
+    wgt = None if atom_weight is None else np.ascontiguousarray(atom_weight, dtype=np.float32)
+    off = np.ascontiguousarray(atom_offsets, dtype=np.int64)
+    frt = np.ascontiguousarray(frames_rt, dtype=np.float32)
+    fst = np.ascontiguousarray(frame_structure, dtype=np.int32)
+    n_frames, V = frt.shape[0], int(voxels_per_side)
+    if fst.shape[0] != n_frames or off.ndim != 1 or off.shape[0] < 1 or chn.shape[0] != xyz.shape[0] or sig.shape[0] != xyz.shape[0] or \
+            (wgt is not None and wgt.shape[0] != xyz.shape[0]):
+        raise ValueError("voxelise_batch: array lengths disagree")
+    out = None
+    if d_out is None:
+        out = np.empty((n_frames, V, V, V, n_channels), dtype=np.float32 if gaussian else np.uint8)
+    ms = C.c_double(0.0)
+    _lib.check(lib.th_voxelise_batch(device, _lib.ptr(xyz), _lib.ptr(chn), _lib.ptr(sig), _lib.ptr(wgt), xyz.shape[0], _lib.ptr(off),
+                                     off.shape[0] - 1, _lib.ptr(frt), _lib.ptr(fst), n_frames, V, float(frame_edge_length), n_channels,
+                                     1 if gaussian else 0, C.c_void_p(d_out) if d_out is not None else _lib.ptr(out),
+                                     1 if d_out is not None else 0, C.byref(ms) if timing is not None else None))
+    if timing is not None:
+        timing["kernel_ms"] = timing.get("kernel_ms", 0.0) + ms.value
+    return out
+
+
 def voxelise_pdb(path, voxels_per_side: int = 21, frame_edge_length: float = 21.0, encode_cb: bool = True,
-                 atom_encoder: Sequence[str] = DEFAULT_ENCODER, gaussian: bool = True, all_states: bool = False, device: int = 0):
+                 atom_encoder: Sequence[str] = DEFAULT_ENCODER, gaussian: bool = True, all_states: bool = False, device: int = 0,
+                 property: Optional[str] = None, property_map=None):
     """PDB file -> (frames, labels [n,20] uint8, flat dataset map rows (pdb_code, chain, residue number, label)).
     The pdb code is the file name up to ".pdb"; with ``all_states`` every model is voxelised as "<code>_<k>"
-    (aposteriori's voxelise_all_states), otherwise model 1 only."""
+    (aposteriori's voxelise_all_states), otherwise model 1 only.  ``property`` ("polarity" / "charge", spec item 8) adds the
+    property channel behind ``atom_encoder``'s; ``property_map``: one integer per frame (or {pdb_code: [ints]}), None for the
+    residues' own values."""
     from design_utils.amino_acids import standard_amino_acids
     three = list(standard_amino_acids.values())
     code = os.path.basename(str(path)).split(".pdb")[0]
+    if property is not None and not gaussian:
+        raise ValueError(f"a {property} channel needs Gaussian frames (boolean frames carry no weight)")
+    n_channels = len(property_encoder(property, atom_encoder))
     models = pdbio.read_pdb(path)
     if not models:
         raise ValueError(f"{path}: no ATOM records")
@@ -147,15 +277,21 @@ def voxelise_pdb(path, voxels_per_side: int = 21, frame_edge_length: float = 21.
         models = models[:1]
     frames, labels, flat = [], [], []
     for k, model in enumerate(models):
-        xyz, ch, sg, frt, rows = prepare_structure(model, encode_cb=encode_cb, atom_encoder=atom_encoder)
         name = f"{code}_{k}" if all_states else code
-        frames.append(voxelise(xyz, ch, sg, frt, voxels_per_side, frame_edge_length, len(atom_encoder), gaussian, device))
+        if property is None:
+            xyz, ch, sg, frt, rows = prepare_structure(model, encode_cb=encode_cb, atom_encoder=atom_encoder)
+            frames.append(voxelise(xyz, ch, sg, frt, voxels_per_side, frame_edge_length, n_channels, gaussian, device))
+        else:
+            xyz, ch, sg, wt, frt, rows = prepare_structure_with_property(model, property, map_of(property_map, name), encode_cb=encode_cb,
+                                                                         atom_encoder=atom_encoder, name=name)
+            frames.append(voxelise_batch(xyz, ch, sg, wt, [0, len(xyz)], frt, np.zeros(len(frt), np.int32), voxels_per_side,
+                                         frame_edge_length, n_channels, True, device))
         for chain, number, label in rows:
             flat.append((name, chain, number, label))
             onehot = np.zeros(20, np.uint8)
             onehot[three.index(label)] = 1
             labels.append(onehot)
-    X = np.concatenate(frames) if frames else np.empty((0,) + (voxels_per_side,) * 3 + (len(atom_encoder),), np.float32)
+    X = np.concatenate(frames) if frames else np.empty((0,) + (voxels_per_side,) * 3 + (n_channels,), np.float32)
     return X, np.asarray(labels, dtype=np.uint8).reshape(-1, 20), flat
 
 

@@ -22,16 +22,21 @@ if __name__ == "__main__":
     ap.add_argument("--voxels-per-side", type=int, default=21)
     ap.add_argument("--frame-edge-length", type=float, default=21.0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--property", choices=["polarity", "charge"], default=None,
+                    help="add the property channel of TIMED_polar / TIMED_charge (six channels; PARITY UNPINNED AGAINST AMPAL AND APOSTERIORI)")
+    ap.add_argument("--path_to_property_map", default=None, help="JSON {pdb_code: [ints]} or, for one structure, a bare list")
     a = ap.parse_args()
     t0 = time.perf_counter()
+    property_map = voxeliser.read_property_map(a.path_to_property_map) if a.path_to_property_map else None
     Xs, Ls, flat = [], [], []
     for path in a.structures:
         X, labels, rows = voxeliser.voxelise_pdb(path, a.voxels_per_side, a.frame_edge_length, gaussian=not a.boolean,
-                                                 all_states=a.all_states, device=a.device)
+                                                 all_states=a.all_states, device=a.device, property=a.property, property_map=property_map)
         Xs.append(X); Ls.append(labels); flat += rows
     X, L = np.concatenate(Xs), np.concatenate(Ls)
     voxeliser.write_frame_pack(a.out, X, L, flat, gaussian=not a.boolean, source=",".join(os.path.basename(p) for p in a.structures))
     if a.hdf5:
-        voxeliser.write_hdf5(a.out + ".hdf5", X, L, flat, gaussian=not a.boolean, frame_edge_length=a.frame_edge_length)
+        voxeliser.write_hdf5(a.out + ".hdf5", X, L, flat, gaussian=not a.boolean, atom_encoder=voxeliser.property_encoder(a.property),
+                             frame_edge_length=a.frame_edge_length)
     print(f"{len(flat)} residue frames {X.shape[1:]} {X.dtype} from {len(a.structures)} structure(s) -> {a.out}.framepack "
           f"in {time.perf_counter() - t0:.2f} s")
