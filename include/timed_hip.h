@@ -606,7 +606,14 @@ int th_h5_group_links(const void* file, int64_t file_len, int64_t base, int64_t 
  * else uint8 (0/1); `out` is host memory, or device memory of `device` when out_on_device (frames then go straight to
  * th_predict_device without leaving HBM).  One frame holds at most 2048 encodable atoms (TH_EUNSUP beyond).  An atom
  * whose coordinate in a frame is NaN or infinite is not encoded there: a frames_rt row that holds such a value gives an
- * all-zero frame, never a NaN in the output. */
+ * all-zero frame, never a NaN in the output.
+ * This is th_voxelise_batch (below) for ONE structure that owns every atom and every frame, without weights: the same kernel
+ * and the same host path.  So the call works on a non-blocking stream of its own and waits for that stream only, never for
+ * the whole device.  Every refusal happens before the first HIP call, th_last_error naming th_voxelise: TH_EINVAL for a NULL
+ * array where a count is non-zero, a negative count, n_res > INT_MAX (refused, not truncated), voxels_per_side even or
+ * > 511, frame_edge_length not positive, Gaussian frames of atoms without sigmas; TH_EUNSUP for n_channels outside 1..8.
+ * n_res == 0: TH_OK, nothing is launched.  A failed allocation is TH_ENOMEM when HIP reports out of memory (TH_EHIP
+ * otherwise).  When frames overflow the list, the count in th_last_error is the largest over the frames. */
 int th_voxelise(int device, const float* atoms_xyz, const int32_t* atom_channel, const float* atom_sigma, int64_t n_atoms,
                 const float* frames_rt, int64_t n_res, int voxels_per_side, float frame_edge_length, int n_channels, int gaussian,
                 void* out, int out_on_device);
@@ -618,14 +625,16 @@ int th_voxelise(int device, const float* atoms_xyz, const int32_t* atom_channel,
  * [atom_offsets[s], atom_offsets[s + 1]) (atom_offsets [n_structures + 1], from 0 to n_atoms, never decreasing; a structure may
  * be empty or have no frame).  frames_rt [n_frames, 12] and frame_structure [n_frames]: frame r sees the atoms of structure
  * frame_structure[r] and no others; frames may be listed in any order.  atom_weight [n_atoms] or NULL (every atom counts 1).
- * Rule: with unit weights frame r is what th_voxelise gives for that structure's atoms alone and that frames_rt row.  A Gaussian
- * contribution is acc = acc + weight * (w / total): the quotient, then the product, each rounded to float32, then added, in atom
- * order, no fused multiply-add.  Multiplying by 1.0f is exact, so with atom_weight NULL or all ones the frames equal th_voxelise's
- * byte for byte, Gaussian and boolean alike.  A frame's bytes do not depend on where the frame or its structure sits in the
+ * Rule: frame r is what the specification (timed_hip/voxeliser.py items 3-6 and 8) gives for that structure's atoms alone and
+ * that frames_rt row; th_voxelise is the case of one structure.  A Gaussian contribution is acc = acc + weight * (w / total):
+ * the quotient, then the product, each rounded to float32, then added, in atom order, no fused multiply-add.  Multiplying by
+ * 1.0f is exact, so atom_weight NULL and atom_weight all ones give the same frames byte for byte, and a structure's frames are
+ * th_voxelise's byte for byte, Gaussian and boolean alike.  A frame's bytes do not depend on where the frame or its structure sits in the
  * batch or on what else the batch holds (no float atomics).  At most 2048 encodable atoms inside one frame: beyond, the whole
  * call fails with TH_EUNSUP and the count in th_last_error.
  * The call works on a non-blocking stream of its own and waits for that stream only (no device-wide synchronise): a loader thread
- * does not wait for kernels other threads have queued.  out: host memory, or device memory of `device` when out_on_device (nothing
+ * does not wait for kernels other threads have queued.  The stream is kept for the next call when this one returns (creating one
+ * costs milliseconds); calls that overlap hold different streams.  out: host memory, or device memory of `device` when out_on_device (nothing
  * is downloaded then).  kernel_ms (may be NULL): the kernel's time from events on the call's stream.
  * Refused before any HIP call, th_last_error naming th_voxelise_batch — TH_EINVAL: a NULL array where a count is non-zero;
  * atom_offsets[0] != 0, a decreasing offset, a last offset != n_atoms; a frame_structure entry outside [0, n_structures);

@@ -1,5 +1,7 @@
-"""th_voxelise_batch (csrc/voxelise_batch.hip) on the GPU: many structures in one launch against the per-structure oracle
-(oracle/voxel_oracle.py) and, byte for byte, against one th_voxelise call per structure; frames that do not depend on their batch;
+"""th_voxelise_batch (csrc/voxelise.hip) on the GPU: many structures in one launch against the per-structure oracle
+(oracle/voxel_oracle.py); byte for byte against one th_voxelise call per structure (the same kernel through the one-structure
+wrapper: stack offsets, a zeroed frame_structure) and, both of them, against the digests of the frames th_voxelise gave at 51dee49,
+when it still had a kernel of its own (tests/golden/voxelise_digests.json); frames that do not depend on their batch;
 the atom list at its limit and one past it in the middle of a batch; weights against the restatement
 (tests/voxel_weight_restatement.py) and against a difference of two unit-weight channels; frames written into the middle of a device
 buffer and read there by the CNN; the charge channel of 1ubq.  Clouds from tests/voxel_cases.py.
@@ -19,14 +21,8 @@ from timed_hip import _lib, voxeliser
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 5e-6, 1e-9
+RTOL, ATOL = vc.RTOL, vc.ATOL
 UBQ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "1ubq.pdb1.gz")
-
-
-def _decoy(cloud, C):
-    """the same coordinates with the encodable channels rotated by one, and no frame"""
-    ch = np.where((cloud.ch >= 0) & (cloud.ch < C), (cloud.ch + 1) % C, cloud.ch).astype(np.int32)
-    return vc.Cloud(cloud.xyz, ch, cloud.sg, cloud.frt[:0])
 
 
 def _flatten(clouds, order_seed=None):
@@ -44,19 +40,10 @@ def _flatten(clouds, order_seed=None):
     return kw, frames
 
 
-def _same(got, want, gaussian, label):
-    assert got.dtype == want.dtype and got.shape == want.shape
-    if not gaussian:
-        print(f"{label}: {int(want.sum())} cells set, {int(np.count_nonzero(got != want))} differ")
-        assert np.array_equal(got, want)
-        return
-    g, w = got.astype(np.float64), want.astype(np.float64)
-    worst = float(np.max(np.abs(g - w) / (ATOL + RTOL * np.abs(w)))) if w.size else 0.0
-    print(f"{label}: {int(np.count_nonzero(want))} non-zero, support differs in {int(np.count_nonzero((got != 0) != (want != 0)))}, "
-          f"worst |got - want| / (atol + rtol |want|) = {worst:.3f}")
-    assert not np.isnan(got).any()
-    assert np.array_equal(got != 0, want != 0)
-    np.testing.assert_allclose(got, want, rtol=RTOL, atol=ATOL)
+def _per_structure(got, frames, n_structures):
+    """the frames of a batch regrouped: one array per structure, in that structure's own frame order"""
+    where = {sk: r for r, sk in enumerate(frames)}
+    return [got[[where[(s, k)] for k in range(sum(1 for t, _ in frames if t == s))]] for s in range(n_structures)]
 
 
 def _within_mass(got, want, mass, label):
@@ -72,15 +59,9 @@ def _within_mass(got, want, mass, label):
 @pytest.fixture(scope="module")
 def mixed():
     """structures of the (21, 21.0, 5) geometry, each followed by its decoy; the oracle's frames per structure, computed once"""
-    V, edge, C = 21, 21.0, 5
-    cases = vc.one_launch_cases()
-    row = vc.frame_row(np.random.default_rng(5))
-    real = [cases["batch-3"].cloud, vc.Cloud(np.zeros((0, 3), np.float32), np.zeros(0, np.int32), np.zeros(0, np.float32), row[None, :]),
-            cases["chunking-gauss"].cloud]
-    real += [vc.interior_cloud(V, edge, C, 1, 701)] + [vc.uniform_cloud(V, edge, C, n, 700 + n) for n in (255, 256, 257)]
-    real += [cases["nonfinite"].cloud, vc.Cloud(*vc.uniform_cloud(V, edge, C, 300, 990)[:3], np.zeros((0, 12), np.float32))]
+    clouds, (V, edge, C) = vc.mixed_clouds()
+    real = clouds[::2]
     assert [len(c.xyz) for c in real] == [500, 0, 5000, 1, 255, 256, 257, 240, 300] and [len(c.frt) for c in real] == [3, 1, 1, 1, 1, 1, 1, 5, 0]
-    clouds = [c for r in real for c in (r, _decoy(r, C))]
     starts = np.concatenate([[0], np.cumsum([len(c.xyz) for c in clouds])])[:-1]
     assert sum(1 for c, o in zip(clouds, starts) if len(c.frt) and o % vc.CHUNK) >= 6         # ranges that start off a chunk boundary
     want = {g: [voxel_oracle.voxelise(*c, V, edge, C, g) for c in clouds] for g in (False, True)}
@@ -97,11 +78,14 @@ def test_one_batch_of_many_structures(gpu, mixed, gaussian):
     assert [s for s, _ in frames] != sorted(s for s, _ in frames)                         # interleaved, not grouped by structure
     got = voxeliser.voxelise_batch(**kw, voxels_per_side=V, frame_edge_length=edge, n_channels=C, gaussian=gaussian, device=gpu)
     expect = np.stack([want[gaussian][s][k] for s, k in frames])
-    _same(got, expect, gaussian, f"mixed batch, gaussian={gaussian}")
+    vc.same(got, expect, gaussian, f"mixed batch, gaussian={gaussian}")
     assert expect.any(axis=(1, 2, 3, 4)).sum() == 11                                      # all but the empty structure's and the two NaN frames
-    # the bytes of one th_voxelise call per structure
+    # the bytes of one th_voxelise call per structure, and of both the bytes of the parent's th_voxelise
     single = [voxeliser.voxelise(*c, V, edge, C, gaussian, device=gpu) for c in clouds]
     assert got.tobytes() == np.stack([single[s][k] for s, k in frames]).tobytes()
+    for s, (mine, alone) in enumerate(zip(_per_structure(got, frames, len(clouds)), single)):
+        vc.assert_parent_bytes(mine, f"mixed/{s}/{vc.mode(gaussian)}")
+        vc.assert_parent_bytes(alone, f"mixed/{s}/{vc.mode(gaussian)}")
     # the same batch again, and every frame in a batch of its own that holds nothing but its structure
     again = voxeliser.voxelise_batch(**kw, voxels_per_side=V, frame_edge_length=edge, n_channels=C, gaussian=gaussian, device=gpu)
     assert again.tobytes() == got.tobytes()
@@ -121,6 +105,9 @@ def test_every_sweep_geometry_gives_the_bytes_of_th_voxelise(gpu, gaussian):
         got = voxeliser.voxelise_batch(**kw, voxels_per_side=V, frame_edge_length=edge, n_channels=C, gaussian=gaussian, device=gpu)
         single = [voxeliser.voxelise(*c, V, edge, C, gaussian, device=gpu) for c in clouds]
         assert got.any() and got.tobytes() == np.stack([single[s][k] for s, k in frames]).tobytes(), (V, edge, C)
+        for which, mine, alone in zip(("bool-cloud", "gauss-cloud"), _per_structure(got, frames, 2), single):
+            vc.assert_parent_bytes(mine, f"sweep/{V}-{edge}-{C}/{which}/{vc.mode(gaussian)}")
+            vc.assert_parent_bytes(alone, f"sweep/{V}-{edge}-{C}/{which}/{vc.mode(gaussian)}")
 
 
 # ---- b. many frames --------------------------------------------------------------------------------------------------------------
@@ -133,6 +120,8 @@ def test_three_hundred_frames_twice(gpu, gaussian):
     single = voxeliser.voxelise(*case.cloud, case.V, case.edge, case.C, gaussian, device=gpu)
     assert got.shape == (600, 5, 5, 5, 4) and single.any(axis=(1, 2, 3, 4)).all()
     assert got[:300].tobytes() == single.tobytes() and got[300:].tobytes() == single.tobytes()
+    for frames_of_one in (got[:300], got[300:], single):
+        vc.assert_parent_bytes(frames_of_one, f"batch-300/{vc.mode(gaussian)}")
 
 
 # ---- c. capacity -----------------------------------------------------------------------------------------------------------------
@@ -145,7 +134,7 @@ def test_atom_list_full_and_one_too_many_in_the_middle_of_a_batch(gpu, lib):
     kw, frames = _flatten(clouds)
     got = voxeliser.voxelise_batch(**kw, voxels_per_side=V, frame_edge_length=edge, n_channels=C, gaussian=False, device=gpu)
     want = np.concatenate([voxel_oracle.voxelise(*c, V, edge, C, False) for c in clouds])
-    _same(got, want, False, "capacity-2048 between two structures")
+    vc.same(got, want, False, "capacity-2048 between two structures")
     assert int(want[1].sum()) > 1500
     over, _ = _flatten([side[0], vc.capacity_cloud(vc.MAX_LIST + 1, 0, 71), side[1]])
     with pytest.raises(_lib.TimedHipError) as err:
@@ -156,13 +145,31 @@ def test_atom_list_full_and_one_too_many_in_the_middle_of_a_batch(gpu, lib):
     assert after.tobytes() == got.tobytes()
 
 
+@pytest.mark.parametrize("V,edge", [(5, 7.3), (21, 21.0)])
+def test_th_voxelise_reports_the_largest_of_two_overflowing_frames(gpu, lib, V, edge):
+    """one structure, two frames that both overflow (2049 and 2100 encodable atoms): the count in the message is the larger one
+    whichever workgroup wrote last, call after call, and the next valid call is unharmed"""
+    C = 5
+    a, b = vc.capacity_cloud(vc.MAX_LIST + 1, 0, 171, V, edge, C), vc.capacity_cloud(2100, 0, 172, V, edge, C)
+    both = vc.merge(a, b)                                                                 # frames: a's full one, a's few, b's full one, b's few
+    ch_ok = (both.ch >= 0) & (both.ch < C)
+    inside = [int((voxel_oracle.locate(both.xyz, row, V, edge)[2] & ch_ok).sum()) for row in both.frt]
+    assert inside == [2049, 10, 2100, 10]
+    for _ in range(3):
+        with pytest.raises(_lib.TimedHipError) as err:
+            voxeliser.voxelise(both.xyz, both.ch, both.sg, both.frt[[0, 2]], V, edge, C, False, device=gpu)
+        assert err.value.code == -4 and "2100 encodable atoms" in str(err.value) and b"2100" in lib.th_last_error()
+        assert "th_voxelise:" in str(err.value) and "th_voxelise_batch" not in str(err.value)
+    few = voxeliser.voxelise(both.xyz, both.ch, both.sg, both.frt[[1, 3]], V, edge, C, False, device=gpu)
+    want = voxel_oracle.voxelise(both.xyz, both.ch, both.sg, both.frt[[1, 3]], V, edge, C, False)
+    assert want.any(axis=(1, 2, 3, 4)).all() and few.tobytes() == want.tobytes()
+
+
 # ---- d. weights ------------------------------------------------------------------------------------------------------------------
 
 def test_weights_against_the_restatement_and_against_two_channels(gpu):
-    case = vc.sweep_gaussian(9, 12.5, 8)
+    case, wgt, sign, two = vc.weight_inputs()
     cloud, V, edge, C = case.cloud, case.V, case.edge, case.C
-    rng = np.random.default_rng(17)
-    wgt = rng.choice(np.array([-1.0, 1.0, 2.5], np.float32), len(cloud.xyz))
     off, fst = [0, len(cloud.xyz)], np.zeros(len(cloud.frt), np.int32)
     got = voxeliser.voxelise_batch(cloud.xyz, cloud.ch, cloud.sg, wgt, off, cloud.frt, fst, V, edge, C, True, device=gpu)
     want, mass = vw.voxelise_weighted(cloud.xyz, cloud.ch, cloud.sg, wgt, cloud.frt, V, edge, C)
@@ -174,12 +181,13 @@ def test_weights_against_the_restatement_and_against_two_channels(gpu):
     # all ones: the bytes of th_voxelise
     ones = voxeliser.voxelise_batch(cloud.xyz, cloud.ch, cloud.sg, np.ones(len(cloud.xyz), np.float32), off, cloud.frt, fst, V, edge, C, True, device=gpu)
     assert ones.tobytes() == unit.tobytes()
+    vc.assert_parent_bytes(unit, "weights/unit")
+    vc.assert_parent_bytes(ones, "weights/unit")
     # without the restatement: positive atoms in channel 0 and negative ones in channel 1 at unit weight, against all of them in
     # channel 0 with weights +-1
     keep = (cloud.ch >= 0) & (cloud.ch < C)
-    sign = np.where(rng.random(len(cloud.xyz)) < 0.5, -1.0, 1.0).astype(np.float32)
-    two = np.where(keep, np.where(sign > 0, 0, 1), -1).astype(np.int32)
     old = voxeliser.voxelise(cloud.xyz, two, cloud.sg, cloud.frt, V, edge, 2, True, device=gpu)
+    vc.assert_parent_bytes(old, "weights/two-channel")
     new = voxeliser.voxelise_batch(cloud.xyz, np.where(keep, 0, -1).astype(np.int32), cloud.sg, sign, off, cloud.frt, fst, V, edge, 1, True, device=gpu)
     assert old[..., 0].any() and old[..., 1].any() and ((old[..., 0] != 0) & (old[..., 1] != 0)).any()
     _within_mass(new[..., 0], old[..., 0].astype(np.float64) - old[..., 1].astype(np.float64), old[..., 0].astype(np.float64) + old[..., 1], "+-1 against two channels")
@@ -224,6 +232,7 @@ def test_charge_channel_of_1ubq(gpu, tmp_path):
     from timed_hip import pdbio
     five, _, flat = voxeliser.voxelise_pdb(UBQ, device=gpu)
     assert five.shape == (76, 21, 21, 21, 5)
+    vc.assert_parent_bytes(five, vc.UBQ_DIGEST)
     for value in (1, -1, 0):
         six, labels, flat6 = voxeliser.voxelise_pdb(UBQ, device=gpu, property="charge", property_map=[value] * 76)
         assert six.shape == (76, 21, 21, 21, 6) and flat6 == flat and labels.shape == (76, 20)

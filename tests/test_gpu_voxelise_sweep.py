@@ -1,10 +1,10 @@
-"""th_voxelise (csrc/voxelise.hip) against oracle/voxel_oracle.py away from the one geometry of tests/test_voxeliser.py: voxel edges
+"""th_voxelise (csrc/voxelise.hip: the one-structure call of the kernel th_voxelise_batch runs) against oracle/voxel_oracle.py away from the one geometry of tests/test_voxeliser.py: voxel edges
 that are not 1, atoms on voxel faces, 1..8 channels, atoms spread over twenty compaction chunks, the atom list at its limit and one
 past it, atoms at the cube's border, stacked atoms, hundreds of frames in a launch, non-finite input, boolean frames kept on the
 device.  The clouds come from tests/voxel_cases.py; tests/test_voxel_cases_host.py shows on the CPU what they can tell apart.
 
 Tolerances are those of tests/test_voxeliser.py: boolean frames bit-exact; Gaussian frames with the same non-zero voxels and values
-within rtol 5e-6, atol 1e-9 (expf against NumPy's float32 exp)."""
+within rtol 5e-6, atol 1e-9 (expf against NumPy's float32 exp): voxel_cases.same."""
 import numpy as np
 import pytest
 
@@ -13,8 +13,6 @@ from oracle import voxel_oracle
 from timed_hip import _lib, voxeliser
 
 pytestmark = pytest.mark.gpu
-
-RTOL, ATOL = 5e-6, 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -39,21 +37,6 @@ def _run(case, gaussian, gpu, cloud=None, **kw):
     return voxeliser.voxelise(*(case.cloud if cloud is None else cloud), case.V, case.edge, case.C, gaussian, device=gpu, **kw)
 
 
-def _same(got, want, gaussian, label):
-    assert got.dtype == want.dtype and got.shape == want.shape
-    if not gaussian:
-        print(f"{label}: {int(want.sum())} cells set, {int(np.count_nonzero(got != want))} differ")
-        assert np.array_equal(got, want)                                      # bit-exact
-        return
-    g, w = got.astype(np.float64), want.astype(np.float64)
-    worst = float(np.max(np.abs(g - w) / (ATOL + RTOL * np.abs(w)))) if w.size else 0.0
-    print(f"{label}: {int(np.count_nonzero(want))} non-zero, support differs in {int(np.count_nonzero((got != 0) != (want != 0)))}, "
-          f"worst |got - want| / (atol + rtol |want|) = {worst:.3f}")
-    assert not np.isnan(got).any()
-    assert np.array_equal(got != 0, want != 0)                                # the same voxels are touched
-    np.testing.assert_allclose(got, want, rtol=RTOL, atol=ATOL)
-
-
 # ---- a. geometry sweep ---------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("gaussian", [False, True])
@@ -64,7 +47,7 @@ def test_geometry_sweep(gpu, cases, V, edge, C, gaussian):
     name = f"sweep-{'gauss' if gaussian else 'bool'}-{V}-{edge}-{C}"
     want = _want(cases, name, gaussian)
     assert want.shape == (3, V, V, V, C) and want.any()
-    _same(_run(cases[name], gaussian, gpu), want, gaussian, name)
+    vc.same(_run(cases[name], gaussian, gpu), want, gaussian, name)
 
 
 # ---- b. chunking ---------------------------------------------------------------------------------------------------------------
@@ -73,14 +56,14 @@ def test_geometry_sweep(gpu, cases, V, edge, C, gaussian):
 def test_atoms_inside_scattered_over_twenty_chunks(gpu, cases, gaussian):
     """5000 atoms: chunks with no atom inside, with whole waves inside, with a sprinkle, and a partial last chunk"""
     name = f"chunking-{'gauss' if gaussian else 'bool'}"
-    _same(_run(cases[name], gaussian, gpu), _want(cases, name, gaussian), gaussian, name)
+    vc.same(_run(cases[name], gaussian, gpu), _want(cases, name, gaussian), gaussian, name)
 
 
 # ---- c. capacity ---------------------------------------------------------------------------------------------------------------
 
 def test_atom_list_exactly_full(gpu, cases):
     """2048 encodable atoms inside one frame, interleaved with 1500 that are outside or of channel -1 or C and must not count"""
-    _same(_run(cases["capacity-2048"], False, gpu), _want(cases, "capacity-2048", False), False, "capacity-2048")
+    vc.same(_run(cases["capacity-2048"], False, gpu), _want(cases, "capacity-2048", False), False, "capacity-2048")
 
 
 def test_atom_list_one_too_many(gpu, lib):
@@ -108,7 +91,7 @@ def _encodable(case):
 def test_weight_beyond_the_border_is_lost(gpu, cases, V):
     name = f"borders-{V}"
     got, want = _run(cases[name], True, gpu), _want(cases, name, True)
-    _same(got, want, True, name)
+    vc.same(got, want, True, name)
     for r, n in enumerate(_encodable(cases[name])):
         lost_got, lost_want = n - got[r].sum(dtype=np.float64), n - want[r].sum(dtype=np.float64)
         print(f"{name} frame {r}: {n} atoms inside, mass lost {lost_got:.6f} (oracle {lost_want:.6f})")
@@ -123,7 +106,7 @@ def test_interior_atoms_keep_unit_mass(gpu, cases, V):
     name = f"interiors-{V}"
     case = cases[name]
     got = _run(case, True, gpu)
-    _same(got, _want(cases, name, True), True, name)
+    vc.same(got, _want(cases, name, True), True, name)
     count = np.bincount(case.cloud.ch, minlength=case.C)
     mass = got[0].reshape(-1, case.C).sum(axis=0, dtype=np.float64)
     print(f"{name}: atoms per channel {count.tolist()}, |mass - count| / count {(np.abs(mass - count) / count).tolist()}")
@@ -137,10 +120,10 @@ def test_stacked_atoms(gpu, cases, C, channel):
     """120 atoms of one channel in four voxels: a boolean cell stays 1, a Gaussian cell holds the sum"""
     name = f"stacked-{C}"
     b = _run(cases[name], False, gpu)
-    _same(b, _want(cases, name, False), False, name)
+    vc.same(b, _want(cases, name, False), False, name)
     assert b.max() == 1 and 1 <= b.sum() <= 4 and b[..., channel].sum() == b.sum()
     g = _run(cases[name], True, gpu)
-    _same(g, _want(cases, name, True), True, name)
+    vc.same(g, _want(cases, name, True), True, name)
     assert g.max() > 2.0 and g[..., channel].sum(dtype=np.float64) == g.sum(dtype=np.float64)
 
 
@@ -156,7 +139,7 @@ def test_channels_out_of_range_leave_no_trace_and_bytes_are_stored_one_by_one(gp
         assert np.array_equal(got, _run(case, gaussian, gpu, cloud=vc.subset(cloud, keep)))
         if not gaussian:
             want = voxel_oracle.voxelise(*cloud, 9, 12.5, C, False)
-            _same(got, want, False, f"channels-{C}")
+            vc.same(got, want, False, f"channels-{C}")
             assert all(want[..., c].any() for c in range(C))
 
 
@@ -173,7 +156,7 @@ def test_frames_do_not_depend_on_their_launch(gpu, cases, name, gaussian):
         single = _run(case, gaussian, gpu, cloud=vc.Cloud(*case.cloud[:3], case.cloud.frt[r:r + 1]))
         assert np.array_equal(single[0], full[r]), r
     if name == "batch-3":
-        _same(full, _want(cases, name, gaussian), gaussian, name)
+        vc.same(full, _want(cases, name, gaussian), gaussian, name)
 
 
 # ---- g. non-finite input -------------------------------------------------------------------------------------------------------
@@ -193,7 +176,7 @@ def test_non_finite_atoms_and_frames_are_not_encoded(gpu, gaussian):
     assert not np.isnan(got).any()
     assert not got[nan_frames].any()
     assert want[~nan_frames].any(axis=(1, 2, 3, 4)).all()
-    _same(got[~nan_frames], want[~nan_frames], gaussian, "non-finite")
+    vc.same(got[~nan_frames], want[~nan_frames], gaussian, "non-finite")
 
 
 # ---- h. boolean frames on the device -------------------------------------------------------------------------------------------
@@ -203,7 +186,7 @@ def test_boolean_frames_stay_on_the_device_for_the_cnn(gpu, cases):
     case = cases["batch-3"]
     n, V, C = len(case.cloud.frt), case.V, case.C
     host = _run(case, False, gpu)
-    _same(host, _want(cases, "batch-3", False), False, "device-uint8")
+    vc.same(host, _want(cases, "batch-3", False), False, "device-uint8")
     d_frames = engine.DeviceBuffer(host.nbytes + 64, gpu)
     d_frames.upload(np.full(host.nbytes + 64, 0xAB, np.uint8))                 # every byte of the frames must be written, none beyond
     assert _run(case, False, gpu, d_out=d_frames.ptr) is None

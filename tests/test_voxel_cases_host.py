@@ -119,3 +119,20 @@ def test_oracle_on_non_finite_input_encodes_the_finite_atoms_and_warns_of_nothin
         assert np.array_equal(vc.boolean_frames(cloud, 21, 21.0, 5), voxel_oracle.voxelise(*cloud, gaussian=False))
         _loc, idx, inside = voxel_oracle.locate(cloud.xyz, cloud.frt[3])
         assert not inside.any() and not idx.any()
+
+
+def test_recorded_digests_cover_the_cases_and_say_where_they_come_from():
+    """tests/golden/voxelise_digests.json: one entry per case of digest_cases and the frames of 1ubq, each of the shape the case's
+    cloud and geometry give, recorded at the last commit at which th_voxelise had a kernel of its own"""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "voxelise_digests.json")) as f:
+        rec = json.load(f)
+    assert rec["commit"] == "51dee49" and rec["hip"] and "gfx950" in rec["device"]
+    calls = vc.digest_cases()
+    assert list(rec["cases"]) == [c[0] for c in calls] + [vc.UBQ_DIGEST] and len(set(rec["cases"])) == 69
+    for case_id, cloud, V, edge, C, gaussian in calls:
+        got = rec["cases"][case_id]
+        assert got["shape"] == [len(cloud.frt), V, V, V, C] and got["dtype"] == ("float32" if gaussian else "uint8"), case_id
+        assert len(got["sha256"]) == 64
+    assert rec["cases"][vc.UBQ_DIGEST]["shape"] == [76, 21, 21, 21, 5]

@@ -1,5 +1,5 @@
 """th_voxelise_batch, the property channel and structure sets without a GPU: the header prototype against the ctypes entry, every
-refusal of the call (all decided on the host), the charge / polarity tables against what the reference pins, the property-aware
+refusal of the call and of th_voxelise, its one-structure case (all decided on the host), the charge / polarity tables against what the reference pins, the property-aware
 preparation of 1ubq, property-map validation, a set of three files, and predict.py over a directory with the batch call replaced by
 its restatement (tests/voxel_weight_restatement.py) and a model double."""
 import ctypes as C
@@ -59,9 +59,12 @@ def test_header_prototype_ctypes_entry_build_list_and_phrase(lib):
         assert words in block, words
     assert hasattr(lib, "th_voxelise_batch")
     import __graft_entry__
-    assert "voxelise_batch.hip" in __graft_entry__.HIP_SOURCES and "voxelise.hip" in __graft_entry__.HIP_SOURCES
-    source = open(os.path.join(ROOT, "timed-design_amd", "csrc", "voxelise_batch.hip")).read()
-    assert "hipDeviceSynchronize" not in source and "hipStreamNonBlocking" in source
+    # one unit holds the one kernel and the one host path of th_voxelise and th_voxelise_batch
+    csrc = os.path.join(ROOT, "timed-design_amd", "csrc")
+    assert "voxelise_batch.hip" not in __graft_entry__.HIP_SOURCES and "voxelise.hip" in __graft_entry__.HIP_SOURCES
+    assert "voxelise_batch.hip" not in os.listdir(csrc) and hasattr(lib, "th_voxelise")
+    source = open(os.path.join(csrc, "voxelise.hip")).read()
+    assert source.count("__global__") == 1 and "hipDeviceSynchronize" not in source and "hipStreamNonBlocking" in source
     # the only atomics are on integers in LDS (plane counts) and on the overflow flag: none on frame data
     assert sorted(set(re.findall(r"atomic\w+\([^,]*,", source))) == ["atomicAdd(&Ps[((Li[e] >> 18) & 511) + 1],", "atomicMax(p.overflow,"]
     assert "__shared__ int Ps[" in source and "int* overflow" in source
@@ -112,6 +115,32 @@ def test_every_refusal_is_decided_without_a_gpu(lib):
     assert call(n_frames=0, frt=None, fst=None, out=None, sig=None, gaussian=0) == _lib.TH_OK
     with pytest.raises(ValueError, match="lengths disagree"):
         voxeliser.voxelise_batch(xyz, chn, sig, wgt[:3], off, frt, fst, 3, 3.0, 2)
+
+
+def test_th_voxelise_refuses_on_the_host_under_its_own_name(lib):
+    """the one-structure entry point shares the batch call's refusals, all of them before the first HIP call"""
+    xyz, chn, sig = np.zeros((4, 3), np.float32), np.zeros(4, np.int32), np.ones(4, np.float32)
+    frt = np.array([[1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]], np.float32)
+    out = np.full((1, 3, 3, 3, 2), 7, np.float32)
+    nan = float("nan")
+
+    def call(xyz=xyz, chn=chn, sig=sig, n_atoms=4, frt=frt, n_res=1, V=3, edge=3.0, channels=2, gaussian=1, out=out):
+        return lib.th_voxelise(0, _lib.ptr(xyz), _lib.ptr(chn), _lib.ptr(sig), n_atoms, _lib.ptr(frt), n_res, V, edge, channels, gaussian,
+                               _lib.ptr(out), 0)
+    einval = {"even side": dict(V=4), "side 0": dict(V=0), "side 513": dict(V=513), "edge 0": dict(edge=0.0), "edge negative": dict(edge=-3.0),
+              "edge nan": dict(edge=nan), "negative atoms": dict(n_atoms=-1), "negative frames": dict(n_res=-1), "frames_rt NULL": dict(frt=None),
+              "out NULL": dict(out=None), "xyz NULL": dict(xyz=None), "channel NULL": dict(chn=None), "sigma NULL, Gaussian": dict(sig=None),
+              "2^31 frames": dict(n_res=2 ** 31)}
+    for what, kw in einval.items():
+        assert call(**kw) == _lib.TH_EINVAL, what
+        assert b"th_voxelise" in lib.th_last_error() and b"th_voxelise_batch" not in lib.th_last_error(), what
+    for channels in (0, 9):
+        assert call(channels=channels) == _lib.TH_EUNSUP, channels
+        assert b"th_voxelise" in lib.th_last_error() and b"th_voxelise_batch" not in lib.th_last_error()
+    assert not (out != 7).any()                                           # nothing was written
+    assert call(n_res=0) == _lib.TH_OK and call(n_res=0, frt=None, out=None) == _lib.TH_OK
+    assert call(n_res=0, sig=None, gaussian=0) == _lib.TH_OK
+    assert not (out != 7).any()
 
 
 # ---- 3, 4. tables ----------------------------------------------------------------------------------------------------------------
@@ -212,7 +241,8 @@ def three_files(tmp_path):
 
 
 def test_structure_set_of_three_files(three_files, tmp_path, monkeypatch):
-    monkeypatch.setattr(voxeliser, "voxelise", lambda xyz, ch, sg, frt, V, edge, C_, g, dev: np.zeros((len(frt), V, V, V, C_), np.float32))
+    monkeypatch.setattr(voxeliser, "voxelise_batch",
+                        lambda xyz, ch, sg, wt, off, frt, fst, V, edge, C_, g, dev: np.zeros((len(frt), V, V, V, C_), np.float32))
     sset = structureset.StructureSet(three_files)
     assert sset.codes == ["alpha", "mid", "zeta"] and sset.n_channels == 5 and sset.frame_dims == (21, 21, 21, 5)
     rows = []

@@ -2,12 +2,19 @@
 frames: the specification itself and two deliberately wrong ones.  Plain helpers, no tests: tests/test_voxel_cases_host.py checks
 on the CPU that the generators are sharp (they separate the wrong restatements from the right one), that every cloud fits the
 kernel's atom list, and that no weight is small enough for denormal flushing to matter; tests/test_gpu_voxelise_sweep.py runs the
-same clouds through th_voxelise against oracle/voxel_oracle.py.
+same clouds through th_voxelise against oracle/voxel_oracle.py, tests/test_gpu_voxelise_batch.py through th_voxelise_batch, many to
+a launch.  Both entry points run the one kernel of csrc/voxelise.hip (th_voxelise is the one-structure case); the comparison both
+test files share (`same`) and the digests of the frames th_voxelise gave while it still had a kernel of its own
+(tests/golden/voxelise_digests.json) are at the end of this file.
 
-A cloud is (xyz float32 [n,3], ch int32 [n], sg float32 [n], frt float32 [n_frames,12]) — the four arrays th_voxelise takes.  Every
+A cloud is (xyz float32 [n,3], ch int32 [n], sg float32 [n], frt float32 [n_frames,12]) — the four arrays th_voxelise takes, and one
+structure of a th_voxelise_batch call.  Every
 generator draws its atoms in the LOCAL frame of one residue (targets t), then maps them back with p = CA + R^T t in float64, R and
 CA being the float32 values of the frame row, and rounds p to float32: what the kernel reads is a float32 structure whose atoms sit
 where the generator wants them to within the rounding of a coordinate tens of Angstrom from the origin (~4e-6)."""
+import hashlib
+import json
+import os
 from collections import namedtuple
 
 import numpy as np
@@ -15,7 +22,7 @@ import numpy as np
 Cloud = namedtuple("Cloud", "xyz ch sg frt")
 Case = namedtuple("Case", "cloud V edge C")
 
-MAX_LIST = 2048                       # kMaxList of csrc/voxelise.hip: encodable atoms inside one frame
+MAX_LIST = 2048                       # kMaxList of csrc/voxelise.hip, the one kernel of both entry points: encodable atoms inside one frame
 CHUNK = 256                           # atoms per pass of the kernel's ordered compaction
 
 # (voxels_per_side, frame_edge_length, n_channels) of the geometry sweep
@@ -296,3 +303,96 @@ def one_launch_cases():
 
 
 GAUSSIAN_CASES = ("sweep-gauss", "chunking-gauss", "borders", "interiors", "stacked", "batch", "nonfinite")
+
+
+# ---- what the two GPU test files share ------------------------------------------------------------------------------------------
+
+RTOL, ATOL = 5e-6, 1e-9               # Gaussian frames against the oracle: expf against NumPy's float32 exp
+
+
+def same(got, want, gaussian, label):
+    """boolean frames bit-exact; Gaussian frames the same non-zero voxels and values within RTOL, ATOL"""
+    assert got.dtype == want.dtype and got.shape == want.shape
+    if not gaussian:
+        print(f"{label}: {int(want.sum())} cells set, {int(np.count_nonzero(got != want))} differ")
+        assert np.array_equal(got, want)                                      # bit-exact
+        return
+    g, w = got.astype(np.float64), want.astype(np.float64)
+    worst = float(np.max(np.abs(g - w) / (ATOL + RTOL * np.abs(w)))) if w.size else 0.0
+    print(f"{label}: {int(np.count_nonzero(want))} non-zero, support differs in {int(np.count_nonzero((got != 0) != (want != 0)))}, "
+          f"worst |got - want| / (atol + rtol |want|) = {worst:.3f}")
+    assert not np.isnan(got).any()
+    assert np.array_equal(got != 0, want != 0)                                # the same voxels are touched
+    np.testing.assert_allclose(got, want, rtol=RTOL, atol=ATOL)
+
+
+def decoy(cloud, C):
+    """the same coordinates with the encodable channels rotated by one, and no frame"""
+    ch = np.where((cloud.ch >= 0) & (cloud.ch < C), (cloud.ch + 1) % C, cloud.ch).astype(np.int32)
+    return Cloud(cloud.xyz, ch, cloud.sg, cloud.frt[:0])
+
+
+def mixed_clouds():
+    """(18 clouds, (V, edge, C)): nine structures of the (21, 21.0, 5) geometry, each followed by its decoy"""
+    V, edge, C = 21, 21.0, 5
+    cases = one_launch_cases()
+    row = frame_row(np.random.default_rng(5))
+    real = [cases["batch-3"].cloud, Cloud(np.zeros((0, 3), np.float32), np.zeros(0, np.int32), np.zeros(0, np.float32), row[None, :]),
+            cases["chunking-gauss"].cloud]
+    real += [interior_cloud(V, edge, C, 1, 701)] + [uniform_cloud(V, edge, C, n, 700 + n) for n in (255, 256, 257)]
+    real += [cases["nonfinite"].cloud, Cloud(*uniform_cloud(V, edge, C, 300, 990)[:3], np.zeros((0, 12), np.float32))]
+    return [c for r in real for c in (r, decoy(r, C))], (V, edge, C)
+
+
+def weight_inputs():
+    """(case, weights from {-1, 1, 2.5}, signs +-1, channels that put the positive atoms in 0 and the negative ones in 1): what the
+    weights test of tests/test_gpu_voxelise_batch.py feeds the kernel"""
+    case = sweep_gaussian(9, 12.5, 8)
+    cloud = case.cloud
+    rng = np.random.default_rng(17)
+    wgt = rng.choice(np.array([-1.0, 1.0, 2.5], np.float32), len(cloud.xyz))
+    keep = (cloud.ch >= 0) & (cloud.ch < case.C)
+    sign = np.where(rng.random(len(cloud.xyz)) < 0.5, -1.0, 1.0).astype(np.float32)
+    two = np.where(keep, np.where(sign > 0, 0, 1), -1).astype(np.int32)
+    return case, wgt, sign, two
+
+
+# ---- the bytes of the commit before the two voxeliser kernels became one (tests/golden/voxelise_digests.json) -------------------
+
+UBQ_DIGEST = "1ubq/five"              # the 76 five-channel Gaussian frames of tests/golden/1ubq.pdb1.gz
+
+
+def digest_cases():
+    """[(id, cloud, V, edge, C, gaussian)]: every synthetic th_voxelise call whose bytes tests/golden/make_voxelise_digests.py records"""
+    calls = []
+    for V, edge, C in SWEEP:
+        for which, case in (("bool-cloud", sweep_boolean(V, edge, C)), ("gauss-cloud", sweep_gaussian(V, edge, C))):
+            calls += [(f"sweep/{V}-{edge}-{C}/{which}/{mode(g)}", case.cloud, V, edge, C, g) for g in (False, True)]
+    clouds, (V, edge, C) = mixed_clouds()
+    calls += [(f"mixed/{s}/{mode(g)}", c, V, edge, C, g) for s, c in enumerate(clouds) for g in (False, True)]
+    case = one_launch_cases()["batch-300"]
+    calls += [(f"batch-300/{mode(g)}", case.cloud, case.V, case.edge, case.C, g) for g in (False, True)]
+    case, _wgt, _sign, two = weight_inputs()
+    calls.append(("weights/unit", case.cloud, case.V, case.edge, case.C, True))
+    calls.append(("weights/two-channel", Cloud(case.cloud.xyz, two, case.cloud.sg, case.cloud.frt), case.V, case.edge, 2, True))
+    return calls
+
+
+def mode(gaussian):
+    return "gaussian" if gaussian else "boolean"
+
+
+def digest(frames):
+    a = np.ascontiguousarray(frames)
+    return dict(shape=list(a.shape), dtype=str(a.dtype), sha256=hashlib.sha256(a.tobytes()).hexdigest())
+
+
+_RECORDED = {}
+
+
+def assert_parent_bytes(frames, case_id):
+    """shape, dtype and SHA-256 of ``frames`` are those recorded under ``case_id`` at the parent commit"""
+    if not _RECORDED:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "voxelise_digests.json")) as f:
+            _RECORDED.update(json.load(f)["cases"])
+    assert digest(frames) == _RECORDED[case_id], case_id

@@ -204,8 +204,8 @@ def _prepare(model, encode_cb, atom_encoder, uncommon, property, property_map, n
 
 def voxelise(atoms_xyz, atom_channel, atom_sigma, frames_rt, voxels_per_side: int = 21, frame_edge_length: float = 21.0,
              n_channels: int = 5, gaussian: bool = True, device: int = 0, d_out: Optional[int] = None) -> Optional[np.ndarray]:
-    """Run the kernel (th_voxelise).  Returns frames [n_res, V, V, V, C] (float32 for Gaussian, uint8 for boolean frames),
-    or None when ``d_out`` (a device address with room for them) is given: the frames then stay in HBM for
+    """The frames of one structure (th_voxelise: the one-structure, unit-weight case of th_voxelise_batch).  Returns frames
+    [n_res, V, V, V, C] (float32 for Gaussian, uint8 for boolean frames), or None when ``d_out`` (a device address with room for them) is given: the frames then stay in HBM for
     th_predict_device."""
     lib = _lib.load()
     xyz = np.ascontiguousarray(atoms_xyz, dtype=np.float32)
@@ -278,14 +278,10 @@ def voxelise_pdb(path, voxels_per_side: int = 21, frame_edge_length: float = 21.
     frames, labels, flat = [], [], []
     for k, model in enumerate(models):
         name = f"{code}_{k}" if all_states else code
-        if property is None:
-            xyz, ch, sg, frt, rows = prepare_structure(model, encode_cb=encode_cb, atom_encoder=atom_encoder)
-            frames.append(voxelise(xyz, ch, sg, frt, voxels_per_side, frame_edge_length, n_channels, gaussian, device))
-        else:
-            xyz, ch, sg, wt, frt, rows = prepare_structure_with_property(model, property, map_of(property_map, name), encode_cb=encode_cb,
-                                                                         atom_encoder=atom_encoder, name=name)
-            frames.append(voxelise_batch(xyz, ch, sg, wt, [0, len(xyz)], frt, np.zeros(len(frt), np.int32), voxels_per_side,
-                                         frame_edge_length, n_channels, True, device))
+        xyz, ch, sg, wt, frt, rows = prepare_structure_with_property(model, property, map_of(property_map, name), encode_cb=encode_cb,
+                                                                     atom_encoder=atom_encoder, name=name)
+        frames.append(voxelise_batch(xyz, ch, sg, wt if property is not None else None, [0, len(xyz)], frt, np.zeros(len(frt), np.int32),
+                                     voxels_per_side, frame_edge_length, n_channels, gaussian, device))
         for chain, number, label in rows:
             flat.append((name, chain, number, label))
             onehot = np.zeros(20, np.uint8)
