@@ -13,20 +13,8 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import winograd_numerics as wn  # noqa: E402
 from oracle import cnn_oracle  # noqa: E402
+from split_products import _bf16, _split3  # noqa: E402
 from timed_hip import synth  # noqa: E402
-
-
-def _bf16(x):
-    """round to nearest even to bfloat16, returned as float32"""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000
-    return u.astype(np.uint32).view(np.float32)
-
-
-def _split3(x):
-    h = _bf16(x)
-    m = _bf16(x - h)
-    return h, m, _bf16(x - h - m)
 
 
 def test_three_bf16_pieces_hold_every_float32_exactly():
