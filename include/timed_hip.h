@@ -515,7 +515,8 @@ int th_superpose(int device, const double* ref_xyz, const double* mob_xyz, int64
  *     not the mean of lddt_i.
  * MIRROR IMAGES: every distance of a mirror image is that of the original, so lDDT does not see one — the mirror case of the
  * superposition fixture scores 1.0 here where th_superpose reports 10.7 Angstrom.  Conversely one re-oriented domain costs
- * th_superpose everything and lDDT only the pairs across the hinge.  That is the reason to report both.
+ * th_superpose everything and lDDT only the pairs across the hinge.  That is the reason to report both.  (th_tmscore, below,
+ * superposes with a proper rotation and scores that mirror image 0.308.)
  * All outputs are integers decided by float64 comparisons: a pair's outputs depend on its own coordinates alone — not on its place
  * in the batch or on its neighbours — and two calls give the same bytes.  No atomics.  Device memory: 68 bytes per position + 8 per
  * 256 positions of every pair + 56 per pair; the O(L^2) distances exist in registers only.  TH_EINVAL, before anything is launched
@@ -524,6 +525,70 @@ int th_superpose(int device, const double* ref_xyz, const double* mob_xyz, int64
  * or not > 0.  n_pairs = 0 (with total = 0) is success without a launch. */
 int th_lddt(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
             double radius, const double* thresholds, int32_t* residue_out, int64_t* pair_out, double* kernel_ms);
+
+/* ---- *** PARITY UNPINNED AGAINST THE TM-score PROGRAM *** TM-score of models against their native: analyse_models.py --tmscore —
+ * the template-modelling score (Zhang & Skolnick 2004), the "scTM against the native" of a design pipeline's self-consistency
+ * check.  It is the MAXIMUM over superpositions of sum_i 1 / (1 + (d_i / d0)^2) / L, and the superposition that attains it is in
+ * general not the least-squares fit of th_superpose: it has to be searched for.  Here for a BATCH of position-paired coordinate
+ * lists, every seed of every pair one wavefront.
+ *
+ *     *** PARITY UNPINNED AGAINST THE TM-score PROGRAM ***  Zhang & Skolnick's TMscore is not available where this project is built.
+ *     The rule below is this project's reading of the PUBLISHED definition and of the published search (fits over windows of the
+ *     chain, refined by re-fitting over the positions that came close); it is not their code, it aligns no sequences, and no test can
+ *     pin it against their program.
+ *
+ * All arrays are host memory.  ref_xyz, mob_xyz, total, offsets and n_pairs are exactly those of th_superpose, except that a pair
+ * has at most TH_TM_MAX_POSITIONS positions;
+ *   norm_len           NULL, or int32[n_pairs]: the normalisation length L of every pair, >= the pair's number of positions (the
+ *                      length of the native, when the model lacks residues).  NULL: L is the pair's number of positions;
+ *   rounds             refinement rounds per seed at most, >= 0 (the Python layer's default: 20);
+ *   tm_out             double[n_pairs][2]: tm, d0;
+ *   count_out          int64[n_pairs][4]: n_valid, L, n_seeds, n_fits;
+ *   dist_out           double[total] or NULL: d_i under the best superposition, NaN at an invalid position;
+ *   transform_out      double[n_pairs][12] or NULL: rows of [R | t] of the best superposition, as th_superpose (the identity when
+ *                      no position is valid);
+ *   kernel_ms          NULL, or receives the device time of the two kernels (events around them), in milliseconds.
+ * The rule, for one pair of n positions ref[i], mob[i], all arithmetic float64 and no fused multiply-add:
+ *   - a position is VALID when all six of its coordinates are finite.  m is the number of valid positions; they are kept in index
+ *     order, and "position" below means a valid one;
+ *   - L = norm_len[p] if given, else n.  d0 = th_tm_d0(L) = max(0.5, 1.24 cbrt(L - 15) - 1.8) for L > 15, else 0.5, computed on the
+ *     host.  d_search = min(max(d0, 4.5), 8.0);
+ *   - the SCORE of a superposition is (sum over the positions in index order of 1 / (1 + (d_i / d0)^2)) / L, with d_i formed as in
+ *     th_superpose: moved = R (mob - cm) + cr, then the square root of the three squares.  (The kernel sums each lane's positions
+ *     l, l + 64, ... in index order and then the 64 lanes in a fixed tree.)
+ *   - SEEDS: the window lengths are W = m, then W <- W div 2 for as long as the halved value is >= 4; for every W in that order,
+ *     every start s = 0 .. m - W is a seed, its set the positions s .. s + W - 1.  n_seeds is their number (239 for m = 76, 1 for
+ *     m <= 7);
+ *   - per seed, rounds r = 0 .. rounds: FIT over the set by the rule of th_superpose (centroids, two-pass cross-covariance, Horn's
+ *     matrix, cyclic Jacobi, the proper rotation); the d_i of all positions and the SCORE; a SCORE strictly greater than the best
+ *     so far replaces it.  After round `rounds` the seed ends.  Otherwise cut = d_search - 1 in round 0 and d_search + 1 afterwards,
+ *     and the new set is the positions with d_i < cut (strict); while it holds fewer than min(3, m) positions, cut += 0.5 and the
+ *     selection is made again (at most TH_TM_MAX_WIDENINGS times — no structure gets there; the seed ends if that is not enough).
+ *     If the new set equals the current one the seed ends, otherwise it is the set of the next round.  n_fits counts every fit of
+ *     every seed;
+ *   - the pair's tm is the best SCORE over its seeds; of equal scores the first seed and round wins.  transform_out and dist_out
+ *     are that superposition;
+ *   - m = 0 (and a pair none of whose scores is a number): tm is NaN, dist_out NaN and the transform the identity; with m = 0,
+ *     n_seeds = n_fits = 0.
+ * MIRROR IMAGES: the rotation is proper, so a mirror image scores low here — 0.308 for the mirror case of the superposition
+ * fixture, which lDDT (above) scores 1.0 and th_superpose reports as 10.7 Angstrom.  A re-oriented domain costs TM-score only its
+ * own positions: the hinge case of that fixture scores 0.904 here, 0.661 under the one global fit of th_superpose, and 0.906 by lDDT.
+ * k_tm_seeds runs one wavefront per (pair, seed) with the seed's set as one 64-bit mask per lane in registers (hence 64 x 64 = 4096
+ * positions at most) and leaves 12 bytes per seed; k_tm_best, one wavefront per pair, takes the first maximum and runs that one
+ * seed again to write the pair's outputs.  No atomics.  A pair's outputs depend on its own coordinates and L alone — not on its
+ * place in the batch or on its neighbours — and two calls give the same bytes.  Device memory: 48 bytes per valid position + 4 (12
+ * with dist_out) per position + 12 per seed + 104 (200 with transform_out) per pair.  TH_EINVAL, before anything is launched or
+ * written: the cases of th_superpose (a negative or too large size, a NULL that is required — offsets, tm_out, count_out; with
+ * total > 0 also both lists —, offsets that decrease, do not start at 0 or do not end at total), rounds < 0, a norm_len[p] below the
+ * pair's number of positions, a pair of more than TH_TM_MAX_POSITIONS positions, more than 2^31 - 1 seeds in one call.  n_pairs = 0
+ * (with total = 0) is success without a launch. */
+#define TH_TM_MAX_POSITIONS 4096
+#define TH_TM_MAX_WIDENINGS 4096
+int th_tmscore(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
+               const int32_t* norm_len, int rounds, double* tm_out, int64_t* count_out, double* dist_out, double* transform_out,
+               double* kernel_ms);
+/* max(0.5, 1.24 cbrt(L - 15) - 1.8) for L > 15, else 0.5: the scale d0 of the TM-score for normalisation length L.  Host code. */
+double th_tm_d0(int64_t L);
 
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked

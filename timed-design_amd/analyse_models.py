@@ -35,6 +35,18 @@ PARITY UNPINNED AGAINST OPENSTRUCTURE: neither OpenStructure nor AlphaFold's ldd
 this project's reading of the published definition (Mariani et al. 2013) in the CA-only form AlphaFold uses, written out in
 include/timed_hip.h and timed_hip/lddt.py: one position per residue, no stereochemistry checks, strict inequalities on both tests, the
 global score weighted by pairs (not the mean of the per-residue scores).
+
+--tmscore additionally writes ``model_tmscore.csv``, one row per pair — label, reference, model, n_valid, norm_length (the residues
+of the reference that have a CA atom: what the model lacks of them costs score), d0, tm_score, tm_global_fit (the same sum under the
+ONE least-squares fit over all positions, th_superpose with cycles 0: beside tm_score it shows what the search bought), n_seeds, n_fits,
+error.  TM-score is the maximum over superpositions of sum 1 / (1 + (d_i / d0)^2) / norm_length; the superposition that attains it is
+searched for from every window of the chain (--tm_rounds refinement rounds per seed at most), a re-oriented domain costs only its own
+positions, and a mirror image scores low (the rotation is proper).  At most 4096 positions per pair.  The files parsed for the
+superposition are reused.
+
+PARITY UNPINNED AGAINST THE TM-score PROGRAM: Zhang & Skolnick's TMscore is not available to pin this against.  The rule is this
+project's reading of the published definition and search, written out in include/timed_hip.h and timed_hip/tmscore.py.  It aligns no
+sequences (that is TM-align).
 """
 import argparse
 import csv
@@ -43,6 +55,7 @@ from pathlib import Path
 
 from timed_hip import lddt as lddt_module
 from timed_hip import superpose
+from timed_hip import tmscore as tmscore_module
 from timed_hip.pdbio import find_structures
 from timed_hip.textio import float_repr as _fmt
 
@@ -52,6 +65,7 @@ RESIDUE_COLUMNS = ["label", "chain", "residue_number", "distance", "kept"]
 LDDT_COLUMNS = ["label", "reference", "model", "n_valid", "n_included", "lddt", "preserved_0.5", "preserved_1", "preserved_2", "preserved_4",
                 "mean_model_bfactor", "error"]
 RESIDUE_LDDT_COLUMNS = ["label", "chain", "number", "residue", "n_included", "lddt", "model_bfactor"]
+TMSCORE_COLUMNS = ["label", "reference", "model", "n_valid", "norm_length", "d0", "tm_score", "tm_global_fit", "n_seeds", "n_fits", "error"]
 
 
 def read_pairs(path):
@@ -84,6 +98,28 @@ def write_lddt(out, todo, scores):
                 wr.writerow([label, r.chain, r.number, r.name, n, _fmt(score), _fmt(b)])
 
 
+def tm_sum(dist, d0, norm_length):
+    """sum over the numbers of ``dist``, in index order, of 1 / (1 + (d / d0)^2), divided by ``norm_length``: NaN when there is none"""
+    total, seen = 0.0, False
+    for d in dist.tolist():
+        if d == d:
+            q = d / d0
+            total += 1.0 / (1.0 + q * q)
+            seen = True
+    return total / norm_length if seen else float("nan")
+
+
+def write_tmscore(out, todo, scores, global_fits):
+    """model_tmscore.csv; ``global_fits``: the results of th_superpose with cycles = 0 for the same pairs"""
+    with open(out / "model_tmscore.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(TMSCORE_COLUMNS)
+        for (label, ref, model), res, once in zip(todo, scores, global_fits):
+            whole = float("nan") if res.error or once.error else tm_sum(once.dist, res.d0, res.norm_length)
+            w.writerow([label, str(ref), str(model), res.n_valid, res.norm_length, _fmt(res.d0), _fmt(res.tm), _fmt(whole), res.n_seeds, res.n_fits,
+                        res.error or ""])
+
+
 def main(args):
     if args.pairs:
         if args.path_to_reference or args.path_to_models:
@@ -100,6 +136,8 @@ def main(args):
         sys.exit("no pair to score: no *.pdb / *.pdb1 / *.ent (.gz) file under --path_to_models, or an empty --pairs file")
     if args.lddt and not (args.lddt_radius > 0 and args.lddt_radius < float("inf")):
         sys.exit(f"--lddt_radius {args.lddt_radius} is not a positive finite number")
+    if args.tmscore and args.tm_rounds < 0:
+        sys.exit(f"--tm_rounds {args.tm_rounds} is negative")
     stats = {}
     prepared = superpose.prepare([(ref, model) for _, ref, model in todo], args.pair_by, "CA", args.workers)     # read and paired once for both scores
     results = superpose.superpose(prepared, cycles=args.cycles, cutoff=args.cutoff, device=args.device, stats=stats)
@@ -107,6 +145,9 @@ def main(args):
     out.mkdir(parents=True, exist_ok=True)
     if args.lddt:
         write_lddt(out, todo, lddt_module.lddt(prepared, radius=args.lddt_radius, device=args.device, stats=stats))
+    if args.tmscore:
+        write_tmscore(out, todo, tmscore_module.tmscore(prepared, rounds=args.tm_rounds, device=args.device, stats=stats),
+                      superpose.superpose(prepared, cycles=0, device=args.device, stats=stats))
     with open(out / "model_scores.csv", "w", newline="") as fs, open(out / "residue_deviation.csv", "w", newline="") as fr:
         ws, wr = csv.writer(fs), csv.writer(fr)
         ws.writerow(SCORE_COLUMNS)
@@ -141,6 +182,11 @@ CLI_FLAGS = (
                     help="also write model_lddt.csv and residue_lddt.csv: the lDDT of every model and residue (CA atoms, thresholds 0.5, 1, 2, 4), "
                          "a superposition-free score, beside the model's B-factor (AlphaFold2's pLDDT).  PARITY UNPINNED AGAINST OPENSTRUCTURE")),
     ("--lddt_radius", dict(type=float, default=15.0, help="inclusion radius of --lddt in the reference structure (default 15.0)")),
+    ("--tmscore", dict(action="store_true",
+                       help="also write model_tmscore.csv: the TM-score of every model (CA atoms, normalised by the reference's length), the "
+                            "maximum over superpositions found by a search on the GPU, beside the same sum under the one global fit.  At most "
+                            "4096 positions per pair.  PARITY UNPINNED AGAINST THE TM-score PROGRAM")),
+    ("--tm_rounds", dict(type=int, default=20, help="refinement rounds per seed of --tmscore at most (default 20)")),
 )
 
 

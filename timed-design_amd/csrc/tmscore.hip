@@ -1,0 +1,442 @@
+// th_tmscore: the TM-score (Zhang & Skolnick 2004) of a BATCH of position-paired coordinate lists — the CA atoms of a model against
+// those of its native — as the maximum over a fixed schedule of seed superpositions, each refined by a short fixed-point iteration
+// of least-squares fits.  The fit is that of th_superpose (horn_fit.h); the search is what th_superpose does not have.
+//
+//     *** PARITY UNPINNED AGAINST THE TM-score PROGRAM ***  Zhang & Skolnick's TMscore is not available where this project is built.
+//     The rule — written out in include/timed_hip.h — is this project's reading of the published definition and search; it is not
+//     their code and no test can pin it against their program.
+//
+// The host counts the valid positions of every pair, compacts them and knows from that count alone how many seeds a pair has.
+// k_tm_seeds: one wavefront per (pair, seed), four per 256-thread workgroup.  Lane l owns compacted positions l, l + 64, ... of its
+// pair, and the current set of the seed is ONE 64-bit mask per lane in registers (bit b: position l + 64 b) — hence at most
+// 64 x 64 = 4096 positions per pair.  "The set did not change" is a wave-wide AND of mask equality.  No per-seed memory, no LDS, no
+// barrier: the coordinates are read from global memory (L2) in every pass, the sums are the xor butterflies of horn_fit.h, every lane
+// solves the 4 x 4 eigenproblem itself.  A seed leaves 12 bytes: its best score and the number of fits it made.
+// k_tm_best: one wavefront per pair scans those scores for the first maximum, sums the fits and RUNS THAT ONE SEED AGAIN — the same
+// device function, so the same bits — this time keeping the superposition of its best round, and writes the pair's outputs.
+// A pair's arithmetic depends on its own coordinates alone: not on the grid, not on its neighbours; two calls give the same bytes.
+// No atomics.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <vector>
+
+#include "common.h"
+#include "horn_fit.h"
+
+namespace {
+
+constexpr int kBlock = 256;                       // threads per workgroup
+constexpr int kPerBlock = kBlock / kWave;         // wavefronts (seeds, or pairs) per workgroup
+constexpr int kWidenings = TH_TM_MAX_WIDENINGS;
+
+struct TmPair {                                   // one per pair, and one more that ends the seed offsets
+    long long lo, n;                              // its positions in the caller's lists
+    long long clo, m;                             // its valid positions in the compacted lists
+    long long slo;                                // its first seed
+    long long L;                                  // normalisation length
+    double d0;
+};
+
+__device__ inline long long wave_sum_ll(long long v) {
+    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+    return v;
+}
+
+// d of compacted position c under moved = R (mob - cm) + cr
+__device__ inline double tm_dist(const double* __restrict__ ref, const double* __restrict__ mob, int c, const double (&cm)[3],
+                                 const double (&cr)[3], const double (&R)[9]) {
+    const double ax = mob[3 * c] - cm[0], ay = mob[3 * c + 1] - cm[1], az = mob[3 * c + 2] - cm[2];
+    const double dx = (((R[0] * ax + R[1] * ay) + R[2] * az) + cr[0]) - ref[3 * c];
+    const double dy = (((R[3] * ax + R[4] * ay) + R[5] * az) + cr[1]) - ref[3 * c + 1];
+    const double dz = (((R[6] * ax + R[7] * ay) + R[8] * az) + cr[2]) - ref[3 * c + 2];
+    return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
+// (W, s) of seed k of a pair with m valid positions: the window lengths m, m div 2, ... >= 4, every start of each
+__device__ inline void tm_window(int m, long long k, int& W, int& s) {
+    W = m;
+    while (k >= m - W + 1) {                      // k < n_seeds(m), so the walk ends before W div 2 < 4
+        k -= m - W + 1;
+        W /= 2;
+    }
+    s = (int)k;
+}
+
+// One seed: rounds 0 .. `rounds` of fit, score, select.  Returns the best SCORE of the seed (-infinity if none compared greater),
+// counts its fits and, with kKeep, leaves the superposition of the first round that reached that score.
+template <bool kKeep>
+__device__ inline double tm_seed(const double* __restrict__ ref, const double* __restrict__ mob, int m, int W, int s, double d0,
+                                 double d_search, double L, int rounds, int lane, int& fits, double (&bcm)[3], double (&bcr)[3], double (&bR)[9]) {
+    const int nb = lane < m ? (m - lane + kWave - 1) / kWave : 0;      // positions this lane owns, <= 64
+    const int need = m < 3 ? m : 3;
+    unsigned long long cur = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int c = lane + kWave * b;
+        if (c >= s && c < s + W) cur |= 1ull << b;
+    }
+    double best = -__builtin_inf();
+    fits = 0;
+    for (int r = 0;; ++r) {
+        const double count = (double)wave_sum((int)__popcll(cur));
+        double sm[3] = {0.0, 0.0, 0.0}, sr[3] = {0.0, 0.0, 0.0}, cm[3], cr[3];
+        for (int b = 0; b < nb; ++b)
+            if ((cur >> b) & 1) {
+                const int c = lane + kWave * b;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    sm[a] += mob[3 * c + a];
+                    sr[a] += ref[3 * c + a];
+                }
+            }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            cm[a] = wave_sum(sm[a]) / count;
+            cr[a] = wave_sum(sr[a]) / count;
+        }
+        double S[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+        for (int b = 0; b < nb; ++b)
+            if ((cur >> b) & 1) {
+                const int c = lane + kWave * b;
+                double a[3], e[3];
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+                    a[x] = mob[3 * c + x] - cm[x];
+                    e[x] = ref[3 * c + x] - cr[x];
+                }
+#pragma unroll
+                for (int x = 0; x < 3; ++x)
+#pragma unroll
+                    for (int y = 0; y < 3; ++y) S[x][y] += a[x] * e[y];
+            }
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) S[x][y] = wave_sum(S[x][y]);
+        double R[9];
+        horn_rotation(S, R);
+        ++fits;
+        // the score of this superposition over every valid position, and the next set in the same pass
+        double cut = r == 0 ? d_search - 1.0 : d_search + 1.0;
+        double sum = 0.0;
+        unsigned long long next = 0;
+        for (int b = 0; b < nb; ++b) {
+            const double d = tm_dist(ref, mob, lane + kWave * b, cm, cr, R);
+            const double q = d / d0;
+            sum += 1.0 / (1.0 + q * q);
+            if (d < cut) next |= 1ull << b;
+        }
+        const double score = wave_sum(sum) / L;
+        if (score > best) {
+            best = score;
+            if (kKeep) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    bcm[a] = cm[a];
+                    bcr[a] = cr[a];
+                }
+#pragma unroll
+                for (int a = 0; a < 9; ++a) bR[a] = R[a];
+            }
+        }
+        if (r >= rounds) break;
+        int chosen = wave_sum((int)__popcll(next));
+        for (int widened = 0; chosen < need && widened < kWidenings; ++widened) {      // uniform: both are the same in every lane
+            cut += 0.5;
+            next = 0;
+            for (int b = 0; b < nb; ++b)
+                if (tm_dist(ref, mob, lane + kWave * b, cm, cr, R) < cut) next |= 1ull << b;
+            chosen = wave_sum((int)__popcll(next));
+        }
+        if (chosen < need || __all(next == cur)) break;
+        cur = next;
+    }
+    return best;
+}
+
+// kStage exists in the knock-out build only (common.h, TH_TM_STAGE=1): the workgroup first copies the coordinates of its first
+// wavefront's pair into LDS and the wavefronts of that pair read them from there.  Measured and not adopted: profiles/tmscore.txt.
+template <bool kStage>
+__global__ void __launch_bounds__(kBlock) k_tm_seeds(const double* __restrict__ cref, const double* __restrict__ cmob, const TmPair* __restrict__ pairs,
+                                                     long long n_pairs, long long n_seeds, int rounds, double* __restrict__ seed_score,
+                                                     int* __restrict__ seed_fits, int stage_positions) {
+    const long long g = (long long)blockIdx.x * kPerBlock + threadIdx.x / kWave;
+    if (!kStage && g >= n_seeds) return;                               // the whole wavefront leaves
+    const int lane = threadIdx.x % kWave;
+    const long long mine = g < n_seeds ? g : n_seeds - 1;
+    long long lo = 0, hi = n_pairs;                                    // the first pair whose seeds end beyond this one
+    while (lo < hi) {
+        const long long mid = (lo + hi) / 2;
+        if (pairs[mid + 1].slo <= mine) lo = mid + 1; else hi = mid;
+    }
+    const TmPair p = pairs[lo];
+    int W, s, fits;
+    tm_window((int)p.m, mine - p.slo, W, s);
+    const double d_search = fmin(fmax(p.d0, 4.5), 8.0);
+    double cm[3], cr[3], R[9], best;
+#if TH_KNOCKOUTS
+    if (kStage) {
+        extern __shared__ double staged[];
+        __shared__ long long first_pair;
+        if (threadIdx.x == 0) first_pair = lo;
+        __syncthreads();
+        const TmPair f = pairs[first_pair];
+        for (int i = threadIdx.x; i < 3 * (int)f.m; i += kBlock) {
+            staged[i] = cref[3 * f.clo + i];
+            staged[3 * stage_positions + i] = cmob[3 * f.clo + i];
+        }
+        __syncthreads();
+        if (g >= n_seeds) return;
+        if (lo == first_pair) {
+            best = tm_seed<false>(staged, staged + 3 * stage_positions, (int)p.m, W, s, p.d0, d_search, (double)p.L, rounds, lane, fits, cm, cr, R);
+            if (lane == 0) {
+                seed_score[g] = best;
+                seed_fits[g] = fits;
+            }
+            return;
+        }
+    }
+#endif
+    best = tm_seed<false>(cref + 3 * p.clo, cmob + 3 * p.clo, (int)p.m, W, s, p.d0, d_search, (double)p.L, rounds, lane, fits, cm, cr, R);
+    if (lane == 0) {
+        seed_score[g] = best;
+        seed_fits[g] = fits;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_tm_best(const double* __restrict__ cref, const double* __restrict__ cmob, const TmPair* __restrict__ pairs,
+                                                    const int* __restrict__ cidx, long long n_pairs, int rounds, const double* __restrict__ seed_score,
+                                                    const int* __restrict__ seed_fits, double* __restrict__ tm_out, long long* __restrict__ count_out,
+                                                    double* __restrict__ dist_out, double* __restrict__ transform_out) {
+    const long long pair = (long long)blockIdx.x * kPerBlock + threadIdx.x / kWave;
+    if (pair >= n_pairs) return;
+    const int lane = threadIdx.x % kWave;
+    const TmPair p = pairs[pair];
+    const long long n_seeds = pairs[pair + 1].slo - p.slo;
+    // the first maximum of the seeds' scores: every lane its own seeds in order, then the lanes
+    double top = -__builtin_inf();
+    long long at = LLONG_MAX, fits_all = 0;
+    for (long long k = lane; k < n_seeds; k += kWave) {
+        const double v = seed_score[p.slo + k];
+        fits_all += seed_fits[p.slo + k];
+        if (v > top) {
+            top = v;
+            at = k;
+        }
+    }
+    for (int mask = kWave / 2; mask >= 1; mask >>= 1) {
+        const double v = __shfl_xor(top, mask, kWave);
+        const long long k = __shfl_xor(at, mask, kWave);
+        if (v > top || (v == top && k < at)) {
+            top = v;
+            at = k;
+        }
+    }
+    fits_all = wave_sum_ll(fits_all);
+    const double nan = __builtin_nan("");
+    double cm[3] = {0.0, 0.0, 0.0}, cr[3] = {0.0, 0.0, 0.0};
+    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    double tm = nan;
+    const double* ref = cref + 3 * p.clo;
+    const double* mob = cmob + 3 * p.clo;
+    const bool found = at != LLONG_MAX;                                // uniform: every lane holds the same (top, at)
+    if (found) {
+        int W, s, fits;
+        tm_window((int)p.m, at, W, s);
+        tm = tm_seed<true>(ref, mob, (int)p.m, W, s, p.d0, fmin(fmax(p.d0, 4.5), 8.0), (double)p.L, rounds, lane, fits, cm, cr, R);
+    }
+    if (dist_out)
+        for (long long i = lane; i < p.n; i += kWave) {
+            const int c = cidx[p.lo + i];                              // the compacted index of position i, -1 at an invalid one
+            dist_out[p.lo + i] = found && c >= 0 ? tm_dist(ref, mob, c, cm, cr, R) : nan;
+        }
+    if (lane != 0) return;
+    tm_out[2 * pair] = tm;
+    tm_out[2 * pair + 1] = p.d0;
+    long long* count = count_out + 4 * pair;
+    count[0] = p.m;
+    count[1] = p.L;
+    count[2] = n_seeds;
+    count[3] = fits_all;
+    if (transform_out) {                                               // moved = R mob + t, t = cr - R cm; the identity when nothing is valid
+        double* t = transform_out + 12 * pair;
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            t[4 * x] = R[3 * x];
+            t[4 * x + 1] = R[3 * x + 1];
+            t[4 * x + 2] = R[3 * x + 2];
+            t[4 * x + 3] = cr[x] - ((R[3 * x] * cm[0] + R[3 * x + 1] * cm[1]) + R[3 * x + 2] * cm[2]);
+        }
+    }
+}
+
+struct TmCall {
+    int device = -1;
+    hipStream_t st = nullptr;
+    unsigned char* mem = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~TmCall() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (mem) (void)hipFree(mem);
+    }
+};
+
+size_t tm_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+long long tm_seed_count(long long m) {
+    long long seeds = 0;
+    for (long long W = m; W >= 1; W /= 2) {
+        seeds += m - W + 1;
+        if (W / 2 < 4) break;
+    }
+    return seeds;
+}
+
+}  // namespace
+
+extern "C" double th_tm_d0(int64_t L) {
+    if (L <= 15) return 0.5;
+    const double d0 = 1.24 * std::cbrt((double)(L - 15)) - 1.8;
+    return d0 > 0.5 ? d0 : 0.5;
+}
+
+extern "C" int th_tmscore(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
+                          const int32_t* norm_len, int rounds, double* tm_out, int64_t* count_out, double* dist_out, double* transform_out,
+                          double* kernel_ms) {
+    if (total < 0 || n_pairs < 0) TH_FAIL(TH_EINVAL, "th_tmscore: negative size (total = %lld, n_pairs = %lld)", (long long)total, (long long)n_pairs);
+    if (total > INT_MAX || n_pairs > INT_MAX)
+        TH_FAIL(TH_EINVAL, "th_tmscore: %lld positions / %lld pairs in one call (limit 2^31 - 1 each)", (long long)total, (long long)n_pairs);
+    if (rounds < 0) TH_FAIL(TH_EINVAL, "th_tmscore: rounds = %d is negative", rounds);
+    if (n_pairs == 0) {
+        if (total != 0) TH_FAIL(TH_EINVAL, "th_tmscore: n_pairs = 0 owns no position, total = %lld", (long long)total);
+        if (kernel_ms) *kernel_ms = 0.0;
+        return TH_OK;
+    }
+    if (!offsets || !tm_out || !count_out || (total > 0 && (!ref_xyz || !mob_xyz)))
+        TH_FAIL(TH_EINVAL, "th_tmscore: n_pairs = %lld needs offsets, tm_out and count_out, total = %lld needs ref_xyz and mob_xyz", (long long)n_pairs,
+                (long long)total);
+    if (offsets[0] != 0 || offsets[n_pairs] != total)
+        TH_FAIL(TH_EINVAL, "th_tmscore: offsets run from %lld to %lld, not from 0 to total = %lld", (long long)offsets[0], (long long)offsets[n_pairs],
+                (long long)total);
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        if (offsets[p + 1] < offsets[p]) TH_FAIL(TH_EINVAL, "th_tmscore: offsets[%lld] > offsets[%lld]", (long long)p, (long long)p + 1);
+        const int64_t n = offsets[p + 1] - offsets[p];
+        if (n > TH_TM_MAX_POSITIONS)
+            TH_FAIL(TH_EINVAL, "th_tmscore: pair %lld has %lld positions (limit TH_TM_MAX_POSITIONS = %d)", (long long)p, (long long)n, TH_TM_MAX_POSITIONS);
+        if (norm_len && norm_len[p] < n)
+            TH_FAIL(TH_EINVAL, "th_tmscore: norm_len[%lld] = %d is below the pair's %lld positions", (long long)p, (int)norm_len[p], (long long)n);
+    }
+
+    // the valid positions of every pair, compacted in index order; a pair's seeds follow from their number
+    const size_t n = (size_t)total, np = (size_t)n_pairs;
+    std::vector<TmPair> pairs(np + 1);
+    std::vector<int> cidx(n);
+    std::vector<double> cref, cmob;
+    cref.reserve(3 * n);
+    cmob.reserve(3 * n);
+    long long n_seeds = 0;
+    for (size_t p = 0; p < np; ++p) {
+        TmPair& q = pairs[p];
+        q.lo = offsets[p];
+        q.n = offsets[p + 1] - offsets[p];
+        q.clo = (long long)(cref.size() / 3);
+        for (long long i = q.lo; i < q.lo + q.n; ++i) {
+            const double* r = ref_xyz + 3 * i;
+            const double* m = mob_xyz + 3 * i;
+            const bool ok = std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(m[2]);
+            cidx[(size_t)i] = ok ? (int)(cref.size() / 3 - (size_t)q.clo) : -1;
+            if (ok) {
+                cref.insert(cref.end(), r, r + 3);
+                cmob.insert(cmob.end(), m, m + 3);
+            }
+        }
+        q.m = (long long)(cref.size() / 3) - q.clo;
+        q.slo = n_seeds;
+        q.L = norm_len ? norm_len[p] : q.n;
+        q.d0 = th_tm_d0(q.L);
+        n_seeds += tm_seed_count(q.m);
+    }
+    pairs[np] = TmPair{total, 0, (long long)(cref.size() / 3), 0, n_seeds, 0, 0.5};
+    if (n_seeds > INT_MAX)
+        TH_FAIL(TH_EINVAL, "th_tmscore: %lld seeds in one call (limit 2^31 - 1): submit fewer pairs at once", n_seeds);
+    const size_t nc = cref.size() / 3, ns = (size_t)n_seeds;
+
+    TmCall call;
+    HIP_TRY(hipSetDevice(device));
+    call.device = device;
+    const size_t off_mob = tm_align(nc * 3 * sizeof(double));
+    const size_t off_pairs = off_mob + tm_align(nc * 3 * sizeof(double));
+    const size_t off_cidx = off_pairs + tm_align((np + 1) * sizeof(TmPair));
+    const size_t off_score = off_cidx + tm_align(n * sizeof(int));
+    const size_t off_fits = off_score + tm_align(ns * sizeof(double));
+    const size_t off_tm = off_fits + tm_align(ns * sizeof(int));
+    const size_t off_count = off_tm + tm_align(np * 2 * sizeof(double));
+    const size_t off_dist = off_count + tm_align(np * 4 * sizeof(int64_t));
+    const size_t off_tr = off_dist + tm_align(dist_out ? n * sizeof(double) : 0);
+    const size_t bytes = off_tr + tm_align(transform_out ? np * 12 * sizeof(double) : 0) + 256;       // never a zero-byte allocation
+    hipError_t e = th_malloc_retry(&call.mem, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        call.mem = nullptr;
+        th_set_error("th_tmscore: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
+    if (kernel_ms)
+        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
+    double* d_ref = (double*)call.mem;
+    double* d_mob = (double*)(call.mem + off_mob);
+    TmPair* d_pairs = (TmPair*)(call.mem + off_pairs);
+    int* d_cidx = (int*)(call.mem + off_cidx);
+    double* d_score = (double*)(call.mem + off_score);
+    int* d_fits = (int*)(call.mem + off_fits);
+    double* d_tm = (double*)(call.mem + off_tm);
+    long long* d_count = (long long*)(call.mem + off_count);
+    double* d_dist = dist_out && n ? (double*)(call.mem + off_dist) : nullptr;
+    double* d_tr = transform_out ? (double*)(call.mem + off_tr) : nullptr;
+    hipStream_t st = call.st;
+    if (nc) {
+        HIP_TRY(hipMemcpyAsync(d_ref, cref.data(), nc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_mob, cmob.data(), nc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (n) HIP_TRY(hipMemcpyAsync(d_cidx, cidx.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), (np + 1) * sizeof(TmPair), hipMemcpyHostToDevice, st));
+    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    if (ns) {
+        const dim3 grid((unsigned)((ns + kPerBlock - 1) / kPerBlock));
+        bool staged = false;
+#if TH_KNOCKOUTS
+        long long longest = 0;
+        for (size_t p = 0; p < np; ++p) longest = pairs[p].m > longest ? pairs[p].m : longest;
+        const char* knob = getenv("TH_TM_STAGE");
+        staged = knob && atoi(knob) == 1 && longest * 48 <= 64 * 1024;
+        if (staged)
+            hipLaunchKernelGGL(k_tm_seeds<true>, grid, dim3(kBlock), (size_t)longest * 48, st, d_ref, d_mob, d_pairs, (long long)n_pairs, n_seeds, rounds,
+                               d_score, d_fits, (int)longest);
+#endif
+        if (!staged)
+            hipLaunchKernelGGL(k_tm_seeds<false>, grid, dim3(kBlock), 0, st, d_ref, d_mob, d_pairs, (long long)n_pairs, n_seeds, rounds, d_score, d_fits, 0);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tm_best, dim3((unsigned)((np + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_ref, d_mob, d_pairs, d_cidx,
+                       (long long)n_pairs, rounds, d_score, d_fits, d_tm, d_count, d_dist, d_tr);
+    HIP_TRY(hipGetLastError());
+    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(hipMemcpyAsync(tm_out, d_tm, np * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(count_out, d_count, np * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (d_dist) HIP_TRY(hipMemcpyAsync(dist_out, d_dist, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (transform_out) HIP_TRY(hipMemcpyAsync(transform_out, d_tr, np * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
+        *kernel_ms = ms;
+    }
+    return TH_OK;
+}

@@ -1,4 +1,4 @@
-"""Host-side batching shared by the structure analyses (timed_hip.structure, .superpose, .lddt): files are parsed on host threads,
+"""Host-side batching shared by the structure analyses (timed_hip.structure, .superpose, .lddt, .tmscore): files are parsed on host threads,
 the work is cut into runs of consecutive items whose flat arrays fit a byte budget, and each run is one GPU submission.  An
 analysis supplies its layouts, its cost per unit in bytes and a ``submit(part, timing)`` closure that concatenates one run, makes
 the one call and slices the outputs back.  No GPU and no ctypes here."""

@@ -198,11 +198,13 @@ def prepare(pairs: Sequence[Tuple], pair_by: str = "position", atom: str = "CA",
 
 
 def score_pairs(prepared: Prepared, budget_bytes: int, stats: Optional[dict], position_bytes: int, arrays: Callable, result: Callable,
-                failed: Callable) -> list:
-    """The driver superpose() and lddt.lddt() share: the pairs that can be scored go in batches of ``position_bytes`` per position
-    under ``budget_bytes``, one ``arrays(ref_xyz, mob_xyz, offsets, timing)`` call each; a pair's result is
-    ``result(got, j, a, b, ref, mod, ours, theirs)`` — pair j of the call, positions [a, b) of its flat arrays — or
-    ``failed(error text)``.  ``stats`` receives ``submissions``, ``kernel_ms`` and ``files_parsed``."""
+                failed: Callable, cost: Optional[Callable] = None, whole_pairs: bool = False) -> list:
+    """The driver superpose(), lddt.lddt() and tmscore.tmscore() share: the pairs that can be scored go in batches of
+    ``position_bytes`` per position under ``budget_bytes``, one ``arrays(ref_xyz, mob_xyz, offsets, timing)`` call each; a pair's
+    result is ``result(got, j, a, b, ref, mod, ours, theirs)`` — pair j of the call, positions [a, b) of its flat arrays — or
+    ``failed(error text)``.  ``stats`` receives ``submissions``, ``kernel_ms`` and ``files_parsed``.  ``cost(ref, mod, ours,
+    theirs)``, when given, is what a pair is charged in units of ``position_bytes`` instead of its number of positions;
+    ``whole_pairs``: ``arrays`` receives a fifth argument, the ``(ref, mod, ours, theirs)`` of the pairs of its call."""
     results = [failed(item) if isinstance(item, str) else None for item in prepared.pairs]
     ready = [(k,) + item for k, item in enumerate(prepared.pairs) if not isinstance(item, str)]
 
@@ -211,10 +213,10 @@ def score_pairs(prepared: Prepared, budget_bytes: int, stats: Optional[dict], po
         np.cumsum([len(item[3]) for item in part], out=offsets[1:])
         ref_xyz = np.concatenate([ref.xyz[ours] for _, ref, _, ours, _ in part])
         mob_xyz = np.concatenate([mod.xyz[theirs] for _, _, mod, _, theirs in part])
-        got = arrays(ref_xyz, mob_xyz, offsets, timing)
+        got = arrays(ref_xyz, mob_xyz, offsets, timing, [item[1:] for item in part]) if whole_pairs else arrays(ref_xyz, mob_xyz, offsets, timing)
         for j, (k, ref, mod, ours, theirs) in enumerate(part):
             results[k] = result(got, j, int(offsets[j]), int(offsets[j + 1]), ref, mod, ours, theirs)
-    batching.run_batches(ready, [len(item[3]) for item in ready], budget_bytes, position_bytes, submit, stats)
+    batching.run_batches(ready, [cost(*item[1:]) if cost else len(item[3]) for item in ready], budget_bytes, position_bytes, submit, stats)
     if stats is not None and not any(seen is stats for seen in prepared.counted):
         prepared.counted.append(stats)
         stats["files_parsed"] = stats.get("files_parsed", 0) + prepared.files

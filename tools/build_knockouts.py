@@ -10,6 +10,8 @@ experiments, loaded in a process of its own through the last line printed here:
 
     TIMED_HIP_LIB=.../libtimedhip_knock.so TH_WF_DBG=2 python tools/bench_layer.py 10 32 64 3 8192 1
 
+It also has TH_TM_STAGE=1 (th_tmscore with the coordinates staged in LDS; right results, see profiles/tmscore.txt).
+
 A library newer than every source and header is left alone (the objects may be gone: nothing is compiled then)."""
 import os
 import sys
