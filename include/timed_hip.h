@@ -418,6 +418,80 @@ int th_tag_rotamers(int device, const double* xyz, const uint32_t* atom_name, in
  * may be NULL.  Host code. */
 int th_rotamer_table(int res_type, int* n_chi, int* class_base, char names[7][4]);
 
+/* ---- *** PARITY UNPINNED AGAINST SCWRL4 *** side chains from rotamer classes: build_sidechains.py — the inverse of th_tag_rotamers.
+ * From N, CA, C, a residue type and chi angles per residue to every side-chain heavy atom, for a BATCH of structures in one
+ * submission; then the deviation from native atoms of the same name, and the steric clashes of the result.  The reference gets
+ * side chains from SCWRL4 (analyse_rotamers.py analyses 2 and 3, pack_sidechains), which searches rotamers by energy; here the
+ * rotamer is the caller's choice (a predicted class, the native angles) and nothing is searched.
+ *
+ *     *** PARITY UNPINNED AGAINST SCWRL4 ***  SCWRL4 is not available where this project is built.  The tree of internal
+ *     coordinates (csrc/sidechain_table.h; th_sidechain_table), its values (standard stereochemistry after Engh & Huber 1991, the
+ *     offsets of the sp3 branches from the means of 1ubq) and the rules below are this project's own; no test can pin them against
+ *     SCWRL4 itself.  Rebuilding 1ubq from its native chi angles gives 0.347 Angstrom RMSD over its 297 side-chain heavy atoms.
+ *
+ * All arrays are host memory.
+ *   backbone            double[n_res][nb][3] with nb = 3 (N, CA, C) or, with TH_SC_BACKBONE_O in flags, nb = 4 (N, CA, C, O).  Any
+ *                       value; O is used by the clash count alone and may be NaN;
+ *   res_type            int8[n_res]: 0..19 in the codec's order (th_tag_rotamers), -1 for anything else: the type that is BUILT;
+ *   chi                 double[n_res][4], degrees; only the angles the type needs are read (th_rotamer_table's n_chi);
+ *   chain_id            NULL (one chain) or int32[n_res]: any labels; read by the clash count alone;
+ *   struct_offsets      int64[n_struct + 1]: structure s owns residues struct_offsets[s] .. struct_offsets[s + 1]; starts at 0,
+ *                       non-decreasing, ends at n_res.  A structure may be empty;
+ *   n_struct, n_res     0 <= n_struct <= 2^31 - 1, 0 <= n_res <= TH_SC_MAX_RESIDUES;
+ *   native_xyz, native_name, native_total, native_res_offsets
+ *                       the native atoms in the format of th_tag_rotamers (packed names; residue r owns atoms
+ *                       native_res_offsets[r] .. [r + 1], non-decreasing, within 0 .. native_total), and
+ *   native_type         int8[n_res], the native residue types, -1..19.  native_res_offsets NULL: no native; the other four and
+ *                       out_n_matched, out_sum_sq must then be NULL / 0;
+ *   clash_distance      finite and > 0 when a clash output is asked for (the Python layer's default: 2.5 Angstrom);
+ *   flags               TH_SC_BACKBONE_O or 0;
+ *   out_xyz             double[n_res][10][3]: the atoms of residue r in the order of th_sidechain_table, NaN beyond n_built;
+ *   out_n_built         int32[n_res]: the number of atoms of the type, or 0;
+ *   out_n_matched       int32[n_res], out_sum_sq double[n_res] (both required with a native, NULL without);
+ *   out_clashes         int32[n_res] or NULL;  out_struct_pairs  int64[n_struct] or NULL.  Both NULL: no clash kernel runs;
+ *   kernel_ms           NULL, or receives the device time of the kernels (events around them), in milliseconds.
+ * BUILDING.  Atom d with parents a, b, c (N, CA, C or earlier atoms of the residue), bond length L, bond angle t = b-c-d and
+ * dihedral p = a-b-c-d = chi[k] + offset (the offset alone for k = -1), all float64, every product and sum rounded on its own:
+ *   bc = (c - b) / |c - b|,  n = (b - a) x bc divided by its length,  m = n x bc,
+ *   d = c + ((-(L cos t)) bc + ((L sin t) cos p) m) + ((L sin t) sin p) n,      angles in radians = degrees * (pi / 180).
+ * The dihedral of the built atoms, measured by th_tag_rotamers' formula, is p.  CB is built like any other atom, on (C, N, CA).
+ * UNBUILT (all ten atoms NaN, n_built = 0, no match, no clash): res_type -1 or GLY; a coordinate of N, CA or C that is not finite;
+ * a chi angle the type needs that is not finite; any atom that comes out not finite (N, CA, C on a line: 0 / 0 in n).  Never an
+ * error, and the residues beside it are not affected.
+ * DEVIATION.  Where native_type[r] == res_type[r] and r is built, every built atom takes the FIRST native atom of residue r with
+ * its name (a native atom with a coordinate that is not finite matches nothing): n_matched counts them, sum_sq is the sum of
+ * (dx*dx + dy*dy) + dz*dz in table order.  The caller forms sqrt(sum_sq / n_matched).  NO SYMMETRY CORRECTION: a PHE / TYR ring or
+ * an ASP / GLU carboxylate deposited with its two equivalent atoms the other way round (chi2 off by 180 degrees) is reported as it
+ * is named, and so is an ASN / GLN / HIS flip.
+ * CLASHES.  The atoms of a structure are the built side-chain atoms and the nb backbone atoms of every residue (those of unbuilt
+ * residues too).  A pair CLASHES when sqrt((dx*dx + dy*dy) + dz*dz) < clash_distance (strict; the kernel compares the squared
+ * distance with th_packing_threshold(clash_distance), the same decision for every double).  Counted are pairs of a side-chain atom
+ * of residue i with an atom of residue j != i of the same structure, except: between chain neighbours — |i - j| = 1, indices in
+ * the structure, and chain_id[i] == chain_id[j] — only side chain against side chain (the bonded backbone is no clash); two
+ * consecutive residues of DIFFERENT chains are counted in full; a pair of two SG atoms is never counted (a disulfide).
+ * clashes[r] is the number of counted pairs whose side-chain atom is of r (a side chain - side chain pair counts for both
+ * residues); pairs[s] is the number of unordered counted pairs of structure s, each once.
+ * No atomics.  A residue's atoms depend on its own inputs, a structure's counts on its own residues alone — not on the place in
+ * the batch — and two calls give the same bytes.  Device memory: about 400 bytes per residue + 28 per native atom.  TH_EINVAL,
+ * before anything is launched or written: a negative or too large size, a NULL that is required, struct_offsets that decrease, do
+ * not start at 0 or do not end at n_res, native_res_offsets decreasing or outside 0 .. native_total, a type outside -1 .. 19,
+ * unknown flag bits, native arrays or outputs without native_res_offsets, a clash output with a clash_distance that is not finite
+ * or not > 0.  n_res = 0 is success without a launch (pairs all 0). */
+#define TH_SC_BACKBONE_O 1
+#define TH_SC_MAX_RESIDUES 134217727 /* (2^31 - 1) / 16 */
+int th_build_sidechains(int device, const double* backbone, const int8_t* res_type, const double* chi, const int32_t* chain_id,
+                        const int64_t* struct_offsets, int64_t n_struct, int64_t n_res, const double* native_xyz,
+                        const uint32_t* native_name, int64_t native_total, const int64_t* native_res_offsets, const int8_t* native_type,
+                        double clash_distance, int flags, double* out_xyz, int32_t* out_n_built, int32_t* out_n_matched,
+                        double* out_sum_sq, int32_t* out_clashes, int64_t* out_struct_pairs, double* kernel_ms);
+/* The table th_build_sidechains uses, for one residue type 0..19: the number of side-chain heavy atoms (0 for GLY) and, per atom in
+ * build order, its name (zero-padded to 4 bytes), its three parents a, b, c (0 = N, 1 = CA, 2 = C, 3 + j = atom j of this list),
+ * the chi index k (-1: none) and {bond length |cd| in Angstrom, bond angle b-c-d, dihedral offset} in degrees; then the bonds that
+ * close the type's rings, which the tree does not use: their two atoms (indices into this list; -1 beyond n_closure) and the
+ * length the table states for each.  Rows beyond n_atoms are zero (chi_index -1).  Any output may be NULL.  Host code. */
+int th_sidechain_table(int res_type, int* n_atoms, char names[10][4], int8_t parents[10][3], int8_t chi_index[10],
+                       double geometry[10][3], int* n_closure, int8_t closure_atoms[2][2], double closure_length[2]);
+
 /* ---- superposition of models on their native: analyse_models.py — what the reference's calculate_RMSD_and_gdt
  * (scripts/analyse_af2.py) gets from PyMOL one pair at a time: cmd.align on the CA atoms, its RMSD, and the fractions of aligned
  * pairs within 1, 2, 4 and 8 Angstrom.  Here for a BATCH of position-paired coordinate lists in one launch.

@@ -100,7 +100,7 @@ CLI_FLAGS = (
     ("--path_to_datasetmap", dict(default="datasetmap.txt", type=str, help="dataset map written by predict.py (.txt)")),
     ("--workers", dict(type=int, default=8, help="host threads that parse the structures of --path_to_pdb (at most 16); the metrics are computed on the GPU")),
     ("--support_old_datasetmap", dict(default=False, action="store_true", help="the dataset map is the old 4-column csv")),
-    ("--scwrl_path", dict(default="/Users/leo/scwrl4/Scwrl4", type=str, help="accepted for compatibility: the SCWRL4 analyses are not part of this build")),
+    ("--scwrl_path", dict(default="/Users/leo/scwrl4/Scwrl4", type=str, help="accepted for compatibility: the SCWRL4 analyses are not part of this build; build_sidechains.py builds the predicted classes into side chains and measures them against the native (RMSD, clashes) without SCWRL4")),
     ("--path_to_rotamer_labels", dict(type=str, default=None, help="JSON {\"<pdb><chain>\": [rotamer class index or null, ...]}: the first dict tag_pdb_with_rot returns (tag_rotamers.py writes it)")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
 )

@@ -86,6 +86,8 @@ PROTOTYPES = {
     "th_packing_threshold": (_d, [_d]),
     "th_tag_rotamers": (_i, [_i, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _pd]),
     "th_rotamer_table": (_i, [_i, _pi, _pi, _vp]),
+    "th_build_sidechains": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _pd]),
+    "th_sidechain_table": (_i, [_i, _pi, _vp, _vp, _vp, _vp, _pi, _vp, _vp]),
     "th_superpose": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _pd]),
     "th_lddt": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _pd]),
     "th_tmscore": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _pd]),

@@ -3,6 +3,7 @@ gzipped (the reference ships tests/testing_files/1ubq.pdb1.gz and passes ``is_pd
 Only what voxelisation needs: coordinates, atom / residue names, chain, residue number (+ insertion code), element,
 model number.  Alternate locations: the first one seen for an atom name within a residue wins (blank or 'A').
 The temperature factor (columns 61-66; AlphaFold2 writes pLDDT there) is kept per atom for timed_hip.structure.
+``write_pdb`` writes one model back as fixed-column records (timed_hip.sidechains: the native backbone with built side chains).
 ``find_structures`` / ``stem_of``: which files of a directory the command-line programs take for structures, and their labels.
 """
 from __future__ import annotations
@@ -120,3 +121,54 @@ def read_pdb(path) -> List[Model]:
                     res.bfactors[name] = float("nan")
     close_model()
     return models
+
+
+def element_of(name: str) -> str:
+    """the element of a protein heavy atom or hydrogen from its name: the first letter behind any leading digits ("CA" is carbon)"""
+    letters = name.lstrip("0123456789 ")
+    return letters[:1].upper()
+
+
+def _name_column(name: str, element: str) -> str:
+    """columns 13-16: a four-character name fills them; a shorter one starts in column 14 unless its element has two letters"""
+    if len(name) >= 4:
+        return name[:4]
+    if len(element) == 2 and name.upper().startswith(element.upper()):
+        return name.ljust(4)
+    return (" " + name).ljust(4)
+
+
+def write_pdb(path, model: Model) -> int:
+    """Write one model as fixed-column ATOM / HETATM records, residue after residue in the model's order: serial numbers from 1,
+    occupancy 1.00, the B-factor of ``Residue.bfactors`` (0.00 where absent or NaN), the element of ``Residue.elements`` or else
+    from the name (``element_of``), a TER record where the chain changes and after the last residue, then END.  Coordinates are
+    written with three decimals.  A path ending in .gz is gzipped.  Returns the number of atoms written; ``read_pdb`` of the file
+    gives the same residues, names and the coordinates rounded to three decimals."""
+    lines, serial = [], 0
+    residues = model.residues
+
+    def number_of(res):
+        number = res.number.strip()
+        icode = number[-1] if number and number[-1].isalpha() else " "
+        return (number[:-1] if icode != " " else number)[-4:].rjust(4), icode
+    for r, res in enumerate(residues):
+        number, icode = number_of(res)
+        for name, pos in res.atoms.items():
+            serial += 1
+            element = (res.elements.get(name) or element_of(name)).strip().upper()[:2]
+            if not element.isalpha():
+                element = element_of(name)
+            b = res.bfactors.get(name, 0.0)
+            b = 0.0 if b != b else b
+            lines.append("%-6s%5d %4s %3s %1s%4s%1s   %8.3f%8.3f%8.3f%6.2f%6.2f          %2s\n" % (
+                "HETATM" if res.hetero else "ATOM", serial % 100000, _name_column(name, element), res.name[:3].rjust(3), res.chain[:1] or "A",
+                number, icode, pos[0], pos[1], pos[2], 1.0, b, element.rjust(2)))
+        if r + 1 == len(residues) or residues[r + 1].chain != res.chain:
+            serial += 1
+            lines.append("TER   %5d      %3s %1s%4s%1s\n" % (serial % 100000, res.name[:3].rjust(3), res.chain[:1] or "A", number, icode))
+    lines.append("END\n")
+    path = str(path)
+    opener = gzip.open if path.endswith(".gz") else open
+    with opener(path, "wt", encoding="ascii") as f:
+        f.writelines(lines)
+    return serial - sum(1 for line in lines if line.startswith("TER"))
