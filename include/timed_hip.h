@@ -86,6 +86,10 @@ int th_model_info(const th_model* m, int dims[4], int* n_classes);
 int th_model_cost(const th_model* m, double* algo_flops, double* exec_flops, int* n_steps);
 /* frames processed per internal pass (Keras' own predict() minibatch is 32 — no numeric effect) */
 int th_model_set_chunk(th_model* m, int frames_per_chunk);
+/* 16-row tiles per wave, 1 or 2, that the batch-row convolution kernel (k_conv_gl) runs with when one launch covers `rows` GEMM rows
+ * (rows = frames in the chunk x output voxels per frame).  The results do not depend on it; tests call the rule so that they do not
+ * copy it.  Host code. */
+int th_conv_gl_row_tiles(int64_t rows);
 
 /* ---- forward: replaces frame_model.predict(X_batch) — predict.py:142 --------------------- */
 /* host frames [n,D,H,W,C] of `dtype` -> host probs_out [n,n_classes] fp32 (rows sum to 1) */

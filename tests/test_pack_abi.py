@@ -74,6 +74,15 @@ def test_abi_exports_every_declared_symbol(lib):
     assert lib.th_version() == 1
 
 
+def test_conv_gl_row_tile_rule(lib):
+    """th_conv_gl_row_tiles (host code): launches of fewer than 8 192 waves of 32 rows run one 16-row tile per wave, larger ones two.
+    Today's boundary, and the frame counts tests/test_gpu_conv_gl.py runs on 27 000 rows per frame: 9 frames are still one tile."""
+    assert lib.th_conv_gl_row_tiles(262112) == 1 and lib.th_conv_gl_row_tiles(262113) == 2
+    assert [lib.th_conv_gl_row_tiles(n * 27000) for n in (1, 2, 9, 10, 11, 12, 13)] == [1, 1, 1, 2, 2, 2, 2]
+    assert lib.th_conv_gl_row_tiles(0) == 1 and lib.th_conv_gl_row_tiles(1) == 1 and lib.th_conv_gl_row_tiles(2 ** 40) == 2
+    assert lib.th_conv_gl_row_tiles(4096 * 125) == 2 and lib.th_conv_gl_row_tiles(1024 * 125) == 1      # ProDCoNN's conv3d_2: chunk 4096, 1024
+
+
 def test_no_gpu_is_an_error_not_a_fallback(lib, monkeypatch):
     """Without a device the product must fail loudly (there is no CPU path).  A timing knock-out variable is refused by name
     before the device is looked for: the product library has no knock-outs (tools/build_knockouts.py builds the one that has)."""

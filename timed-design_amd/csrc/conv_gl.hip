@@ -190,6 +190,11 @@ void conv_gl_pack_weights(const ConvGeom& g, int Cin, int Cout, const float* w, 
                     }
 }
 
+// row tiles per wave: two share every weight fragment; ONE when the layer is so small that two leave SIMDs short of waves
+// (ProDCoNN's 'valid' layer, 3 456 such waves: 0.262 -> 0.247 ms with one; its strided layer, 16 000: 0.528 -> 0.586 ms with one)
+int conv_gl_row_tiles(int64_t rows) { return (rows + 31) / 32 < 8 * 1024 ? 1 : 2; }
+extern "C" int th_conv_gl_row_tiles(int64_t rows) { return conv_gl_row_tiles(rows); }
+
 int launch_conv_gl(hipStream_t s, int64_t n, TView in, TView out, ConvGeom g, int Cin, int Cout, const float* wpk, const float* bias,
                    PreOp pre, PostOps post) {
     if (n <= 0) return TH_OK;
@@ -204,9 +209,7 @@ int launch_conv_gl(hipStream_t s, int64_t n, TView in, TView out, ConvGeom g, in
     a.bias = bias; a.post = post; a.pre = pre;
     a.out = out.p; a.out_fs = out.fs; a.out_cs = out.cs; a.out_coff = out.coff; a.Cout = Cout;
     a.rows = n * (int64_t)out.V();
-    // row tiles per wave: two share every weight fragment; ONE when the layer is so small that two leave SIMDs short of waves
-    // (ProDCoNN's 'valid' layer, 3 456 such waves: 0.262 -> 0.247 ms with one; its strided layer, 16 000: 0.528 -> 0.586 ms with one)
-    const int mt = (a.rows + 31) / 32 < 8 * 1024 ? 1 : 2;
+    const int mt = conv_gl_row_tiles(a.rows);
     const int64_t waves = (a.rows + 16 * mt - 1) / (16 * mt);
     const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
     const bool has_pre = pre.scale || pre.act != ACT_LINEAR;
