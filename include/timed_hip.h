@@ -90,6 +90,13 @@ int th_model_set_chunk(th_model* m, int frames_per_chunk);
  * (rows = frames in the chunk x output voxels per frame).  The results do not depend on it; tests call the rule so that they do not
  * copy it.  Host code. */
 int th_conv_gl_row_tiles(int64_t rows);
+/* The dispatch rule of the pointwise (1x1x1) kernels, for tests.  th_conv_pw_pick writes the name of the instantiation that runs a
+ * Cin -> Cout layer (pool: 0 none, 1 max, 2 avg) on an input view of voxel stride in_cs floats (<= 0: Cin) at channel offset
+ * in_coff, with chunk-blocked output or not, behind a "BN-affine -> ReLU" epilogue or not: "k_conv_pw2<12,2,0,1,2>",
+ * "k_conv_pw<16,4,0>"; the empty string when the pointwise family refuses the layer.  th_conv_pw_kernels lists every compiled
+ * instantiation, one name per line. */
+int th_conv_pw_pick(int Cin, int Cout, int pool, int in_cs, int in_coff, int out_blk, int relu_chain, char* buf, size_t len);
+int th_conv_pw_kernels(char* buf, size_t len);
 
 /* ---- forward: replaces frame_model.predict(X_batch) — predict.py:142 --------------------- */
 /* host frames [n,D,H,W,C] of `dtype` -> host probs_out [n,n_classes] fp32 (rows sum to 1) */

@@ -72,6 +72,7 @@ struct ThKnobs {
     int no_pool_first = 0;     // TH_NO_POOL_FIRST: act / BN before the max-pool even when the chain is monotone
     int no_tail_fuse = 0;      // TH_NO_TAIL_FUSE: keep GAP / Dense / Softmax as separate launches
     int conv_notail = 0, n16_resident = 0;
+    int pw_resident = 0;       // TH_PW_RESIDENT: tests, at most this many workgroups of k_conv_pw / k_conv_pw2 (multi-trip waves)
     int wf_resident = 0, wf_noblk = 0;
     long long wino_piece = 0;
     int wino_b3var = 2, wino_nomid = 0;
@@ -341,12 +342,12 @@ struct ConvPwPlan {
     int pool = 0;                 // 0 none, 1 max 2x2x2, 2 avg 2x2x2
     size_t lds_bytes = 0, wpk_floats = 0;
     double exec_flops = 0;        // MFMA FLOPs issued per frame
-    const ThKnobs* knobs = nullptr;
+    const ThKnobs* knobs = nullptr;   // launch-time ones: TH_PW_RESIDENT
     std::string label;
 };
 bool conv_pw_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn, ConvPwPlan* plan);
 void conv_pw_pack_weights(const ConvPwPlan& p, int Cin, int Cout, const float* w_keras, float* dst);
-std::string conv_pw_label(const ConvPwPlan& p, bool out_blk, const PostOps& post);
+std::string conv_pw_label(const ConvPwPlan& p, const TView& in, int Cin, bool out_blk, const PostOps& post);
 int launch_conv_pw(hipStream_t s, int64_t n, const ConvPwPlan& p, TView in, TView out, int Cin, int Cout, const float* wpk,
                    const float* bias, PreOp pre, PostOps post);
 

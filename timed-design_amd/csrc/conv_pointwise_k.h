@@ -9,8 +9,6 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-namespace {
-
 struct ConvPwArgs {
     const float* in; int64_t in_fs; int in_cs, in_coff, Cin, K8, vec_ok, in_dense;
     int V, H, W;        // conv extent per frame (input voxels), V = D*H*W
@@ -30,6 +28,15 @@ struct ConvPwArgs {
     // 17 VGPRs (44 bytes of scratch per lane) in k_conv_pw2<12, 2, 1|2, 0, 0>, which have none with the run-time read.
     int dbg;
 };
+
+// a dispatch-table entry: the kernel, its KMAX, whether it is a BLK instantiation (the only ones that use the per-wave transpose
+// tile in LDS) and the name of the instantiation as the step labels and th_conv_pw_pick print it
+typedef void (*PwKernel)(const ConvPwArgs);
+struct PwEntry { PwKernel k; int kmax, blk; const char* name; };
+#define PW2_ENTRY(K, N, P, B, E) {k_conv_pw2<K, N, P, B, E>, K, B, "k_conv_pw2<" #K "," #N "," #P "," #B "," #E ">"}
+#define PW_NONE {nullptr, 0, 0, ""}
+
+namespace {
 
 // this lane's input row for a tile: lane j supplies GEMM row tile*32 + j (POOL: pooled voxel tile*4 + j/8, mate j%8);
 // rows past the end are clamped to the last one (their results are never stored)
@@ -213,7 +220,7 @@ __global__ void __launch_bounds__(256, (NT == 4 || KMAX == 16 || (BLK && KMAX ==
     float4* Bs = smem;
     float* psc = reinterpret_cast<float*>(smem + (size_t)K8 * NT * 64);
     float* psh = psc + K8 * 8;
-    // chunk-blocked output only: a [32 rows][36] transpose tile per wave behind the prologue constants (launch_conv_pw adds it)
+    // chunk-blocked output only: a [32 rows][36] transpose tile per wave behind the prologue constants (launch_conv_pw adds it for BLK kernels)
     float* const tsc = psh + K8 * 8 + wave * (32 * 36);
     {
         const float4* src = reinterpret_cast<const float4*>(a.wpk);
@@ -407,7 +414,5 @@ __global__ void __launch_bounds__(256, (NT == 4 || KMAX == 16 || (BLK && KMAX ==
         tile = t2;
     }
 }
-
-typedef void (*PwKernel)(const ConvPwArgs);
 
 }  // namespace

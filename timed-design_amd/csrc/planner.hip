@@ -715,7 +715,7 @@ int emit_pointwise(const ConvArgs& c, const LayerPlan& L, Step& st) {
     if (int rc = upload_packed(c.M, pw.wpk_floats, [&](float* d) { conv_pw_pack_weights(pw, c.Cin, c.Cout, c.hw, d); }, &dw)) return rc;
     const bool blk = c.node(c.dst).blk != 0;
     st.exec_flops = pw.exec_flops;
-    st.label = conv_label(c, conv_pw_label(pw, blk, c.po), false, blk);
+    st.label = conv_label(c, conv_pw_label(pw, c.in(), c.Cin, blk, c.po), false, blk);
     st.run = [=](hipStream_t s, int64_t cnt) { return launch_conv_pw(s, cnt, pw, c.in(), c.out(), c.Cin, c.Cout, dw, c.bias, c.pre, c.po); };
     return TH_OK;
 }

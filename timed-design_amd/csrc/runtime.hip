@@ -62,6 +62,7 @@ int th_knobs_read(ThKnobs* k) {
     flag("TH_CONV_NOTAIL", &k->conv_notail);
     KNOCK("TH_CONV_DBG", conv_dbg);
     num("TH_N16_RESIDENT", &k->n16_resident, 0, 1 << 20);
+    num("TH_PW_RESIDENT", &k->pw_resident, 0, 1 << 20);
     KNOCK("TH_PW_DBG", pw_dbg);
     num("TH_WF_RESIDENT", &k->wf_resident, 0, 1 << 20);
     KNOCK("TH_WF_DBG", wf_dbg);

@@ -34,6 +34,8 @@ PROTOTYPES = {
     "th_model_cost": (_i, [_vp, _pd, _pd, _pi]),
     "th_model_set_chunk": (_i, [_vp, _i]),
     "th_conv_gl_row_tiles": (_i, [_i64]),
+    "th_conv_pw_pick": (_i, [_i, _i, _i, _i, _i, _i, _i, C.c_char_p, _sz]),
+    "th_conv_pw_kernels": (_i, [C.c_char_p, _sz]),
     "th_predict": (_i, [_vp, _vp, _i, _i64, _vp, _u]),
     "th_predict_device": (_i, [_vp, _vp, _i, _i64, _vp, _u]),
     "th_predict_async": (_i, [_vp, _vp, _i, _i64, _vp, _u, _pi]),
