@@ -675,6 +675,77 @@ int th_tmscore(int device, const double* ref_xyz, const double* mob_xyz, int64_t
 /* max(0.5, 1.24 cbrt(L - 15) - 1.8) for L > 15, else 0.5: the scale d0 of the TM-score for normalisation length L.  Host code. */
 double th_tm_d0(int64_t L);
 
+/* ---- *** PARITY UNPINNED AGAINST PYMOL *** structural alignment of models of any length: analyse_models.py --cealign — the
+ * reference's calculate_RMSD_and_gdt / _calculate_RMSD of scripts/analyse_all_properties.py and
+ * scripts/analyse_cherrypicked_samples_af2.py, which call PyMOL's cmd.cealign on the CA atoms: a sequence-independent alignment by
+ * combinatorial extension (CE, Shindyalov & Bourne 1998).  Here for a BATCH of (reference, model) pairs whose two lengths are
+ * independent.  The alignment is a pairing: th_superpose, th_lddt and th_tmscore score it unchanged.
+ *
+ *     *** PARITY UNPINNED AGAINST PYMOL ***  PyMOL is not available where this project is built.  The rule below is this project's
+ *     reading of the PUBLISHED algorithm with cealign's documented defaults (window 8, d0 3.0, d1 4.0, gap_max 30, the best 20 paths
+ *     re-scored by RMSD); it is not PyMOL's code and no test can pin it against PyMOL.
+ *
+ * All arrays are host memory.
+ *   ref_xyz            double[ref_total][3]: the reference (native) coordinates of all pairs, pair after pair (any value);
+ *   ref_offsets        int64[n_pairs + 1]: pair p owns positions ref_offsets[p] .. ref_offsets[p + 1]; from 0 to ref_total, never
+ *                      decreasing; a structure may be empty and has at most TH_CE_MAX_POSITIONS positions;
+ *   mob_xyz, mob_total, mob_offsets   the same for the models;
+ *   n_pairs            0 <= n_pairs <= 2^31 - 1, as are both totals;
+ *   d0, d1             the similarity thresholds of a fragment pair and of a path, finite and > 0 (cealign's: 3.0 and 4.0);
+ *   gap_max            0 .. 31 (cealign's: 30): the 2 gap_max + 1 candidates of a step are the lanes of one wavefront;
+ *   align_out          int32[ref_total]: the index, local to the pair, of the model position aligned to this reference position,
+ *                      -1 if none;
+ *   score_out          double[n_pairs][2]: the RMSD over the aligned positions, the winning path's score;
+ *   count_out          int64[n_pairs][6]: mA, mB, n_starts, n_afps, n_aligned, n_candidates;
+ *   transform_out      double[n_pairs][12] or NULL: rows of [R | t] of the winning fit, as th_superpose (the identity without a start);
+ *   kernel_ms          NULL, or receives the device time of the four kernels (events around them), in milliseconds.
+ * The rule, for one pair — A the reference with nA positions, B the model with nB —, all arithmetic float64 and
+ * no fused multiply-add: every product, sum and quotient is rounded on its own, square roots are correctly rounded.  W = TH_CE_WINDOW = 8.
+ *   1. VALID: a position is valid when its three coordinates are finite.  Each list is compacted to its valid positions in index
+ *      order, mA and mB of them; "position" below means a compacted one; outputs are in the caller's original indices.
+ *   2. DISTANCE inside one structure: d(i, j) = sqrt((dx*dx + dy*dy) + dz*dz).
+ *   3. WINDOW STARTS: a = 0 .. mA - W and b = 0 .. mB - W; none when mA < W or mB < W.
+ *   4. SIMILARITY: over the 21 pairs (p, q), 0 <= p, q >= p + 2, q <= 7, in lexicographic order,
+ *      S(a, b) = (sum |dA(a + p, a + q) - dB(b + p, b + q)|) / 21, the terms added left to right.
+ *   5. STARTS: every (a0, b0) with S(a0, b0) < d0, strict; n_starts counts them; a start's index is a0 (mB - W + 1) + b0.
+ *   6. DISTANCE OF TWO FRAGMENT PAIRS (CE's independent set, W terms):
+ *      D((ai, bi), (aj, bj)) = (|dA(ai, aj) - dB(bi, bj)| + |dA(ai + 7, aj + 7) - dB(bi + 7, bj + 7)|
+ *                               + sum over k = 1 .. 6 of |dA(ai + k, aj + 7 - k) - dB(bi + k, bj + 7 - k)|) / 8, added in that order.
+ *   7. PATH from a start: path = [(a0, b0)], sumS = S(a0, b0), sumD = 0.  Repeat, with n AFPs (aligned fragment pairs) so far and
+ *      the last at (a, b): the candidates are g = 0 .. 2 gap_max — g = 0: (a + W, b + W); odd g: (a + W + (g + 1) / 2, b + W); even
+ *      g > 0: (a + W, b + W + g / 2).  A candidate counts only when it is a window start of both sides and its S < d0.  Its cost is
+ *      c = s / n with s = sum over k ascending of D(path[k], candidate); it is eligible when c < d1.  The eligible candidate of
+ *      smallest c is taken, of equal costs the smallest g; without one the path ends.  score = ((sumS + S(cand)) + (sumD + s)) /
+ *      ((n + 1) + (n + 1) n / 2); if that is not < d1 the path ends WITHOUT the candidate; otherwise the candidate is appended,
+ *      sumS += S(cand), sumD += s.  A path's score is (sumS + sumD) / (n + n (n - 1) / 2).
+ *   8. CANDIDATES: all paths ordered by length descending, then score ascending, then start index ascending; the first
+ *      n_candidates = min(TH_CE_KEEP, n_starts) are the candidates.
+ *   9. WINNER: each candidate is fitted by the rule of th_superpose (centroids, two-pass cross-covariance, Horn's matrix, cyclic
+ *      Jacobi, the proper rotation) over its 8 n aligned position pairs; every sum of the fit runs over the pairs in path order, one
+ *      after the other (no tree: among near-identical candidates the order of addition decides); its RMSD is sqrt(sum d_i^2 / (8 n)).  The candidate of smallest RMSD
+ *      wins, of equal RMSDs the first in candidate order.  n_afps = n, n_aligned = 8 n.
+ *  10. NO START: n_afps = n_aligned = n_candidates = 0, the RMSD and the score are NaN, the transform is the identity and nothing
+ *      is aligned.  That is a result, not an error.
+ * MIRROR IMAGES: CE compares distances and does not see a mirror image; the proper rotation then refuses to fit it (64 aligned
+ * positions at 9.55 Angstrom for the mirror case of the superposition fixture).  An ideal helix against an ideal strand has no start.
+ * k_ce_windows writes the 21 distances of every window start, k_ce_similarity S in 16 x 16 tiles with the rows staged in LDS,
+ * k_ce_paths runs one wavefront per (a0, b0) — lane g evaluates candidate g, the path lives in registers, at most 256 AFPs —
+ * and leaves 12 bytes per (a0, b0); k_ce_best, one wavefront per pair, selects the candidates by rule 8, traces each again, fits it
+ * and writes the winner.  No atomics.  A pair's outputs depend on its own coordinates alone — not on its place in the batch or on
+ * its neighbours — and two calls give the same bytes.  Device memory per pair: (mA - 7)(mB - 7) * 8 bytes for S — the dominant
+ * term, 33 MB at 2048 x 2048 — and 12 more per (a0, b0) for the paths' records, 168 bytes per window start of either side, 28 per
+ * valid position, 4 per reference position and 160 (256 with transform_out) per pair.  TH_EINVAL, before anything is launched or
+ * written: a negative or too large size, a NULL that is required (both offsets, score_out, count_out; with ref_total > 0 also
+ * ref_xyz and align_out, with mob_total > 0 also mob_xyz), offsets of either list that decrease, do not start at 0 or do not end at
+ * the list's total, d0 or d1 not finite or <= 0, gap_max < 0 or > 31, a structure of more than TH_CE_MAX_POSITIONS positions, more
+ * than 2^33 - 4 window pairs in one call.  n_pairs = 0 (with both totals 0) is success without a launch. */
+#define TH_CE_MAX_POSITIONS 2048      /* per structure */
+#define TH_CE_WINDOW 8
+#define TH_CE_KEEP 20
+int th_cealign(int device, const double* ref_xyz, int64_t ref_total, const int64_t* ref_offsets, const double* mob_xyz, int64_t mob_total,
+               const int64_t* mob_offsets, int64_t n_pairs, double d0, double d1, int gap_max, int32_t* align_out, double* score_out,
+               int64_t* count_out, double* transform_out, double* kernel_ms);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

@@ -47,12 +47,29 @@ superposition are reused.
 PARITY UNPINNED AGAINST THE TM-score PROGRAM: Zhang & Skolnick's TMscore is not available to pin this against.  The rule is this
 project's reading of the published definition and search, written out in include/timed_hip.h and timed_hip/tmscore.py.  It aligns no
 sequences (that is TM-align).
+
+--cealign additionally writes ``model_cealign.csv``, one row per pair — label, reference, model, n_ref, n_model (the positions of either
+structure), n_starts (fragment pairs similar enough to start a path), n_afps, n_aligned (8 per aligned fragment pair), rmsd (over the
+aligned positions: the number cmd.cealign returns), path_score, error — and ``residue_cealign.csv`` — label, chain, number and residue
+of every residue of the reference, the chain, number and residue of the model's residue aligned to it (empty if none) and their
+distance under the winning fit.  This is the reference's calculate_RMSD_and_gdt / _calculate_RMSD of scripts/analyse_all_properties.py:
+a sequence-independent structural alignment (CE, Shindyalov & Bourne 1998) of the CA atoms, for which the two chains need be neither
+equally long nor numbered alike (at most 2048 positions each).  --ce_d0, --ce_d1 and --ce_gap_max are its thresholds.
+--pair_by_cealign makes that alignment the pairing of model_scores.csv, of --lddt and of --tmscore, in place of --pair_by: a length
+mismatch is then no error, and what either side has outside the alignment counts as unpaired.
+
+PARITY UNPINNED AGAINST PYMOL: the rule of --cealign is this project's reading of the published CE algorithm with cealign's documented
+defaults (window 8, d0 3.0, d1 4.0, gap_max 30, the best 20 paths re-scored by RMSD), written out in include/timed_hip.h and
+timed_hip/cealign.py.
 """
 import argparse
 import csv
 import sys
 from pathlib import Path
 
+import numpy as np
+
+from timed_hip import cealign as cealign_module
 from timed_hip import lddt as lddt_module
 from timed_hip import superpose
 from timed_hip import tmscore as tmscore_module
@@ -65,6 +82,8 @@ RESIDUE_COLUMNS = ["label", "chain", "residue_number", "distance", "kept"]
 LDDT_COLUMNS = ["label", "reference", "model", "n_valid", "n_included", "lddt", "preserved_0.5", "preserved_1", "preserved_2", "preserved_4",
                 "mean_model_bfactor", "error"]
 RESIDUE_LDDT_COLUMNS = ["label", "chain", "number", "residue", "n_included", "lddt", "model_bfactor"]
+CEALIGN_COLUMNS = ["label", "reference", "model", "n_ref", "n_model", "n_starts", "n_afps", "n_aligned", "rmsd", "path_score", "error"]
+RESIDUE_CEALIGN_COLUMNS = ["label", "chain", "number", "residue", "model_chain", "model_number", "model_residue", "distance"]
 TMSCORE_COLUMNS = ["label", "reference", "model", "n_valid", "norm_length", "d0", "tm_score", "tm_global_fit", "n_seeds", "n_fits", "error"]
 
 
@@ -120,6 +139,26 @@ def write_tmscore(out, todo, scores, global_fits):
                         res.error or ""])
 
 
+def write_cealign(out, todo, aligned):
+    """model_cealign.csv and residue_cealign.csv; ``aligned``: what cealign.cealign returned, with the transforms"""
+    with open(out / "model_cealign.csv", "w", newline="") as fs, open(out / "residue_cealign.csv", "w", newline="") as fr:
+        ws, wr = csv.writer(fs), csv.writer(fr)
+        ws.writerow(CEALIGN_COLUMNS)
+        wr.writerow(RESIDUE_CEALIGN_COLUMNS)
+        for (label, ref, model), res in zip(todo, aligned):
+            ws.writerow([label, str(ref), str(model), res.n_ref, res.n_model, res.n_starts, res.n_afps, res.n_aligned, _fmt(res.rmsd),
+                         _fmt(res.path_score), res.error or ""])
+            if res.error:
+                continue
+            partner = dict(zip(res.reference_index.tolist(), res.model_index.tolist()))
+            moved = res.model.xyz[res.model_index] @ res.transform[:, :3].T + res.transform[:, 3]
+            delta = moved - res.reference.xyz[res.reference_index]
+            distance = dict(zip(res.reference_index.tolist(), np.sqrt((delta * delta).sum(axis=1)).tolist()))
+            for k, r in enumerate(res.reference.residues):
+                m = res.model.residues[partner[k]] if k in partner else None
+                wr.writerow([label, r.chain, r.number, r.name] + ([m.chain, m.number, m.name, _fmt(distance[k])] if m else ["", "", "", ""]))
+
+
 def main(args):
     if args.pairs:
         if args.path_to_reference or args.path_to_models:
@@ -138,11 +177,26 @@ def main(args):
         sys.exit(f"--lddt_radius {args.lddt_radius} is not a positive finite number")
     if args.tmscore and args.tm_rounds < 0:
         sys.exit(f"--tm_rounds {args.tm_rounds} is negative")
+    aligning = args.cealign or args.pair_by_cealign
+    if aligning and not (0 < args.ce_d0 < float("inf") and 0 < args.ce_d1 < float("inf")):
+        sys.exit(f"--ce_d0 {args.ce_d0} and --ce_d1 {args.ce_d1} must be positive finite numbers")
+    if aligning and not 0 <= args.ce_gap_max <= 31:
+        sys.exit(f"--ce_gap_max {args.ce_gap_max} is outside 0 .. 31")
     stats = {}
-    prepared = superpose.prepare([(ref, model) for _, ref, model in todo], args.pair_by, "CA", args.workers)     # read and paired once for both scores
+    pairs = [(ref, model) for _, ref, model in todo]
+    aligned = None
+    if aligning:
+        aligned = cealign_module.cealign(pairs, "CA", args.ce_d0, args.ce_d1, args.ce_gap_max, args.device, True, args.workers, stats=stats)
+        pairs = [(res.reference or ref, res.model or model) for (ref, model), res in zip(pairs, aligned)]        # parsed once for all scores
+    if args.pair_by_cealign:
+        prepared = cealign_module.prepare_aligned(pairs, results=aligned, stats=stats)
+    else:
+        prepared = superpose.prepare(pairs, args.pair_by, "CA", args.workers)     # read and paired once for both scores
     results = superpose.superpose(prepared, cycles=args.cycles, cutoff=args.cutoff, device=args.device, stats=stats)
     out = Path(args.path_to_output)
     out.mkdir(parents=True, exist_ok=True)
+    if args.cealign:
+        write_cealign(out, todo, aligned)
     if args.lddt:
         write_lddt(out, todo, lddt_module.lddt(prepared, radius=args.lddt_radius, device=args.device, stats=stats))
     if args.tmscore:
@@ -187,6 +241,16 @@ CLI_FLAGS = (
                             "maximum over superpositions found by a search on the GPU, beside the same sum under the one global fit.  At most "
                             "4096 positions per pair.  PARITY UNPINNED AGAINST THE TM-score PROGRAM")),
     ("--tm_rounds", dict(type=int, default=20, help="refinement rounds per seed of --tmscore at most (default 20)")),
+    ("--cealign", dict(action="store_true",
+                       help="also write model_cealign.csv and residue_cealign.csv: the sequence-independent structural alignment (CE) of the CA "
+                            "atoms of every model on its native, of any two lengths (at most 2048 positions each), and the RMSD over the aligned "
+                            "positions.  PARITY UNPINNED AGAINST PYMOL")),
+    ("--ce_d0", dict(type=float, default=3.0, help="--cealign: two fragments of 8 are similar below this mean distance difference (default 3.0)")),
+    ("--ce_d1", dict(type=float, default=4.0, help="--cealign: a path grows while its step cost and its score stay below this (default 4.0)")),
+    ("--ce_gap_max", dict(type=int, default=30, help="--cealign: the longest gap between two aligned fragments, 0 .. 31 (default 30)")),
+    ("--pair_by_cealign", dict(action="store_true",
+                               help="pair the positions of model_scores.csv, --lddt and --tmscore by the alignment of --cealign in place of "
+                                    "--pair_by: a length mismatch is then no error")),
 )
 
 

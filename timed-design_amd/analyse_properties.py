@@ -14,8 +14,9 @@ residues are reported is the structure rule of timed_hip/structure.py (first mod
 neighbour, the non-hetero residues of the first chain reported; --all_chains reports every chain).  B-factor: of the residue's
 first atom, as the reference reads the pLDDT of an AlphaFold2 model.
 
-Out of scope: the reference script's CE-align RMSD (PyMOL) and its parsing of AlphaFold2 file names into model / temperature /
-sample / rank columns — the ``structure`` column is the file's path relative to the --path_to_pdb entry it was found under.
+Out of scope here: the reference script's CE-align RMSD (PyMOL), which is analyse_models.py --cealign, and its parsing of AlphaFold2
+file names into model / temperature / sample / rank columns — the ``structure`` column is the file's path relative to the
+--path_to_pdb entry it was found under.
 """
 import argparse
 import csv

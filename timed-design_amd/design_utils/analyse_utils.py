@@ -175,6 +175,21 @@ def calculate_RMSD_and_gdt(pdb_original_path, pdb_predicted_path, device: int = 
     return res.rmsd_kept, res.mean_gdt
 
 
+def calculate_cealign_RMSD(pdb_original_path, pdb_predicted_path, device: int = 0) -> float:
+    """reference scripts/analyse_all_properties.py:23-34 ``_calculate_RMSD`` (and ``calculate_RMSD_and_gdt`` of
+    scripts/analyse_cherrypicked_samples_af2.py): the RMSD of a predicted structure on its original after PyMOL's ``cmd.cealign`` on
+    the CA atoms — a sequence-independent structural alignment, so the two files need be neither equally long nor numbered alike.
+    Here the ``rmsd`` of ``timed_hip.cealign.cealign`` with cealign's defaults (window 8, d0 3.0, d1 4.0, gap_max 30):
+    PARITY UNPINNED AGAINST PYMOL, the rule is this project's reading of the published CE algorithm (include/timed_hip.h, th_cealign).  NaN when no
+    two fragments are similar enough to align; a file that cannot be read or a structure of more than 2048 positions raises
+    ValueError.  For many pairs call ``cealign`` itself: it batches them."""
+    from timed_hip import cealign
+    (res,) = cealign.cealign([(pdb_original_path, pdb_predicted_path)], device=device)
+    if res.error:
+        raise ValueError(f"{pdb_original_path} / {pdb_predicted_path}: {res.error}")
+    return res.rmsd
+
+
 # ---- per-class rotamer metrics (analyse_rotamers.py; computed on the GPU by timed_hip.analysis) -------------------------------
 def _narrow(matrix: np.ndarray) -> np.ndarray:
     """float16 / float32 matrices as they are; others to float16 when that is exact (the probability CSVs predict.py writes),
