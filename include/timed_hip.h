@@ -503,6 +503,74 @@ int th_build_sidechains(int device, const double* backbone, const int8_t* res_ty
 int th_sidechain_table(int res_type, int* n_atoms, char names[10][4], int8_t parents[10][3], int8_t chi_index[10],
                        double geometry[10][3], int* n_closure, int8_t closure_atoms[2][2], double closure_length[2]);
 
+/* ---- *** PARITY UNPINNED AGAINST SCWRL4 *** side chains packed by a rotamer search: pack_sidechains.py, analyse_rotamers.py --pack.
+ * th_build_sidechains builds the class the caller chose; this CHOOSES, for a BATCH of structures in one submission: for every
+ * residue one of the 3^n_chi classes of its type, under a steric ladder and optionally a rotamer model's own probabilities, by
+ * greedy sweeps from a deterministic start.  It returns classes and energies only; the atoms, the RMSD and the clash counts of the
+ * result come from th_build_sidechains on the chosen classes.
+ *
+ *     *** PARITY UNPINNED AGAINST SCWRL4 ***  The reference hands a sequence and a backbone to SCWRL4 (analyse_rotamers.py analyses
+ *     2 and 3), which is not available where this project is built.  The rule below is this project's own.  It is not SCWRL4's
+ *     backbone-dependent rotamer library nor its energy, it knows no hydrogen bonds, and it finds a local minimum, not the global
+ *     one; no test can pin it against SCWRL4 itself.
+ *
+ * All arrays are host memory.  backbone, res_type, chain_id, struct_offsets, n_struct, flags as in th_build_sidechains
+ * (n_res <= TH_PACK_MAX_RESIDUES); res_type is the type to build.
+ *   ladder, n_levels    double[n_levels], 1 <= n_levels <= TH_PACK_MAX_LEVELS: finite, positive, strictly increasing distances in
+ *                       Angstrom (the Python layer's default: 2.0, 2.5, 3.0, 3.5);
+ *   prior_cost          NULL (none) or int32[n_res][81]: the cost of candidate k of residue r, 0 .. TH_PACK_MAX_COST; entries beyond
+ *                       the type's candidates are ignored (timed_hip.packer.prior_costs: round(-1000 log2 p), computed on the host);
+ *   clash_weight        1 .. TH_PACK_MAX_COST: the cost of one ladder level (the Python layer's default: 2000);
+ *   max_sweeps          0 .. TH_PACK_MAX_SWEEPS;
+ *   out_cls             int16[n_res]: the chosen class (an index into the 338 of th_tag_rotamers) or -1;
+ *   out_cost_initial, out_cost_final      int64[n_res]: the residue's cost in the initial and in the final state, 0 without a class;
+ *   out_energy_initial, out_energy_final  int64[n_struct];
+ *   out_search          int32[n_struct][4]: sweeps run, moves made, converged (0 / 1), status (TH_PACK_OK, TH_PACK_TOO_LONG);
+ *   kernel_ms           NULL or double[3]: the device time of the candidates, the backbone and the search kernel, in milliseconds.
+ * CANDIDATES.  Residue r of type 0..19 has the 3^n_chi classes of its type as candidates, in class order: candidate k is class
+ * th_rotamer_table's class_base + k with every chi at its bin centre — 60 / 180 / -60 degrees for bins 1 / 2 / 3, the first angle
+ * varying slowest — and its atoms are placed exactly as th_build_sidechains places them (the same table, the same float64
+ * operations in the same order).  ALA has one candidate, CB alone.  GLY and type -1 have none: their backbone stays in the energy
+ * and they get class -1.  A residue whose N, CA or C is not finite has no candidates; a candidate with an atom that comes out not
+ * finite is excluded.
+ * PENALTY of a pair of atoms: the number of ladder levels t with sqrt((dx*dx + dy*dy) + dz*dz) < ladder[t], decided as
+ * th_build_sidechains decides a clash: the squared distance against th_packing_threshold(ladder[t]), false for NaN.
+ * PAIRS that count: the CLASHES rule of th_build_sidechains, unchanged — a side-chain atom of i against any atom (the nb backbone
+ * atoms, the current side-chain atoms) of a residue j != i of the same structure; between chain neighbours (|i - j| = 1 and equal
+ * chain_id) side chain against side chain only; SG-SG never.
+ * COST of candidate k of residue i given the current choice of all others, int64:
+ *   cost = prior_cost[i][k] + clash_weight * (penalty against all backbone atoms + penalty against the current side-chain atoms of
+ *   every other residue).
+ * ENERGY of a structure = sum of the priors of the chosen candidates + clash_weight * (all side chain - backbone penalties + every
+ * side chain - side chain pair once).
+ * SEARCH.  Initial state: for every residue the candidate of lowest prior + clash_weight * backbone penalty, the lowest k on ties.
+ * Then sweeps over the residues of the structure in index order: residue i moves to its candidate of lowest cost (lowest k on
+ * ties) only if that cost is strictly below the cost of its current candidate.  The energy is an integer and falls with every
+ * move, so the search ends.  It stops after a sweep without a move (converged = 1) or after max_sweeps sweeps; max_sweeps = 0
+ * returns the initial state.  A structure in which no residue has two candidates cannot move: no sweep is run and converged = 1.
+ * A structure of more than TH_PACK_MAX_STRUCT_RESIDUES residues is not packed: status TH_PACK_TOO_LONG, class -1 everywhere,
+ * everything else 0 — and the structures beside it are packed.  (One workgroup searches one structure, serially over its
+ * residues; the limit bounds its run time, not its memory.)
+ * Everything the search decides is an integer; no atomics; no pair is culled; a structure's outputs depend on its own residues
+ * alone, not on its place in the batch, and two calls give the same bytes.  Device memory: about 250 bytes per candidate + 380
+ * (+ 324 with a prior) per residue.  TH_EINVAL, before anything is launched or written: a negative or too large size, a NULL that
+ * is required (every output, ladder, and with residues backbone and res_type), struct_offsets not as described, a type outside
+ * -1 .. 19, a ladder that is not 1..8 finite positive strictly increasing levels, clash_weight, max_sweeps or a read entry of
+ * prior_cost out of range, unknown flag bits.  n_struct = 0 is success without a launch. */
+#define TH_PACK_MAX_CANDIDATES 81
+#define TH_PACK_MAX_LEVELS 8
+#define TH_PACK_MAX_COST 1000000
+#define TH_PACK_MAX_SWEEPS 1000
+#define TH_PACK_MAX_STRUCT_RESIDUES 4096
+#define TH_PACK_MAX_RESIDUES 16777216 /* 2^24: at most 81 x 2^24 < 2^31 candidates */
+#define TH_PACK_OK 0
+#define TH_PACK_TOO_LONG 1
+int th_pack_sidechains(int device, const double* backbone, const int8_t* res_type, const int32_t* chain_id, const int64_t* struct_offsets,
+                       int64_t n_struct, int64_t n_res, const double* ladder, int n_levels, const int32_t* prior_cost,
+                       int32_t clash_weight, int32_t max_sweeps, int flags, int16_t* out_cls, int64_t* out_cost_initial,
+                       int64_t* out_cost_final, int64_t* out_energy_initial, int64_t* out_energy_final, int32_t* out_search,
+                       double* kernel_ms);
+
 /* ---- superposition of models on their native: analyse_models.py — what the reference's calculate_RMSD_and_gdt
  * (scripts/analyse_af2.py) gets from PyMOL one pair at a time: cmd.align on the CA atoms, its RMSD, and the fractions of aligned
  * pairs within 1, 2, 4 and 8 Angstrom.  Here for a BATCH of position-paired coordinate lists in one launch.

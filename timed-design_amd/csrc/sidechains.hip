@@ -9,7 +9,8 @@
 //
 // k_build_sidechains: 16 lanes per residue, 16 residues per workgroup.  Lanes 0..2 hold N, CA, C; lane 3 + j owns side-chain atom j
 // of the residue's type (at most 10, TRP).  A loop runs over tree depth (the table's: 6 levels, ARG and TRP); at each level every
-// lane fetches its three parents from their lanes by shuffle and the lanes whose atom has that depth place it:
+// lane fetches its three parents from their lanes by shuffle and the lanes whose atom has that depth place it (sidechain_place.h,
+// shared with the packer's candidates):
 //     bc = (c - b) / |c - b|,  n = (b - a) x bc, normalised,  m = n x bc,
 //     d = c + ((-(L cos t)) bc + ((L sin t) cos p) m) + ((L sin t) sin p) n        t = bond angle, p = dihedral (IUPAC sign)
 // in float64, every product and sum rounded on its own; -(L cos t) and L sin t come from the host with the table.  A NaN backbone
@@ -33,63 +34,19 @@
 #include <vector>
 
 #include "common.h"
-#include "sidechain_table.h"
+#include "sidechain_place.h"
 
 // every float64 product and sum below is rounded separately, as the NumPy restatement's are
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kLanes = 16;                     // lanes per residue: 3 backbone atoms + at most 10 side-chain atoms
 constexpr int kBlock = 256;
 constexpr int kPerBlock = kBlock / kLanes;     // residues per workgroup of k_build_sidechains
 constexpr int kTile = 256;                     // slots j per LDS tile of k_sidechain_clashes = its threads
 constexpr int kJSlots = 4 + kScMaxAtoms;       // slots per residue on the j side: N, CA, C, O, side chain
 constexpr int kTileRes = 24;                   // residues per work item on the i side: 240 of 256 threads own a side-chain slot
 constexpr int kWave = 64;
-constexpr double kRad = 0.017453292519943295;  // pi / 180
-
-uint32_t pack_name(const char* s) {            // four ASCII bytes, left-justified, zero-padded, little-endian (as rotamers.hip)
-    uint32_t v = 0;
-    for (int i = 0; i < 4 && s[i]; ++i) v |= (uint32_t)(unsigned char)s[i] << (8 * i);
-    return v;
-}
-
-struct DevRow { double x, ls, offset; uint32_t name; signed char a, b, c, k, depth, pad[3]; };
-struct DevTable { int n[kScTypes]; int depth; uint32_t sg; DevRow row[kScTypes][kScMaxAtoms]; };
-
-__constant__ DevTable c_tab;
-
-const DevTable& host_table() {
-    static const DevTable tab = [] {
-        DevTable t;
-        std::memset(&t, 0, sizeof t);
-        t.sg = pack_name("SG");
-        for (int r = 0; r < kScTypes; ++r) {
-            const ScType& sc = kSidechains[r];
-            t.n[r] = sc.n;
-            int depth[3 + kScMaxAtoms] = {0, 0, 0};
-            for (int j = 0; j < sc.n; ++j) {
-                const ScRow& in = sc.row[j];
-                DevRow& out = t.row[r][j];
-                const double theta = in.angle * kRad;
-                out.x = -(in.length * std::cos(theta));
-                out.ls = in.length * std::sin(theta);
-                out.offset = in.offset;
-                out.name = pack_name(in.name);
-                out.a = in.a, out.b = in.b, out.c = in.c, out.k = in.k;
-                int d = depth[in.a] > depth[in.b] ? depth[in.a] : depth[in.b];
-                d = (d > depth[in.c] ? d : depth[in.c]) + 1;
-                depth[3 + j] = out.depth = (signed char)d;
-                if (d > t.depth) t.depth = d;
-            }
-        }
-        return t;
-    }();
-    return tab;
-}
-
-__device__ inline bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 
 __global__ void __launch_bounds__(kBlock) k_build_sidechains(const double* __restrict__ backbone, int nb, const signed char* __restrict__ res_type,
                                                              const double* __restrict__ chi, long long n_res,
@@ -113,32 +70,7 @@ __global__ void __launch_bounds__(kBlock) k_build_sidechains(const double* __res
         const size_t at = ((size_t)r * nb + lane) * 3;
         px = backbone[at], py = backbone[at + 1], pz = backbone[at + 2];
     }
-    double y = nan, z = nan;
-    const int pa = mine ? row.a : 0, pb = mine ? row.b : 0, pc = mine ? row.c : 0, depth = mine ? row.depth : 0;
-    if (mine) {
-        const double phi = ((row.k >= 0 ? chi[4 * (size_t)r + row.k] : 0.0) + row.offset) * kRad;
-        y = row.ls * cos(phi);
-        z = row.ls * sin(phi);
-    }
-    const int levels = c_tab.depth;
-    for (int level = 1; level <= levels; ++level) {                    // every lane shuffles, the lanes of this level place their atom
-        const double ax = __shfl(px, pa, kLanes), ay = __shfl(py, pa, kLanes), az = __shfl(pz, pa, kLanes);
-        const double bx = __shfl(px, pb, kLanes), by = __shfl(py, pb, kLanes), bz = __shfl(pz, pb, kLanes);
-        const double cx = __shfl(px, pc, kLanes), cy = __shfl(py, pc, kLanes), cz = __shfl(pz, pc, kLanes);
-        if (depth == level) {
-            double ux = cx - bx, uy = cy - by, uz = cz - bz;
-            const double ul = sqrt((ux * ux + uy * uy) + uz * uz);
-            ux = ux / ul, uy = uy / ul, uz = uz / ul;
-            const double vx = bx - ax, vy = by - ay, vz = bz - az;
-            double nx = vy * uz - vz * uy, ny = vz * ux - vx * uz, nz = vx * uy - vy * ux;
-            const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
-            nx = nx / nl, ny = ny / nl, nz = nz / nl;
-            const double mx = ny * uz - nz * uy, my = nz * ux - nx * uz, mz = nx * uy - ny * ux;
-            px = cx + ((row.x * ux + y * mx) + z * nx);
-            py = cy + ((row.x * uy + y * my) + z * ny);
-            pz = cz + ((row.x * uz + y * mz) + z * nz);
-        }
-    }
+    sc_place_lanes(row, mine, mine && row.k >= 0 ? chi[4 * (size_t)r + row.k] : 0.0, px, py, pz);
     const bool bad = (lane < 3 || mine) && !finite3(px, py, pz);
     const unsigned long long bad_mask = __ballot(bad);
     const int group = (threadIdx.x % warpSize) / kLanes;

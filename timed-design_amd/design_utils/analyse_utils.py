@@ -344,3 +344,69 @@ def tag_pdb_with_rot(workers: int, path_to_pdb, pdb_codes, device: int = 0) -> t
 def rotamer_labels_json(results_dict: dict) -> dict:
     """{key: [class or None]}: the labels file analyse_rotamers.py reads (--path_to_rotamer_labels) from a results_dict"""
     return {key: [None if v != v else int(v) for v in values] for key, values in results_dict.items()}
+
+
+# ---- side chains packed by a rotamer search (analyse_rotamers.py --pack; computed on the GPU by timed_hip.packer) ----------------
+def _types_of_sequence(sequence: str) -> np.ndarray:
+    from .amino_acids import standard_amino_acids
+    index = {one: k for k, one in enumerate(standard_amino_acids.keys())}
+    return np.array([index.get(letter, -1) for letter in sequence], dtype=np.int8)
+
+
+def _model_of_chains(chains: t.Dict[str, RotamerChain]):
+    from timed_hip import pdbio
+    return pdbio.Model(1, [r for chain in chains.values() for r in chain.residues])
+
+
+def pack_sidechains(structure: t.Dict[str, RotamerChain], sequence, device: int = 0, **packer_keywords):
+    """The place of the reference's pack_sidechains (analyse_utils.py:393-416: a structure and a sequence to SCWRL4, the packed
+    structure back) — SCWRL4 IS NOT CALLED (PARITY UNPINNED AGAINST SCWRL4: it is not available where this project is built).  The
+    sequence is packed onto the backbone by this project's own rotamer search, timed_hip.packer (an integer steric ladder, greedy
+    sweeps from a deterministic start; no rotamer library, no SCWRL4 energy), without a prior.
+
+    ``structure``: {chain id: RotamerChain}, an entry of tag_pdb_with_rot's ``pdb_to_assemblies``.  ``sequence``: one string of
+    one-letter codes over all chains in order, or one string per chain; a letter that is not one of the 20 leaves its residue
+    unbuilt.  Returns the timed_hip.packer.PackedSidechains (``.built.to_model()`` is the packed structure, ``.energy_final`` takes
+    the place of the SCWRL score)."""
+    from timed_hip import packer
+    sequence = sequence if isinstance(sequence, str) else "".join(sequence)
+    model = _model_of_chains(structure)
+    if len(sequence) != len(model.residues):
+        raise ValueError(f"the sequence has {len(sequence)} letters, the structure {len(model.residues)} residues")
+    return packer.pack([model], types=[_types_of_sequence(sequence)], prior="none", device=device, **packer_keywords)[0]
+
+
+def analyse_with_packer(pdb_to_seq: dict, pdb_to_assembly: dict, output_path, suffix: str, device: int = 0, **packer_keywords) -> t.Tuple[dict, dict]:
+    """The place of the reference's analyse_with_scwrl (analyse_utils.py:419-500) — SCWRL4 IS NOT CALLED (see pack_sidechains).
+    For every key ``<pdb><chain>`` of ``pdb_to_seq`` whose structure is in ``pdb_to_assembly`` ({pdb4: {chain: RotamerChain}}) the
+    sequence is paired by position with the residues of that chain; a chain without a sequence, or whose sequence has another
+    length (reported on stdout), keeps its native residue types, so that every chain packs against a complete neighbourhood.
+    ALL structures are packed in one batch on the GPU, without a prior, and written to ``<output_path>/<pdb4><suffix>.pdb``.
+    Returns ({key: final energy of the key's structure} — the counterpart of the SCWRL scores — and {pdb4: PackedSidechains})."""
+    from pathlib import Path
+
+    from timed_hip import packer, pdbio
+    output_path = Path(output_path)
+    output_path.mkdir(parents=True, exist_ok=True)
+    codes, models, types = [], [], []
+    for code in dict.fromkeys(str(key)[:4] for key in pdb_to_seq):
+        if code not in pdb_to_assembly:
+            print(f"Error with pdb code {code}: no structure")
+            continue
+        chains = pdb_to_assembly[code]
+        per_chain = []
+        for chain_id, chain in chains.items():
+            sequence = pdb_to_seq.get(f"{code}{chain_id}")
+            if sequence is not None and len(sequence) != len(chain):
+                print(f"Error with pdb code {code}{chain_id} - Length Mismatch")
+                sequence = None
+            per_chain.append(_types_of_sequence(chain.sequence if sequence is None else sequence))
+        codes.append(code)
+        models.append(_model_of_chains(chains))
+        types.append(np.concatenate(per_chain) if per_chain else np.zeros(0, np.int8))
+    packed = packer.pack(models, types=types, prior="none", device=device, **packer_keywords)
+    pdb_to_packed = dict(zip(codes, packed))
+    for code, result in pdb_to_packed.items():
+        pdbio.write_pdb(output_path / f"{code}{suffix}.pdb", result.built.to_model())
+    pdb_to_scores = {str(key): pdb_to_packed[str(key)[:4]].energy_final for key in pdb_to_seq if str(key)[:4] in pdb_to_packed}
+    return pdb_to_scores, pdb_to_packed

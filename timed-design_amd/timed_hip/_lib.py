@@ -91,6 +91,7 @@ PROTOTYPES = {
     "th_rotamer_table": (_i, [_i, _pi, _pi, _vp]),
     "th_build_sidechains": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _pd]),
     "th_sidechain_table": (_i, [_i, _pi, _vp, _vp, _vp, _vp, _pi, _vp, _vp]),
+    "th_pack_sidechains": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _vp, C.c_int32, C.c_int32, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "th_superpose": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _pd]),
     "th_lddt": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _pd]),
     "th_tmscore": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _pd]),
