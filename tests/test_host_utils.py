@@ -249,3 +249,11 @@ def test_legacy_rand_replays_numpys_global_generator():
 def test_runtime_units_are_built():
     import __graft_entry__
     assert {"devcache.hip", "planner.hip", "guard.hip", "predict.hip"} <= set(__graft_entry__.HIP_SOURCES)
+
+
+def test_one_shot_units_take_their_scaffolding_from_oneshot_h():
+    """moved, not copied: the eight one-shot entry points hold no align rule and no stream teardown of their own"""
+    csrc = os.path.join(os.path.dirname(G), os.pardir, "timed-design_amd", "csrc")
+    for unit in ("superpose", "lddt", "tmscore", "cealign", "packdensity", "rotamers", "sidechains", "pack_sidechains"):
+        source = open(os.path.join(csrc, unit + ".hip")).read()
+        assert "& ~(size_t)255" not in source and "hipStreamDestroy" not in source and '#include "oneshot.h"' in source, unit

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "oneshot.h"
 
 namespace {
 
@@ -196,23 +197,18 @@ void an_launch(hipStream_t s, int blocks, const AnArgs& a) {
     else hipLaunchKernelGGL((k_analyse<F16, 64>), dim3(blocks), dim3(kAnThreads), 0, s, a);
 }
 
-// everything one call holds on the device; released (after both streams drained) on every return path
-struct AnCall {
-    int device = -1;
-    hipStream_t st[2] = {nullptr, nullptr};
-    unsigned char* mem = nullptr;
-    ~AnCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        for (hipStream_t s : st)
-            if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t an_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
+
+// rows staged per block by th_analyse_probs and th_analyse_classes: a few hundred thousand, at most 256 MB of matrix.
+// TH_ANALYSIS_BLOCK_ROWS overrides it (tests: the blocking must not change a single result)
+int64_t th_analysis_block_rows(size_t row_bytes, int64_t n) {
+    int64_t block = std::min<int64_t>(262144, std::max<int64_t>(1, (int64_t)((256u << 20) / row_bytes)));
+    if (const char* e = std::getenv("TH_ANALYSIS_BLOCK_ROWS")) {
+        const long long v = std::atoll(e);
+        if (v > 0) block = v;
+    }
+    return std::min<int64_t>(block, n);
+}
 
 extern "C" int th_analyse_probs(int device, const void* matrix, int dtype, int64_t n, int64_t k, const int8_t* col_res,
                                 const int8_t* true_res, int8_t* pred_out, int8_t* rank_out, double* entropy_out,
@@ -228,40 +224,25 @@ extern "C" int th_analyse_probs(int device, const void* matrix, int dtype, int64
     if (n == 0) return TH_OK;
 
     const size_t esz = dtype == TH_F16 ? 2 : 4, row_bytes = esz * (size_t)k;
-    // rows staged per block: a few hundred thousand, at most 256 MB of matrix.  TH_ANALYSIS_BLOCK_ROWS overrides it (tests: the
-    // blocking must not change a single result)
-    int64_t block = std::min<int64_t>(262144, std::max<int64_t>(1, (int64_t)((256u << 20) / row_bytes)));
-    if (const char* e = std::getenv("TH_ANALYSIS_BLOCK_ROWS")) {
-        const long long v = std::atoll(e);
-        if (v > 0) block = v;
-    }
-    block = std::min<int64_t>(block, n);
+    const int64_t block = th_analysis_block_rows(row_bytes, n);
     const int64_t n_blocks = (n + block - 1) / block;
     const int slots = n_blocks > 1 ? 2 : 1;
 
-    AnCall call;
+    ThCall call;
     HIP_TRY(hipSetDevice(device));
     call.device = device;
     int ncu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
     // one allocation: totals, col_res, then per slot the matrix block (+16 bytes: the tile loads round the last row up to 16),
     // true residues and the per-row outputs
-    const size_t off_cres = an_align(kBins * sizeof(unsigned long long));
-    const size_t off_slot = off_cres + an_align((size_t)k);
-    const size_t sz_x = an_align(block * row_bytes + 16), sz_i8 = an_align((size_t)block), sz_ent = an_align((size_t)block * sizeof(double));
-    const size_t slot_bytes = sz_x + 3 * sz_i8 + sz_ent;
-    {
-        hipError_t e = th_malloc_retry(&call.mem, off_slot + slots * slot_bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            call.mem = nullptr;
-            th_set_error("th_analyse_probs: hipMalloc of %zu bytes: %s", off_slot + slots * slot_bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-        }
-    }
+    ThLayout lay, slot_lay;
+    const size_t o_tot = lay.take(kBins * sizeof(unsigned long long)), o_cres = lay.take((size_t)k), off_slot = lay.bytes;
+    const size_t o_x = slot_lay.take(block * row_bytes + 16), o_true = slot_lay.take((size_t)block), o_pred = slot_lay.take((size_t)block);
+    const size_t o_rank = slot_lay.take((size_t)block), o_ent = slot_lay.take((size_t)block * sizeof(double)), slot_bytes = slot_lay.bytes;
+    if (int rc = th_alloc_or_fail("th_analyse_probs", &call.mem[0], off_slot + slots * slot_bytes)) return rc;
     for (int s = 0; s < slots; ++s) HIP_TRY(hipStreamCreateWithFlags(&call.st[s], hipStreamNonBlocking));
-    unsigned long long* d_tot = (unsigned long long*)call.mem;
-    int8_t* d_cres = (int8_t*)(call.mem + off_cres);
+    unsigned long long* d_tot = call.at<unsigned long long>(o_tot);
+    int8_t* d_cres = call.at<int8_t>(o_cres);
     HIP_TRY(hipMemsetAsync(d_tot, 0, kBins * sizeof(unsigned long long), call.st[0]));
     HIP_TRY(hipMemcpyAsync(d_cres, col_res, (size_t)k, hipMemcpyHostToDevice, call.st[0]));
     HIP_TRY(hipStreamSynchronize(call.st[0]));          // both streams' kernels add into d_tot
@@ -278,12 +259,10 @@ extern "C" int th_analyse_probs(int device, const void* matrix, int dtype, int64
     for (int64_t b = 0; b < n_blocks; ++b) {
         const int s = (int)(b % slots);
         hipStream_t st = call.st[s];
-        unsigned char* slot = call.mem + off_slot + s * slot_bytes;
+        unsigned char* slot = call.at<unsigned char>(off_slot + s * slot_bytes + o_x);
         const int64_t lo = b * block, rows = std::min(block, n - lo);
-        int8_t* d_true = (int8_t*)(slot + sz_x);
-        int8_t* d_pred = (int8_t*)(slot + sz_x + sz_i8);
-        int8_t* d_rank = (int8_t*)(slot + sz_x + 2 * sz_i8);
-        double* d_ent = (double*)(slot + sz_x + 3 * sz_i8);
+        int8_t *d_true = (int8_t*)(slot + o_true), *d_pred = (int8_t*)(slot + o_pred), *d_rank = (int8_t*)(slot + o_rank);
+        double* d_ent = (double*)(slot + o_ent);
         HIP_TRY(hipMemcpyAsync(slot, (const unsigned char*)matrix + lo * row_bytes, rows * row_bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_true, true_res + lo, (size_t)rows, hipMemcpyHostToDevice, st));
         a.x = slot;

@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "horn_fit.h"
+#include "oneshot.h"
 
 // every float64 product, sum and quotient below is rounded on its own, as the NumPy restatement's are
 #pragma clang fp contract(off)
@@ -356,34 +357,13 @@ __global__ void __launch_bounds__(kWave) k_ce_best(const double* __restrict__ ca
     }
 }
 
-struct CeCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~CeCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t ce_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // offsets of one of the two lists: from 0 to total, never decreasing, no structure above the limit
-int ce_check_offsets(const char* side, const int64_t* offsets, int64_t total, int64_t n_pairs) {
-    if (offsets[0] != 0 || offsets[n_pairs] != total)
-        TH_FAIL(TH_EINVAL, "th_cealign: %s_offsets run from %lld to %lld, not from 0 to %s_total = %lld", side, (long long)offsets[0],
-                (long long)offsets[n_pairs], side, (long long)total);
-    for (int64_t p = 0; p < n_pairs; ++p) {
-        if (offsets[p + 1] < offsets[p]) TH_FAIL(TH_EINVAL, "th_cealign: %s_offsets[%lld] > %s_offsets[%lld]", side, (long long)p, side, (long long)p + 1);
+int ce_check_offsets(const char* side, const char* name, const char* total_name, const int64_t* offsets, int64_t total, int64_t n_pairs) {
+    if (int rc = th_check_offsets("th_cealign", name, total_name, offsets, n_pairs, total)) return rc;
+    for (int64_t p = 0; p < n_pairs; ++p)
         if (offsets[p + 1] - offsets[p] > TH_CE_MAX_POSITIONS)
             TH_FAIL(TH_EINVAL, "th_cealign: %s structure %lld has %lld positions (limit TH_CE_MAX_POSITIONS = %d)", side, (long long)p,
                     (long long)(offsets[p + 1] - offsets[p]), TH_CE_MAX_POSITIONS);
-    }
     return TH_OK;
 }
 
@@ -425,8 +405,8 @@ extern "C" int th_cealign(int device, const double* ref_xyz, int64_t ref_total, 
     if (!ref_offsets || !mob_offsets || !score_out || !count_out || (ref_total > 0 && (!ref_xyz || !align_out)) || (mob_total > 0 && !mob_xyz))
         TH_FAIL(TH_EINVAL, "th_cealign: n_pairs = %lld needs ref_offsets, mob_offsets, score_out and count_out, ref_total = %lld needs ref_xyz and "
                            "align_out, mob_total = %lld needs mob_xyz", (long long)n_pairs, (long long)ref_total, (long long)mob_total);
-    if (int rc = ce_check_offsets("ref", ref_offsets, ref_total, n_pairs)) return rc;
-    if (int rc = ce_check_offsets("mob", mob_offsets, mob_total, n_pairs)) return rc;
+    if (int rc = ce_check_offsets("ref", "ref_offsets", "ref_total", ref_offsets, ref_total, n_pairs)) return rc;
+    if (int rc = ce_check_offsets("mob", "mob_offsets", "mob_total", mob_offsets, mob_total, n_pairs)) return rc;
 
     const size_t np = (size_t)n_pairs, nr = (size_t)ref_total;
     std::vector<CePair> pairs(np + 1);
@@ -462,48 +442,22 @@ extern "C" int th_cealign(int device, const double* ref_xyz, int64_t ref_total, 
         TH_FAIL(TH_EINVAL, "th_cealign: %lld window pairs in one call (limit 2^33 - 4): submit fewer pairs at once", n_windows);
     const size_t nca = orig_a.size(), ncb = orig_b.size(), nw = (size_t)n_windows;
 
-    CeCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
-    const size_t off_cb = ce_align(nca * 3 * sizeof(double));
-    const size_t off_oa = off_cb + ce_align(ncb * 3 * sizeof(double));
-    const size_t off_ob = off_oa + ce_align(nca * sizeof(int));
-    const size_t off_pairs = off_ob + ce_align(ncb * sizeof(int));
-    const size_t off_wa = off_pairs + ce_align((np + 1) * sizeof(CePair));
-    const size_t off_wb = off_wa + ce_align((size_t)rows_a * kTerms * sizeof(double));
-    const size_t off_s = off_wb + ce_align((size_t)rows_b * kTerms * sizeof(double));
-    const size_t off_len = off_s + ce_align(nw * sizeof(double));
-    const size_t off_ps = off_len + ce_align(nw * sizeof(int));
-    const size_t off_align = off_ps + ce_align(nw * sizeof(double));
-    const size_t off_score = off_align + ce_align(nr * sizeof(int32_t));
-    const size_t off_count = off_score + ce_align(np * 2 * sizeof(double));
-    const size_t off_tr = off_count + ce_align(np * 6 * sizeof(int64_t));
-    const size_t bytes = off_tr + ce_align(transform_out ? np * 12 * sizeof(double) : 0) + 256;      // never a zero-byte allocation
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_cealign: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    double* d_ca = (double*)call.mem;
-    double* d_cb = (double*)(call.mem + off_cb);
-    int* d_oa = (int*)(call.mem + off_oa);
-    int* d_ob = (int*)(call.mem + off_ob);
-    CePair* d_pairs = (CePair*)(call.mem + off_pairs);
-    double* d_wa = (double*)(call.mem + off_wa);
-    double* d_wb = (double*)(call.mem + off_wb);
-    double* d_s = (double*)(call.mem + off_s);
-    int* d_len = (int*)(call.mem + off_len);
-    double* d_ps = (double*)(call.mem + off_ps);
-    int* d_align = (int*)(call.mem + off_align);
-    double* d_score = (double*)(call.mem + off_score);
-    long long* d_count = (long long*)(call.mem + off_count);
-    double* d_tr = transform_out ? (double*)(call.mem + off_tr) : nullptr;
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_ca = lay.take(nca * 3 * sizeof(double)), o_cb = lay.take(ncb * 3 * sizeof(double));
+    const size_t o_oa = lay.take(nca * sizeof(int)), o_ob = lay.take(ncb * sizeof(int)), o_pairs = lay.take((np + 1) * sizeof(CePair));
+    const size_t o_wa = lay.take((size_t)rows_a * kTerms * sizeof(double)), o_wb = lay.take((size_t)rows_b * kTerms * sizeof(double));
+    const size_t o_s = lay.take(nw * sizeof(double)), o_len = lay.take(nw * sizeof(int)), o_ps = lay.take(nw * sizeof(double));
+    const size_t o_align = lay.take(nr * sizeof(int32_t)), o_score = lay.take(np * 2 * sizeof(double)), o_count = lay.take(np * 6 * sizeof(int64_t));
+    const size_t o_tr = lay.take(transform_out ? np * 12 * sizeof(double) : 0);
+    ThCall call;
+    if (int rc = call.open("th_cealign", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
+    double *d_ca = call.at<double>(o_ca), *d_cb = call.at<double>(o_cb), *d_wa = call.at<double>(o_wa), *d_wb = call.at<double>(o_wb);
+    double *d_s = call.at<double>(o_s), *d_ps = call.at<double>(o_ps), *d_score = call.at<double>(o_score);
+    double* d_tr = transform_out ? call.at<double>(o_tr) : nullptr;
+    int *d_oa = call.at<int>(o_oa), *d_ob = call.at<int>(o_ob), *d_len = call.at<int>(o_len), *d_align = call.at<int>(o_align);
+    CePair* d_pairs = call.at<CePair>(o_pairs);
+    long long* d_count = call.at<long long>(o_count);
+    hipStream_t st = call.st[0];
     if (nca) {
         HIP_TRY(hipMemcpyAsync(d_ca, ca.data(), nca * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_oa, orig_a.data(), nca * sizeof(int), hipMemcpyHostToDevice, st));
@@ -513,7 +467,7 @@ extern "C" int th_cealign(int device, const double* ref_xyz, int64_t ref_total, 
         HIP_TRY(hipMemcpyAsync(d_ob, orig_b.data(), ncb * sizeof(int), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), (np + 1) * sizeof(CePair), hipMemcpyHostToDevice, st));
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     if (nw) {
         hipLaunchKernelGGL(k_ce_windows, dim3((unsigned)((rows_a + rows_b + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_ca, d_cb, d_pairs,
                            (long long)n_pairs, rows_a, rows_b, d_wa, d_wb);
@@ -527,16 +481,10 @@ extern "C" int th_cealign(int device, const double* ref_xyz, int64_t ref_total, 
     hipLaunchKernelGGL(k_ce_best, dim3((unsigned)np), dim3(kWave), 0, st, d_ca, d_cb, d_oa, d_ob, d_pairs, d_s, d_len, d_ps, d0, d1, gap_max, d_align,
                        d_score, d_count, d_tr);
     HIP_TRY(hipGetLastError());
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     if (nr) HIP_TRY(hipMemcpyAsync(align_out, d_align, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(score_out, d_score, np * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(count_out, d_count, np * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (transform_out) HIP_TRY(hipMemcpyAsync(transform_out, d_tr, np * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
-        *kernel_ms = ms;
-    }
-    return TH_OK;
+    return call.finish(kernel_ms);
 }

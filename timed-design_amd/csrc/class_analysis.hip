@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "common.h"
+#include "oneshot.h"
 
 namespace {
 
@@ -238,33 +239,6 @@ __global__ void __launch_bounds__(kThreads) k_pair_sweep(SweepArgs a) {
         if (acc[c]) atomicAdd(&a.u2[(size_t)c * k + run.cls], acc[c]);
 }
 
-// everything one call holds on the device; released (after both streams drained) on every return path
-struct ClCall {
-    int device = -1;
-    hipStream_t st[2] = {nullptr, nullptr};
-    unsigned char* mem = nullptr;
-    unsigned char* sort_mem = nullptr;
-    ~ClCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        for (hipStream_t s : st)
-            if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-        if (mem) (void)hipFree(mem);
-        if (sort_mem) (void)hipFree(sort_mem);
-    }
-};
-
-size_t cl_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int cl_malloc(unsigned char** p, size_t bytes) {
-    hipError_t e = th_malloc_retry(p, bytes);
-    if (e == hipSuccess) return TH_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    th_set_error("th_analyse_classes: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-}
-
 // labelled rows of every staging block grouped by true class, cut into runs of at most kRun rows
 struct Grouping {
     std::vector<int> order;            // [labelled rows], block after block
@@ -316,13 +290,7 @@ extern "C" int th_analyse_classes(int device, const void* matrix, int dtype, int
     if (n == 0) return TH_OK;
 
     const size_t esz = dtype == TH_F16 ? 2 : 4, row_bytes = esz * (size_t)k;
-    // rows staged per block: as th_analyse_probs (at most 262 144 rows and 256 MB; TH_ANALYSIS_BLOCK_ROWS overrides the row count)
-    int64_t block = std::min<int64_t>(262144, std::max<int64_t>(1, (int64_t)((256u << 20) / row_bytes)));
-    if (const char* e = std::getenv("TH_ANALYSIS_BLOCK_ROWS")) {
-        const long long v = std::atoll(e);
-        if (v > 0) block = v;
-    }
-    block = std::min<int64_t>(block, n);
+    const int64_t block = th_analysis_block_rows(row_bytes, n);       // as th_analyse_probs
     const int64_t n_blocks = (n + block - 1) / block;
     const int slots = n_blocks > 1 ? 2 : 1;
     const bool auc = pair_u2 != nullptr;
@@ -342,7 +310,7 @@ extern "C" int th_analyse_classes(int device, const void* matrix, int dtype, int
         max_runs = std::max(max_runs, grp.run_lo[b + 1] - grp.run_lo[b]);
     }
 
-    ClCall call;
+    ThCall call;
     HIP_TRY(hipSetDevice(device));
     call.device = device;
     int ncu = 0;
@@ -351,29 +319,28 @@ extern "C" int th_analyse_classes(int device, const void* matrix, int dtype, int
     // the packed value (twice: the sort's output), the positives and the scored flag, then per slot the matrix block (+16 bytes:
     // the tile loads round the last row up to 16), its labels, per-row outputs, row order and runs
     const size_t n_tot = kk + ((size_t)k + 1) + (size_t)k + 3 + (auc ? kk : 0);
-    const size_t off_offset = cl_align(n_tot * sizeof(unsigned long long));
-    const size_t off_packed = off_offset + cl_align(((size_t)k + 1) * sizeof(long long));
-    const size_t sz_packed = auc ? cl_align((size_t)n * 8) : 0, sz_keys = auc ? cl_align((size_t)n * 4) : 0, sz_flag = auc ? cl_align((size_t)n) : 0;
-    const size_t off_slot = off_packed + 2 * sz_packed + sz_keys + sz_flag;
-    const size_t sz_x = cl_align(block * row_bytes + 16), sz_i16 = cl_align((size_t)block * 2);
-    const size_t sz_order = cl_align(max_order * sizeof(int)), sz_runs = cl_align(max_runs * sizeof(Run));
-    const size_t slot_bytes = sz_x + 3 * sz_i16 + sz_order + sz_runs;
-    if (int rc = cl_malloc(&call.mem, off_slot + slots * slot_bytes)) return rc;
+    ThLayout lay, slot_lay;
+    const size_t o_tot = lay.take(n_tot * sizeof(unsigned long long)), o_offset = lay.take(((size_t)k + 1) * sizeof(long long));
+    const size_t o_packed = lay.take(auc ? (size_t)n * 8 : 0), o_sorted = lay.take(auc ? (size_t)n * 8 : 0);
+    const size_t o_keys = lay.take(auc ? (size_t)n * 4 : 0), o_flag = lay.take(auc ? (size_t)n : 0), off_slot = lay.bytes;
+    const size_t o_x = slot_lay.take(block * row_bytes + 16), o_true = slot_lay.take((size_t)block * 2), o_pred = slot_lay.take((size_t)block * 2);
+    const size_t o_rank = slot_lay.take((size_t)block * 2), o_order = slot_lay.take(max_order * sizeof(int)), o_runs = slot_lay.take(max_runs * sizeof(Run));
+    const size_t slot_bytes = slot_lay.bytes;
+    if (int rc = th_alloc_or_fail("th_analyse_classes", &call.mem[0], off_slot + slots * slot_bytes)) return rc;
     for (int s = 0; s < slots; ++s) HIP_TRY(hipStreamCreateWithFlags(&call.st[s], hipStreamNonBlocking));
-    unsigned long long* d_conf = (unsigned long long*)call.mem;
+    unsigned long long* d_conf = call.at<unsigned long long>(o_tot);
     unsigned long long* d_rank_hist = d_conf + kk;
     unsigned long long* d_scored_count = d_rank_hist + k + 1;
     unsigned long long* d_counts = d_scored_count + k;
     unsigned long long* d_u2 = d_counts + 3;
-    long long* d_offset = (long long*)(call.mem + off_offset);
-    unsigned long long* d_packed = (unsigned long long*)(call.mem + off_packed);
-    unsigned long long* d_sorted = (unsigned long long*)(call.mem + off_packed + sz_packed);
-    uint32_t* d_keys = (uint32_t*)(call.mem + off_packed + 2 * sz_packed);
-    unsigned char* d_flag = call.mem + off_packed + 2 * sz_packed + sz_keys;
-    HIP_TRY(hipMemsetAsync(call.mem, 0, n_tot * sizeof(unsigned long long), call.st[0]));
+    long long* d_offset = call.at<long long>(o_offset);
+    unsigned long long *d_packed = call.at<unsigned long long>(o_packed), *d_sorted = call.at<unsigned long long>(o_sorted);
+    uint32_t* d_keys = call.at<uint32_t>(o_keys);
+    unsigned char* d_flag = call.at<unsigned char>(o_flag);
+    HIP_TRY(hipMemsetAsync(d_conf, 0, n_tot * sizeof(unsigned long long), call.st[0]));
     HIP_TRY(hipStreamSynchronize(call.st[0]));          // both streams' kernels add into the totals
 
-    auto slot_of = [&](int s) { return call.mem + off_slot + s * slot_bytes; };
+    auto slot_of = [&](int s) { return call.at<unsigned char>(off_slot + s * slot_bytes + o_x); };
     // ---- step 1: the row pass.  Block b runs on stream b % 2 in slot b % 2: the copy of block b + 1 overlaps the kernel of block b
     RowArgs ra{};
     ra.confusion = d_conf;
@@ -386,9 +353,7 @@ extern "C" int th_analyse_classes(int device, const void* matrix, int dtype, int
         hipStream_t st = call.st[s];
         unsigned char* slot = slot_of(s);
         const int64_t lo = b * block, rows = std::min(block, n - lo);
-        int16_t* d_true = (int16_t*)(slot + sz_x);
-        int16_t* d_pred = (int16_t*)(slot + sz_x + sz_i16);
-        int16_t* d_rank = (int16_t*)(slot + sz_x + 2 * sz_i16);
+        int16_t *d_true = (int16_t*)(slot + o_true), *d_pred = (int16_t*)(slot + o_pred), *d_rank = (int16_t*)(slot + o_rank);
         HIP_TRY(hipMemcpyAsync(slot, (const unsigned char*)matrix + lo * row_bytes, rows * row_bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_true, true_class + lo, (size_t)rows * 2, hipMemcpyHostToDevice, st));
         ra.x = slot;
@@ -420,8 +385,8 @@ extern "C" int th_analyse_classes(int device, const void* matrix, int dtype, int
     HIP_TRY(hipMemcpyAsync(d_offset, offset.data(), ((size_t)k + 1) * sizeof(long long), hipMemcpyHostToDevice, s0));
     size_t tmp_bytes = 0;
     HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_packed, d_sorted, (size_t)n, 0u, kSortBits, s0));
-    if (int rc = cl_malloc(&call.sort_mem, std::max<size_t>(tmp_bytes, 256))) return rc;
-    HIP_TRY(rocprim::radix_sort_keys(call.sort_mem, tmp_bytes, d_packed, d_sorted, (size_t)n, 0u, kSortBits, s0));
+    if (int rc = th_alloc_or_fail("th_analyse_classes", &call.mem[1], std::max<size_t>(tmp_bytes, 256))) return rc;
+    HIP_TRY(rocprim::radix_sort_keys(call.mem[1], tmp_bytes, d_packed, d_sorted, (size_t)n, 0u, kSortBits, s0));
     const long long n_scored = counts->n_scored;
     hipLaunchKernelGGL(k_positives, dim3((unsigned)((n_scored + kThreads - 1) / kThreads)), dim3(kThreads), 0, s0, d_sorted, d_keys, n_scored);
     HIP_TRY(hipGetLastError());
@@ -440,8 +405,8 @@ extern "C" int th_analyse_classes(int device, const void* matrix, int dtype, int
         hipStream_t st = call.st[s];
         unsigned char* slot = slot_of(s);
         const int64_t lo = b * block, rows = std::min(block, n - lo);
-        int* d_order = (int*)(slot + sz_x + 3 * sz_i16);
-        Run* d_runs = (Run*)(slot + sz_x + 3 * sz_i16 + sz_order);
+        int* d_order = (int*)(slot + o_order);
+        Run* d_runs = (Run*)(slot + o_runs);
         if (n_blocks > 1)
             HIP_TRY(hipMemcpyAsync(slot, (const unsigned char*)matrix + lo * row_bytes, rows * row_bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_order, grp.order.data() + grp.order_lo[b], n_order * sizeof(int), hipMemcpyHostToDevice, st));

@@ -96,6 +96,9 @@ template <class T> inline hipError_t th_malloc_retry(T** p, size_t bytes) { retu
 // 11 k / 100 k with 128.  Host-side thread pools size themselves with this.
 int th_usable_cpus();
 
+// rows of the probability matrix that th_analyse_probs and th_analyse_classes stage per block (analysis.hip)
+int64_t th_analysis_block_rows(size_t row_bytes, int64_t n);
+
 // ---- device-side views --------------------------------------------------------------------
 // A channels-last activation tensor, possibly a channel slice of a wider (concat) buffer.
 // element (f, v, c) lives at p[f*fs + v*cs + coff + c], v = (z*H + y)*W + x.

@@ -1,6 +1,22 @@
-// Elementwise device helpers shared by every kernel: Keras activations and the fused epilogue.
+// Device helpers shared by every kernel: the wave-wide sums, Keras activations and the fused epilogue.
 #pragma once
 #include "common.h"
+
+// the sum of v over the 64 lanes of a wavefront, in every lane (xor butterfly: every lane adds in the same order)
+__device__ inline double wave_sum(double v) {
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__device__ inline int wave_sum(int v) {
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__device__ inline long long wave_sum(long long v) {
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
 
 // Keras semantics: ELU x>0 ? x : alpha*(exp(x)-1); LeakyReLU x>0 ? x : alpha*x.
 __device__ __forceinline__ float th_act(float x, int act, float alpha) {

@@ -1,8 +1,10 @@
-// The least-squares fit shared by th_superpose (superpose.hip) and th_tmscore (tmscore.hip): the wave-wide sums, the finiteness test of
-// a position, one Jacobi rotation and Horn's quaternion route from a 3 x 3 cross-covariance to the proper rotation.  Device code for
-// one 64-lane wavefront; every lane computes the same bits.
+// The least-squares fit shared by th_superpose (superpose.hip) and th_tmscore (tmscore.hip): the finiteness test of a position, one
+// Jacobi rotation and Horn's quaternion route from a 3 x 3 cross-covariance to the proper rotation; the wave-wide sums are
+// device_math.h's.  Device code for one 64-lane wavefront; every lane computes the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "device_math.h"
 
 // every float64 product and sum below is rounded separately, as the NumPy restatement's are
 #pragma clang fp contract(off)
@@ -11,16 +13,6 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kSweeps = 10;                       // Jacobi sweeps at most (a 4 x 4 matrix is diagonal to the last bit after 5 or 6)
-
-__device__ inline double wave_sum(double v) {
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-
-__device__ inline int wave_sum(int v) {
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
 
 __device__ inline bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 

@@ -27,6 +27,8 @@
 #include <vector>
 
 #include "common.h"
+#include "device_math.h"
+#include "oneshot.h"
 
 // every float64 product and sum below is rounded separately, as the NumPy restatement's are
 #pragma clang fp contract(off)
@@ -136,11 +138,6 @@ __global__ void __launch_bounds__(kTile) k_lddt(const double* __restrict__ ref_x
     }
 }
 
-__device__ inline long long wave_sum(long long v) {
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-
 __global__ void __launch_bounds__(kTile) k_lddt_totals(const double* __restrict__ ref_xyz, const double* __restrict__ mob_xyz,
                                                        const long long* __restrict__ offsets, long long n_pairs,
                                                        const int* __restrict__ residue, long long* __restrict__ pair_out) {
@@ -161,23 +158,6 @@ __global__ void __launch_bounds__(kTile) k_lddt_totals(const double* __restrict_
         for (int k = 0; k < 6; ++k) pair_out[6 * pair + k] = sum[k];
     }
 }
-
-struct LdCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~LdCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t ld_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -202,11 +182,7 @@ extern "C" int th_lddt(int device, const double* ref_xyz, const double* mob_xyz,
     if (!offsets || !pair_out || (total > 0 && (!ref_xyz || !mob_xyz || !residue_out)))
         TH_FAIL(TH_EINVAL, "th_lddt: n_pairs = %lld needs offsets and pair_out, total = %lld needs ref_xyz, mob_xyz and residue_out",
                 (long long)n_pairs, (long long)total);
-    if (offsets[0] != 0 || offsets[n_pairs] != total)
-        TH_FAIL(TH_EINVAL, "th_lddt: offsets run from %lld to %lld, not from 0 to total = %lld", (long long)offsets[0], (long long)offsets[n_pairs],
-                (long long)total);
-    for (int64_t p = 0; p < n_pairs; ++p)
-        if (offsets[p + 1] < offsets[p]) TH_FAIL(TH_EINVAL, "th_lddt: offsets[%lld] > offsets[%lld]", (long long)p, (long long)p + 1);
+    if (int rc = th_check_offsets("th_lddt", "offsets", "total", offsets, n_pairs, total)) return rc;
     std::vector<Item> items;
     try {
         for (int64_t p = 0; p < n_pairs; ++p) {
@@ -218,40 +194,25 @@ extern "C" int th_lddt(int device, const double* ref_xyz, const double* mob_xyz,
     }
     if (items.size() > (size_t)INT_MAX) TH_FAIL(TH_EINVAL, "th_lddt: %zu work items in one call (limit 2^31 - 1)", items.size());
 
-    LdCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
     const size_t n = (size_t)total, np = (size_t)n_pairs;
-    const size_t off_mob = ld_align(n * 3 * sizeof(double));
-    const size_t off_offsets = off_mob + ld_align(n * 3 * sizeof(double));
-    const size_t off_items = off_offsets + ld_align((np + 1) * sizeof(int64_t));
-    const size_t off_res = off_items + ld_align(items.size() * sizeof(Item));
-    const size_t off_pair = off_res + ld_align(n * 5 * sizeof(int32_t));
-    const size_t bytes = off_pair + ld_align(np * 6 * sizeof(int64_t));
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_lddt: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    double* d_ref = (double*)call.mem;
-    double* d_mob = (double*)(call.mem + off_mob);
-    long long* d_offsets = (long long*)(call.mem + off_offsets);
-    Item* d_items = (Item*)(call.mem + off_items);
-    int* d_res = (int*)(call.mem + off_res);
-    long long* d_pair = (long long*)(call.mem + off_pair);
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_ref = lay.take(n * 3 * sizeof(double)), o_mob = lay.take(n * 3 * sizeof(double));
+    const size_t o_offsets = lay.take((np + 1) * sizeof(int64_t)), o_items = lay.take(items.size() * sizeof(Item));
+    const size_t o_res = lay.take(n * 5 * sizeof(int32_t)), o_pair = lay.take(np * 6 * sizeof(int64_t));
+    ThCall call;
+    if (int rc = call.open("th_lddt", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
+    double *d_ref = call.at<double>(o_ref), *d_mob = call.at<double>(o_mob);
+    long long *d_offsets = call.at<long long>(o_offsets), *d_pair = call.at<long long>(o_pair);
+    Item* d_items = call.at<Item>(o_items);
+    int* d_res = call.at<int>(o_res);
+    hipStream_t st = call.st[0];
     if (n) {
         HIP_TRY(hipMemcpyAsync(d_ref, ref_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_mob, mob_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     if (!items.empty()) {
         hipLaunchKernelGGL(k_lddt, dim3((unsigned)items.size()), dim3(kTile), 0, st, d_ref, d_mob, d_offsets, d_items, th_packing_threshold(radius),
                            lim, d_res);
@@ -260,14 +221,8 @@ extern "C" int th_lddt(int device, const double* ref_xyz, const double* mob_xyz,
     hipLaunchKernelGGL(k_lddt_totals, dim3((unsigned)((np + kPerBlock - 1) / kPerBlock)), dim3(kTile), 0, st, d_ref, d_mob, d_offsets,
                        (long long)n_pairs, d_res, d_pair);
     HIP_TRY(hipGetLastError());
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     if (n) HIP_TRY(hipMemcpyAsync(residue_out, d_res, n * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(pair_out, d_pair, np * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
-        *kernel_ms = ms;
-    }
-    return TH_OK;
+    return call.finish(kernel_ms);
 }

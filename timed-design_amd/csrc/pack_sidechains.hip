@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "oneshot.h"
 #include "sidechain_place.h"
 
 #pragma clang fp contract(off)
@@ -370,23 +371,6 @@ __global__ void __launch_bounds__(kSearch) k_pack_search(SearchArgs a, Ladder la
     }
 }
 
-struct PackCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~PackCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t pk_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int pow3(int n) { int v = 1; while (n-- > 0) v *= 3; return v; }
 
 }  // namespace
@@ -415,12 +399,7 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     if (n_struct == 0 && n_res != 0) TH_FAIL(TH_EINVAL, "th_pack_sidechains: n_struct = 0 owns no residue, n_res = %lld", (long long)n_res);
     if (n_struct == 0) return TH_OK;
     if (!struct_offsets) TH_FAIL(TH_EINVAL, "th_pack_sidechains: n_struct = %lld needs struct_offsets", (long long)n_struct);
-    if (struct_offsets[0] != 0 || struct_offsets[n_struct] != n_res)
-        TH_FAIL(TH_EINVAL, "th_pack_sidechains: struct_offsets run from %lld to %lld, not from 0 to n_res = %lld", (long long)struct_offsets[0],
-                (long long)struct_offsets[n_struct], (long long)n_res);
-    for (int64_t s = 0; s < n_struct; ++s)
-        if (struct_offsets[s + 1] < struct_offsets[s])
-            TH_FAIL(TH_EINVAL, "th_pack_sidechains: struct_offsets[%lld] > struct_offsets[%lld]", (long long)s, (long long)s + 1);
+    if (int rc = th_check_offsets("th_pack_sidechains", "struct_offsets", "n_res", struct_offsets, n_struct, n_res)) return rc;
     if (!out_energy_initial || !out_energy_final || !out_search)
         TH_FAIL(TH_EINVAL, "th_pack_sidechains: n_struct = %lld needs out_energy_initial, out_energy_final and out_search", (long long)n_struct);
     if (n_res > 0 && (!backbone || !res_type || !out_cls || !out_cost_initial || !out_cost_final))
@@ -483,42 +462,25 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     const int tile = max_len < 1 ? 1 : max_len < kResTile ? max_len : kResTile;
     const size_t lds_bytes = (size_t)tile * (kXyz * sizeof(double) + 2 * sizeof(int));
 
-    PackCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
-    size_t bytes = 0;
-    auto take = [&bytes](size_t b) { const size_t at = bytes; bytes += pk_align(b); return at; };
-    const size_t off_bb = take(nr * nb * 3 * sizeof(double)), off_type = take(nr), off_chain = take(chain_id ? nr * sizeof(int32_t) : 0);
-    const size_t off_soff = take((ns + 1) * sizeof(int64_t)), off_coff = take((nr + 1) * sizeof(long long)), off_cres = take(ncand * sizeof(int));
-    const size_t off_cxyz = take(ncand * kXyz * sizeof(double)), off_cok = take(ncand), off_bbpen = take(ncand * sizeof(int));
-    const size_t off_prior = take(prior_cost ? nr * kMaxCand * sizeof(int32_t) : 0), off_items = take(items.size() * sizeof(PItem));
-    const size_t off_cur = take(nr * kXyz * sizeof(double)), off_curk = take(nr * sizeof(int)), off_cls = take(nr * sizeof(int16_t));
-    const size_t off_c0 = take(nr * sizeof(int64_t)), off_c1 = take(nr * sizeof(int64_t)), off_e0 = take(ns * sizeof(int64_t));
-    const size_t off_e1 = take(ns * sizeof(int64_t)), off_search = take(ns * 4 * sizeof(int32_t));
-    bytes += 256;                                                      // never a zero-byte allocation
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_pack_sidechains: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    unsigned char* mem = call.mem;
-    double* d_bb = (double*)(mem + off_bb);
-    signed char* d_type = (signed char*)(mem + off_type);
-    int* d_chain = chain_id ? (int*)(mem + off_chain) : nullptr;
-    long long* d_soff = (long long*)(mem + off_soff);
-    long long* d_coff = (long long*)(mem + off_coff);
-    int* d_cres = (int*)(mem + off_cres);
-    double* d_cxyz = (double*)(mem + off_cxyz);
-    unsigned char* d_cok = mem + off_cok;
-    int* d_bbpen = (int*)(mem + off_bbpen);
-    int* d_prior = prior_cost ? (int*)(mem + off_prior) : nullptr;
-    PItem* d_items = (PItem*)(mem + off_items);
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_bb = lay.take(nr * nb * 3 * sizeof(double)), o_type = lay.take(nr), o_chain = lay.take(chain_id ? nr * sizeof(int32_t) : 0);
+    const size_t o_soff = lay.take((ns + 1) * sizeof(int64_t)), o_coff = lay.take((nr + 1) * sizeof(long long)), o_cres = lay.take(ncand * sizeof(int));
+    const size_t o_cxyz = lay.take(ncand * kXyz * sizeof(double)), o_cok = lay.take(ncand), o_bbpen = lay.take(ncand * sizeof(int));
+    const size_t o_prior = lay.take(prior_cost ? nr * kMaxCand * sizeof(int32_t) : 0), o_items = lay.take(items.size() * sizeof(PItem));
+    const size_t o_cur = lay.take(nr * kXyz * sizeof(double)), o_curk = lay.take(nr * sizeof(int)), o_cls = lay.take(nr * sizeof(int16_t));
+    const size_t o_c0 = lay.take(nr * sizeof(int64_t)), o_c1 = lay.take(nr * sizeof(int64_t)), o_e0 = lay.take(ns * sizeof(int64_t));
+    const size_t o_e1 = lay.take(ns * sizeof(int64_t)), o_search = lay.take(ns * 4 * sizeof(int32_t));
+    ThCall call;
+    if (int rc = call.open("th_pack_sidechains", device, lay.bytes, kernel_ms ? 4 : 0)) return rc;
+    double *d_bb = call.at<double>(o_bb), *d_cxyz = call.at<double>(o_cxyz);
+    signed char* d_type = call.at<signed char>(o_type);
+    int* d_chain = chain_id ? call.at<int>(o_chain) : nullptr;
+    long long *d_soff = call.at<long long>(o_soff), *d_coff = call.at<long long>(o_coff);
+    int *d_cres = call.at<int>(o_cres), *d_bbpen = call.at<int>(o_bbpen);
+    unsigned char* d_cok = call.at<unsigned char>(o_cok);
+    int* d_prior = prior_cost ? call.at<int>(o_prior) : nullptr;
+    PItem* d_items = call.at<PItem>(o_items);
+    hipStream_t st = call.st[0];
     const DevTable& dev_tab = host_table();
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_tab), &dev_tab, sizeof dev_tab, 0, hipMemcpyHostToDevice, st));   // the same bytes every call
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_pack), &tab, sizeof tab, 0, hipMemcpyHostToDevice, st));
@@ -532,28 +494,28 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     HIP_TRY(hipMemcpyAsync(d_coff, cand_off.data(), (nr + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     if (ncand) HIP_TRY(hipMemcpyAsync(d_cres, cand_res.data(), ncand * sizeof(int), hipMemcpyHostToDevice, st));
     if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(PItem), hipMemcpyHostToDevice, st));
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     if (ncand) {
         hipLaunchKernelGGL(k_pack_candidates, dim3((unsigned)((ncand + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_bb, nb, d_type, d_coff, d_cres,
                            (long long)ncand, d_cxyz, d_cok);
         HIP_TRY(hipGetLastError());
     }
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     if (!items.empty()) {
         hipLaunchKernelGGL(k_pack_backbone, dim3((unsigned)items.size()), dim3(kBlock), 0, st, d_bb, nb, d_chain, d_soff, d_coff, d_cres, d_cxyz, d_items,
                            lad, d_bbpen);
         HIP_TRY(hipGetLastError());
     }
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[2], st));
+    HIP_TRY(call.mark(2));
     SearchArgs a;
     a.res_type = d_type, a.offsets = d_soff, a.cand_off = d_coff, a.cand_xyz = d_cxyz, a.cand_ok = d_cok, a.bb_pen = d_bbpen, a.prior = d_prior;
-    a.cur_xyz = (double*)(mem + off_cur), a.cur_k = (int*)(mem + off_curk), a.out_cls = (short*)(mem + off_cls);
-    a.out_cost0 = (long long*)(mem + off_c0), a.out_cost1 = (long long*)(mem + off_c1);
-    a.out_e0 = (long long*)(mem + off_e0), a.out_e1 = (long long*)(mem + off_e1), a.out_search = (int*)(mem + off_search);
+    a.cur_xyz = call.at<double>(o_cur), a.cur_k = call.at<int>(o_curk), a.out_cls = call.at<short>(o_cls);
+    a.out_cost0 = call.at<long long>(o_c0), a.out_cost1 = call.at<long long>(o_c1);
+    a.out_e0 = call.at<long long>(o_e0), a.out_e1 = call.at<long long>(o_e1), a.out_search = call.at<int>(o_search);
     a.weight = clash_weight, a.max_sweeps = max_sweeps, a.tile = tile, a.limit = TH_PACK_MAX_STRUCT_RESIDUES;
     hipLaunchKernelGGL(k_pack_search, dim3((unsigned)ns), dim3(kSearch), lds_bytes, st, a, lad);
     HIP_TRY(hipGetLastError());
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[3], st));
+    HIP_TRY(call.mark(3));
     if (nr) {
         HIP_TRY(hipMemcpyAsync(out_cls, a.out_cls, nr * sizeof(int16_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(out_cost_initial, a.out_cost0, nr * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -562,12 +524,5 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     HIP_TRY(hipMemcpyAsync(out_energy_initial, a.out_e0, ns * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_energy_final, a.out_e1, ns * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_search, a.out_search, ns * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms)
-        for (int q = 0; q < 3; ++q) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, call.ev[q], call.ev[q + 1]));
-            kernel_ms[q] = ms;
-        }
-    return TH_OK;
+    return call.finish(kernel_ms, 3);
 }

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.h"
+#include "oneshot.h"
 
 // every float64 product and sum below is rounded separately, as NumPy's are
 #pragma clang fp contract(off)
@@ -90,23 +91,6 @@ __global__ void __launch_bounds__(kTile) k_residues(const int* __restrict__ dens
     out[g] = cur;
 }
 
-struct PdCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~PdCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t pd_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" double th_packing_threshold(double radius) {
@@ -161,54 +145,33 @@ extern "C" int th_packing_density(int device, const double* xyz, int64_t total, 
         return TH_OK;
     }
 
-    PdCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
     const size_t n = (size_t)total, ng = (size_t)n_groups;
-    const size_t off_density = pd_align(n * 3 * sizeof(double));
-    const size_t off_items = off_density + pd_align(n * sizeof(int));
-    const size_t off_sel = off_items + pd_align(items.size() * sizeof(Item));
-    const size_t off_spans = off_sel + pd_align(ng ? n : 0);
-    const size_t off_res = off_spans + pd_align(ng * sizeof(Span));
-    const size_t bytes = off_res + pd_align(ng * sizeof(double));
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_packing_density: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms_out)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    double* d_xyz = (double*)call.mem;
-    int* d_density = (int*)(call.mem + off_density);
-    Item* d_items = (Item*)(call.mem + off_items);
-    unsigned char* d_sel = call.mem + off_sel;
-    Span* d_spans = (Span*)(call.mem + off_spans);
-    double* d_res = (double*)(call.mem + off_res);
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_xyz = lay.take(n * 3 * sizeof(double)), o_density = lay.take(n * sizeof(int)), o_items = lay.take(items.size() * sizeof(Item));
+    const size_t o_sel = lay.take(ng ? n : 0), o_spans = lay.take(ng * sizeof(Span)), o_res = lay.take(ng * sizeof(double));
+    ThCall call;
+    if (int rc = call.open("th_packing_density", device, lay.bytes, kernel_ms_out ? 2 : 0)) return rc;
+    double *d_xyz = call.at<double>(o_xyz), *d_res = call.at<double>(o_res);
+    int* d_density = call.at<int>(o_density);
+    Item* d_items = call.at<Item>(o_items);
+    unsigned char* d_sel = call.at<unsigned char>(o_sel);
+    Span* d_spans = call.at<Span>(o_spans);
+    hipStream_t st = call.st[0];
     HIP_TRY(hipMemcpyAsync(d_xyz, xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
     if (ng) {
         HIP_TRY(hipMemcpyAsync(d_sel, selected, n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_spans, spans.data(), ng * sizeof(Span), hipMemcpyHostToDevice, st));
     }
-    if (kernel_ms_out) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     hipLaunchKernelGGL(k_contacts, dim3((unsigned)items.size()), dim3(kTile), 0, st, d_xyz, d_items, th_packing_threshold(radius), d_density);
     HIP_TRY(hipGetLastError());
     if (ng) {
         hipLaunchKernelGGL(k_residues, dim3((unsigned)((ng + kTile - 1) / kTile)), dim3(kTile), 0, st, d_density, d_sel, d_spans, (long long)ng, d_res);
         HIP_TRY(hipGetLastError());
     }
-    if (kernel_ms_out) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     if (density_out) HIP_TRY(hipMemcpyAsync(density_out, d_density, n * sizeof(int), hipMemcpyDeviceToHost, st));
     if (ng) HIP_TRY(hipMemcpyAsync(residue_out, d_res, ng * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms_out) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
-        *kernel_ms_out = ms;
-    }
-    return TH_OK;
+    return call.finish(kernel_ms_out);
 }

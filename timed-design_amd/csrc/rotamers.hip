@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "oneshot.h"
 
 // every float64 product and sum below is rounded separately, as NumPy's are
 #pragma clang fp contract(off)
@@ -151,23 +152,6 @@ __global__ void __launch_bounds__(kBlock) k_tag_rotamers(const double* __restric
     if (chi_out && lane < 4) chi_out[4 * (size_t)r + lane] = (labelled && mine) ? chi : nan;
 }
 
-struct RtCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~RtCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t rt_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int th_rotamer_table(int res_type, int* n_chi, int* class_base_out, char names[7][4]) {
@@ -202,51 +186,31 @@ extern "C" int th_tag_rotamers(int device, const double* xyz, const uint32_t* at
             TH_FAIL(TH_EINVAL, "th_tag_rotamers: res_type[%lld] = %d outside -1..%d", (long long)r, (int)res_type[r], kTypes - 1);
     }
 
-    RtCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
     const size_t n = (size_t)total, nr = (size_t)n_res;
-    const size_t off_name = rt_align(n * 3 * sizeof(double));
-    const size_t off_offsets = off_name + rt_align(n * sizeof(uint32_t));
-    const size_t off_type = off_offsets + rt_align((nr + 1) * sizeof(int64_t));
-    const size_t off_cls = off_type + rt_align(nr);
-    const size_t off_chi = off_cls + rt_align(nr * sizeof(int16_t));
-    const size_t bytes = off_chi + rt_align(chi_out ? nr * 4 * sizeof(double) : 0) + 256;      // never a zero-byte allocation
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_tag_rotamers: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    double* d_xyz = (double*)call.mem;
-    uint32_t* d_name = (uint32_t*)(call.mem + off_name);
-    long long* d_offsets = (long long*)(call.mem + off_offsets);
-    signed char* d_type = (signed char*)(call.mem + off_type);
-    short* d_cls = (short*)(call.mem + off_cls);
-    double* d_chi = chi_out ? (double*)(call.mem + off_chi) : nullptr;
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_xyz = lay.take(n * 3 * sizeof(double)), o_name = lay.take(n * sizeof(uint32_t)), o_offsets = lay.take((nr + 1) * sizeof(int64_t));
+    const size_t o_type = lay.take(nr), o_cls = lay.take(nr * sizeof(int16_t)), o_chi = lay.take(chi_out ? nr * 4 * sizeof(double) : 0);
+    ThCall call;
+    if (int rc = call.open("th_tag_rotamers", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
+    double* d_xyz = call.at<double>(o_xyz);
+    uint32_t* d_name = call.at<uint32_t>(o_name);
+    long long* d_offsets = call.at<long long>(o_offsets);
+    signed char* d_type = call.at<signed char>(o_type);
+    short* d_cls = call.at<short>(o_cls);
+    double* d_chi = chi_out ? call.at<double>(o_chi) : nullptr;
+    hipStream_t st = call.st[0];
     if (n) {
         HIP_TRY(hipMemcpyAsync(d_xyz, xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_name, atom_name, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemcpyAsync(d_offsets, res_offsets, (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_type, res_type, nr, hipMemcpyHostToDevice, st));
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     hipLaunchKernelGGL(k_tag_rotamers, dim3((unsigned)((nr + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_xyz, d_name, d_offsets, d_type,
                        (long long)n_res, flags, device_table(), d_cls, d_chi);
     HIP_TRY(hipGetLastError());
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     HIP_TRY(hipMemcpyAsync(cls_out, d_cls, nr * sizeof(int16_t), hipMemcpyDeviceToHost, st));
     if (chi_out) HIP_TRY(hipMemcpyAsync(chi_out, d_chi, nr * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
-        *kernel_ms = ms;
-    }
-    return TH_OK;
+    return call.finish(kernel_ms);
 }

@@ -34,6 +34,8 @@
 #include <vector>
 
 #include "common.h"
+#include "device_math.h"
+#include "oneshot.h"
 #include "sidechain_place.h"
 
 // every float64 product and sum below is rounded separately, as the NumPy restatement's are
@@ -195,11 +197,6 @@ __global__ void __launch_bounds__(kTile) k_sidechain_clashes(const double* __res
     }
 }
 
-__device__ inline long long wave_sum(long long v) {
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-
 // one wavefront per structure: clashes[r] = both counts of the residue; pairs = side chain against backbone once, side chain
 // against side chain seen from both ends and halved
 __global__ void __launch_bounds__(kTile) k_clash_totals(const long long* __restrict__ offsets, long long n_struct, const int* __restrict__ res_count,
@@ -218,23 +215,6 @@ __global__ void __launch_bounds__(kTile) k_clash_totals(const long long* __restr
     bb = wave_sum(bb);
     if (lane == 0 && pairs_out) pairs_out[s] = bb + both / 2;
 }
-
-struct ScCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~ScCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t sc_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -286,12 +266,7 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
     if (n_struct == 0 && n_res != 0) TH_FAIL(TH_EINVAL, "th_build_sidechains: n_struct = 0 owns no residue, n_res = %lld", (long long)n_res);
     if (n_struct == 0) return TH_OK;
     if (!struct_offsets) TH_FAIL(TH_EINVAL, "th_build_sidechains: n_struct = %lld needs struct_offsets", (long long)n_struct);
-    if (struct_offsets[0] != 0 || struct_offsets[n_struct] != n_res)
-        TH_FAIL(TH_EINVAL, "th_build_sidechains: struct_offsets run from %lld to %lld, not from 0 to n_res = %lld", (long long)struct_offsets[0],
-                (long long)struct_offsets[n_struct], (long long)n_res);
-    for (int64_t s = 0; s < n_struct; ++s)
-        if (struct_offsets[s + 1] < struct_offsets[s])
-            TH_FAIL(TH_EINVAL, "th_build_sidechains: struct_offsets[%lld] > struct_offsets[%lld]", (long long)s, (long long)s + 1);
+    if (int rc = th_check_offsets("th_build_sidechains", "struct_offsets", "n_res", struct_offsets, n_struct, n_res)) return rc;
     if (n_res > 0 && (!backbone || !res_type || !chi || !out_xyz || !out_n_built))
         TH_FAIL(TH_EINVAL, "th_build_sidechains: n_res = %lld needs backbone, res_type, chi, out_xyz and out_n_built", (long long)n_res);
     if (native && n_res > 0) {
@@ -328,51 +303,31 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
         }
     }
 
-    ScCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
     const int nb = (flags & TH_SC_BACKBONE_O) ? 4 : 3;
     const size_t nr = (size_t)n_res, ns = (size_t)n_struct, nn = native ? (size_t)native_total : 0;
-    size_t bytes = 0;
-    auto take = [&bytes](size_t b) { const size_t at = bytes; bytes += sc_align(b); return at; };
-    const size_t off_bb = take(nr * nb * 3 * sizeof(double)), off_type = take(nr), off_chi = take(nr * 4 * sizeof(double));
-    const size_t off_chain = take(chain_id && want_clashes ? nr * sizeof(int32_t) : 0), off_soff = take((ns + 1) * sizeof(int64_t));
-    const size_t off_nxyz = take(nn * 3 * sizeof(double)), off_nname = take(nn * sizeof(uint32_t));
-    const size_t off_noff = take(native ? (nr + 1) * sizeof(int64_t) : 0), off_ntype = take(native ? nr : 0);
-    const size_t off_xyz = take(nr * kScMaxAtoms * 3 * sizeof(double)), off_built = take(nr * sizeof(int32_t));
-    const size_t off_matched = take(native ? nr * sizeof(int32_t) : 0), off_sq = take(native ? nr * sizeof(double) : 0);
-    const size_t off_items = take(items.size() * sizeof(Item)), off_count = take(want_clashes ? nr * 2 * sizeof(int32_t) : 0);
-    const size_t off_clashes = take(want_clashes ? nr * sizeof(int32_t) : 0), off_pairs = take(want_clashes ? ns * sizeof(int64_t) : 0);
-    bytes += 256;                                                      // never a zero-byte allocation
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_build_sidechains: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    unsigned char* mem = call.mem;
-    double* d_bb = (double*)(mem + off_bb);
-    signed char* d_type = (signed char*)(mem + off_type);
-    double* d_chi = (double*)(mem + off_chi);
-    int* d_chain = chain_id && want_clashes ? (int*)(mem + off_chain) : nullptr;
-    long long* d_soff = (long long*)(mem + off_soff);
-    double* d_nxyz = (double*)(mem + off_nxyz);
-    uint32_t* d_nname = (uint32_t*)(mem + off_nname);
-    long long* d_noff = native ? (long long*)(mem + off_noff) : nullptr;
-    signed char* d_ntype = native ? (signed char*)(mem + off_ntype) : nullptr;
-    double* d_xyz = (double*)(mem + off_xyz);
-    int* d_built = (int*)(mem + off_built);
-    int* d_matched = native ? (int*)(mem + off_matched) : nullptr;
-    double* d_sq = native ? (double*)(mem + off_sq) : nullptr;
-    Item* d_items = (Item*)(mem + off_items);
-    int* d_count = (int*)(mem + off_count);
-    int* d_clashes = (int*)(mem + off_clashes);
-    long long* d_pairs = (long long*)(mem + off_pairs);
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_bb = lay.take(nr * nb * 3 * sizeof(double)), o_type = lay.take(nr), o_chi = lay.take(nr * 4 * sizeof(double));
+    const size_t o_chain = lay.take(chain_id && want_clashes ? nr * sizeof(int32_t) : 0), o_soff = lay.take((ns + 1) * sizeof(int64_t));
+    const size_t o_nxyz = lay.take(nn * 3 * sizeof(double)), o_nname = lay.take(nn * sizeof(uint32_t));
+    const size_t o_noff = lay.take(native ? (nr + 1) * sizeof(int64_t) : 0), o_ntype = lay.take(native ? nr : 0);
+    const size_t o_xyz = lay.take(nr * kScMaxAtoms * 3 * sizeof(double)), o_built = lay.take(nr * sizeof(int32_t));
+    const size_t o_matched = lay.take(native ? nr * sizeof(int32_t) : 0), o_sq = lay.take(native ? nr * sizeof(double) : 0);
+    const size_t o_items = lay.take(items.size() * sizeof(Item)), o_count = lay.take(want_clashes ? nr * 2 * sizeof(int32_t) : 0);
+    const size_t o_clashes = lay.take(want_clashes ? nr * sizeof(int32_t) : 0), o_pairs = lay.take(want_clashes ? ns * sizeof(int64_t) : 0);
+    ThCall call;
+    if (int rc = call.open("th_build_sidechains", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
+    double *d_bb = call.at<double>(o_bb), *d_chi = call.at<double>(o_chi), *d_nxyz = call.at<double>(o_nxyz), *d_xyz = call.at<double>(o_xyz);
+    signed char* d_type = call.at<signed char>(o_type);
+    int* d_chain = chain_id && want_clashes ? call.at<int>(o_chain) : nullptr;
+    long long *d_soff = call.at<long long>(o_soff), *d_pairs = call.at<long long>(o_pairs);
+    uint32_t* d_nname = call.at<uint32_t>(o_nname);
+    long long* d_noff = native ? call.at<long long>(o_noff) : nullptr;
+    signed char* d_ntype = native ? call.at<signed char>(o_ntype) : nullptr;
+    int *d_built = call.at<int>(o_built), *d_count = call.at<int>(o_count), *d_clashes = call.at<int>(o_clashes);
+    int* d_matched = native ? call.at<int>(o_matched) : nullptr;
+    double* d_sq = native ? call.at<double>(o_sq) : nullptr;
+    Item* d_items = call.at<Item>(o_items);
+    hipStream_t st = call.st[0];
     const DevTable& tab = host_table();
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_tab), &tab, sizeof tab, 0, hipMemcpyHostToDevice, st));       // the same bytes every call
     HIP_TRY(hipMemcpyAsync(d_bb, backbone, nr * nb * 3 * sizeof(double), hipMemcpyHostToDevice, st));
@@ -389,7 +344,7 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
         HIP_TRY(hipMemcpyAsync(d_ntype, native_type, nr, hipMemcpyHostToDevice, st));
     }
     if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     hipLaunchKernelGGL(k_build_sidechains, dim3((unsigned)((nr + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_bb, nb, d_type, d_chi,
                        (long long)n_res, d_nxyz, d_nname, d_noff, d_ntype, d_xyz, d_built, d_matched, d_sq);
     HIP_TRY(hipGetLastError());
@@ -401,7 +356,7 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
                            d_count, d_clashes, d_pairs);
         HIP_TRY(hipGetLastError());
     }
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     HIP_TRY(hipMemcpyAsync(out_xyz, d_xyz, nr * kScMaxAtoms * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_n_built, d_built, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (native) {
@@ -410,11 +365,5 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
     }
     if (out_clashes) HIP_TRY(hipMemcpyAsync(out_clashes, d_clashes, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (out_struct_pairs) HIP_TRY(hipMemcpyAsync(out_struct_pairs, d_pairs, ns * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
-        *kernel_ms = ms;
-    }
-    return TH_OK;
+    return call.finish(kernel_ms);
 }

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "horn_fit.h"
+#include "oneshot.h"
 
 namespace {
 
@@ -156,23 +157,6 @@ __global__ void __launch_bounds__(kBlock) k_superpose(const double* __restrict__
     }
 }
 
-struct SpCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~SpCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t sp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int th_superpose(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
@@ -191,53 +175,31 @@ extern "C" int th_superpose(int device, const double* ref_xyz, const double* mob
     if (!offsets || !rmsd_out || !count_out || (total > 0 && (!ref_xyz || !mob_xyz || !dist_out || !kept_out)))
         TH_FAIL(TH_EINVAL, "th_superpose: n_pairs = %lld needs offsets, rmsd_out and count_out, total = %lld needs ref_xyz, mob_xyz, dist_out and kept_out",
                 (long long)n_pairs, (long long)total);
-    if (offsets[0] != 0 || offsets[n_pairs] != total)
-        TH_FAIL(TH_EINVAL, "th_superpose: offsets run from %lld to %lld, not from 0 to total = %lld", (long long)offsets[0], (long long)offsets[n_pairs],
-                (long long)total);
-    for (int64_t p = 0; p < n_pairs; ++p)
-        if (offsets[p + 1] < offsets[p]) TH_FAIL(TH_EINVAL, "th_superpose: offsets[%lld] > offsets[%lld]", (long long)p, (long long)p + 1);
+    if (int rc = th_check_offsets("th_superpose", "offsets", "total", offsets, n_pairs, total)) return rc;
 
-    SpCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
     const size_t n = (size_t)total, np = (size_t)n_pairs;
-    const size_t off_mob = sp_align(n * 3 * sizeof(double));
-    const size_t off_offsets = off_mob + sp_align(n * 3 * sizeof(double));
-    const size_t off_dist = off_offsets + sp_align((np + 1) * sizeof(int64_t));
-    const size_t off_kept = off_dist + sp_align(n * sizeof(double));
-    const size_t off_rmsd = off_kept + sp_align(n);
-    const size_t off_count = off_rmsd + sp_align(np * 3 * sizeof(double));
-    const size_t off_tr = off_count + sp_align(np * 7 * sizeof(int32_t));
-    const size_t bytes = off_tr + sp_align(transform_out ? np * 12 * sizeof(double) : 0) + 256;      // never a zero-byte allocation
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_superpose: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    double* d_ref = (double*)call.mem;
-    double* d_mob = (double*)(call.mem + off_mob);
-    long long* d_offsets = (long long*)(call.mem + off_offsets);
-    double* d_dist = (double*)(call.mem + off_dist);
-    unsigned char* d_kept = call.mem + off_kept;
-    double* d_rmsd = (double*)(call.mem + off_rmsd);
-    int* d_count = (int*)(call.mem + off_count);
-    double* d_tr = transform_out ? (double*)(call.mem + off_tr) : nullptr;
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_ref = lay.take(n * 3 * sizeof(double)), o_mob = lay.take(n * 3 * sizeof(double)), o_offsets = lay.take((np + 1) * sizeof(int64_t));
+    const size_t o_dist = lay.take(n * sizeof(double)), o_kept = lay.take(n), o_rmsd = lay.take(np * 3 * sizeof(double));
+    const size_t o_count = lay.take(np * 7 * sizeof(int32_t)), o_tr = lay.take(transform_out ? np * 12 * sizeof(double) : 0);
+    ThCall call;
+    if (int rc = call.open("th_superpose", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
+    double *d_ref = call.at<double>(o_ref), *d_mob = call.at<double>(o_mob), *d_dist = call.at<double>(o_dist), *d_rmsd = call.at<double>(o_rmsd);
+    double* d_tr = transform_out ? call.at<double>(o_tr) : nullptr;
+    long long* d_offsets = call.at<long long>(o_offsets);
+    unsigned char* d_kept = call.at<unsigned char>(o_kept);
+    int* d_count = call.at<int>(o_count);
+    hipStream_t st = call.st[0];
     if (n) {
         HIP_TRY(hipMemcpyAsync(d_ref, ref_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_mob, mob_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     hipLaunchKernelGGL(k_superpose, dim3((unsigned)((np + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_ref, d_mob, d_offsets,
                        (long long)n_pairs, cycles, cutoff, d_dist, d_kept, d_rmsd, d_count, d_tr);
     HIP_TRY(hipGetLastError());
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     if (n) {
         HIP_TRY(hipMemcpyAsync(dist_out, d_dist, n * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(kept_out, d_kept, n, hipMemcpyDeviceToHost, st));
@@ -245,11 +207,5 @@ extern "C" int th_superpose(int device, const double* ref_xyz, const double* mob
     HIP_TRY(hipMemcpyAsync(rmsd_out, d_rmsd, np * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(count_out, d_count, np * 7 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (transform_out) HIP_TRY(hipMemcpyAsync(transform_out, d_tr, np * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
-        *kernel_ms = ms;
-    }
-    return TH_OK;
+    return call.finish(kernel_ms);
 }

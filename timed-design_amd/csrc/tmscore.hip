@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "horn_fit.h"
+#include "oneshot.h"
 
 namespace {
 
@@ -39,11 +40,6 @@ struct TmPair {                                   // one per pair, and one more 
     long long L;                                  // normalisation length
     double d0;
 };
-
-__device__ inline long long wave_sum_ll(long long v) {
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
 
 // d of compacted position c under moved = R (mob - cm) + cr
 __device__ inline double tm_dist(const double* __restrict__ ref, const double* __restrict__ mob, int c, const double (&cm)[3],
@@ -234,7 +230,7 @@ __global__ void __launch_bounds__(kBlock) k_tm_best(const double* __restrict__ c
             at = k;
         }
     }
-    fits_all = wave_sum_ll(fits_all);
+    fits_all = wave_sum(fits_all);
     const double nan = __builtin_nan("");
     double cm[3] = {0.0, 0.0, 0.0}, cr[3] = {0.0, 0.0, 0.0};
     double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
@@ -272,23 +268,6 @@ __global__ void __launch_bounds__(kBlock) k_tm_best(const double* __restrict__ c
     }
 }
 
-struct TmCall {
-    int device = -1;
-    hipStream_t st = nullptr;
-    unsigned char* mem = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~TmCall() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (mem) (void)hipFree(mem);
-    }
-};
-
-size_t tm_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 long long tm_seed_count(long long m) {
     long long seeds = 0;
     for (long long W = m; W >= 1; W /= 2) {
@@ -321,11 +300,8 @@ extern "C" int th_tmscore(int device, const double* ref_xyz, const double* mob_x
     if (!offsets || !tm_out || !count_out || (total > 0 && (!ref_xyz || !mob_xyz)))
         TH_FAIL(TH_EINVAL, "th_tmscore: n_pairs = %lld needs offsets, tm_out and count_out, total = %lld needs ref_xyz and mob_xyz", (long long)n_pairs,
                 (long long)total);
-    if (offsets[0] != 0 || offsets[n_pairs] != total)
-        TH_FAIL(TH_EINVAL, "th_tmscore: offsets run from %lld to %lld, not from 0 to total = %lld", (long long)offsets[0], (long long)offsets[n_pairs],
-                (long long)total);
+    if (int rc = th_check_offsets("th_tmscore", "offsets", "total", offsets, n_pairs, total)) return rc;
     for (int64_t p = 0; p < n_pairs; ++p) {
-        if (offsets[p + 1] < offsets[p]) TH_FAIL(TH_EINVAL, "th_tmscore: offsets[%lld] > offsets[%lld]", (long long)p, (long long)p + 1);
         const int64_t n = offsets[p + 1] - offsets[p];
         if (n > TH_TM_MAX_POSITIONS)
             TH_FAIL(TH_EINVAL, "th_tmscore: pair %lld has %lld positions (limit TH_TM_MAX_POSITIONS = %d)", (long long)p, (long long)n, TH_TM_MAX_POSITIONS);
@@ -367,47 +343,27 @@ extern "C" int th_tmscore(int device, const double* ref_xyz, const double* mob_x
         TH_FAIL(TH_EINVAL, "th_tmscore: %lld seeds in one call (limit 2^31 - 1): submit fewer pairs at once", n_seeds);
     const size_t nc = cref.size() / 3, ns = (size_t)n_seeds;
 
-    TmCall call;
-    HIP_TRY(hipSetDevice(device));
-    call.device = device;
-    const size_t off_mob = tm_align(nc * 3 * sizeof(double));
-    const size_t off_pairs = off_mob + tm_align(nc * 3 * sizeof(double));
-    const size_t off_cidx = off_pairs + tm_align((np + 1) * sizeof(TmPair));
-    const size_t off_score = off_cidx + tm_align(n * sizeof(int));
-    const size_t off_fits = off_score + tm_align(ns * sizeof(double));
-    const size_t off_tm = off_fits + tm_align(ns * sizeof(int));
-    const size_t off_count = off_tm + tm_align(np * 2 * sizeof(double));
-    const size_t off_dist = off_count + tm_align(np * 4 * sizeof(int64_t));
-    const size_t off_tr = off_dist + tm_align(dist_out ? n * sizeof(double) : 0);
-    const size_t bytes = off_tr + tm_align(transform_out ? np * 12 * sizeof(double) : 0) + 256;       // never a zero-byte allocation
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("th_tmscore: hipMalloc of %zu bytes: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&call.st, hipStreamNonBlocking));
-    if (kernel_ms)
-        for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
-    double* d_ref = (double*)call.mem;
-    double* d_mob = (double*)(call.mem + off_mob);
-    TmPair* d_pairs = (TmPair*)(call.mem + off_pairs);
-    int* d_cidx = (int*)(call.mem + off_cidx);
-    double* d_score = (double*)(call.mem + off_score);
-    int* d_fits = (int*)(call.mem + off_fits);
-    double* d_tm = (double*)(call.mem + off_tm);
-    long long* d_count = (long long*)(call.mem + off_count);
-    double* d_dist = dist_out && n ? (double*)(call.mem + off_dist) : nullptr;
-    double* d_tr = transform_out ? (double*)(call.mem + off_tr) : nullptr;
-    hipStream_t st = call.st;
+    ThLayout lay;
+    const size_t o_ref = lay.take(nc * 3 * sizeof(double)), o_mob = lay.take(nc * 3 * sizeof(double)), o_pairs = lay.take((np + 1) * sizeof(TmPair));
+    const size_t o_cidx = lay.take(n * sizeof(int)), o_score = lay.take(ns * sizeof(double)), o_fits = lay.take(ns * sizeof(int));
+    const size_t o_tm = lay.take(np * 2 * sizeof(double)), o_count = lay.take(np * 4 * sizeof(int64_t));
+    const size_t o_dist = lay.take(dist_out ? n * sizeof(double) : 0), o_tr = lay.take(transform_out ? np * 12 * sizeof(double) : 0);
+    ThCall call;
+    if (int rc = call.open("th_tmscore", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
+    double *d_ref = call.at<double>(o_ref), *d_mob = call.at<double>(o_mob), *d_score = call.at<double>(o_score), *d_tm = call.at<double>(o_tm);
+    double* d_dist = dist_out && n ? call.at<double>(o_dist) : nullptr;
+    double* d_tr = transform_out ? call.at<double>(o_tr) : nullptr;
+    TmPair* d_pairs = call.at<TmPair>(o_pairs);
+    int *d_cidx = call.at<int>(o_cidx), *d_fits = call.at<int>(o_fits);
+    long long* d_count = call.at<long long>(o_count);
+    hipStream_t st = call.st[0];
     if (nc) {
         HIP_TRY(hipMemcpyAsync(d_ref, cref.data(), nc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_mob, cmob.data(), nc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     }
     if (n) HIP_TRY(hipMemcpyAsync(d_cidx, cidx.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), (np + 1) * sizeof(TmPair), hipMemcpyHostToDevice, st));
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
+    HIP_TRY(call.mark(0));
     if (ns) {
         const dim3 grid((unsigned)((ns + kPerBlock - 1) / kPerBlock));
         bool staged = false;
@@ -427,16 +383,10 @@ extern "C" int th_tmscore(int device, const double* ref_xyz, const double* mob_x
     hipLaunchKernelGGL(k_tm_best, dim3((unsigned)((np + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_ref, d_mob, d_pairs, d_cidx,
                        (long long)n_pairs, rounds, d_score, d_fits, d_tm, d_count, d_dist, d_tr);
     HIP_TRY(hipGetLastError());
-    if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[1], st));
+    HIP_TRY(call.mark(1));
     HIP_TRY(hipMemcpyAsync(tm_out, d_tm, np * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(count_out, d_count, np * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (d_dist) HIP_TRY(hipMemcpyAsync(dist_out, d_dist, n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (transform_out) HIP_TRY(hipMemcpyAsync(transform_out, d_tr, np * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, call.ev[0], call.ev[1]));
-        *kernel_ms = ms;
-    }
-    return TH_OK;
+    return call.finish(kernel_ms);
 }

@@ -21,6 +21,7 @@
 // bytes depend on its own atom range and its own frames_rt row only, not on its place in the batch.  A 21 A cube holds 150-250
 // encodable atoms; the list holds 2048.
 #include "common.h"
+#include "oneshot.h"
 
 #include <cmath>
 #include <limits.h>
@@ -210,8 +211,6 @@ struct VbCall {
     }
 };
 
-size_t vb_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Everything both entry points do; `who` is the entry point's name for th_last_error.  frame_structure may be NULL from th_voxelise
 // alone: every frame then belongs to structure 0, and the device array is zeroed in place of an upload.
 int voxelise_call(const char* who, int device, const float* atoms_xyz, const int32_t* atom_channel, const float* atom_sigma,
@@ -228,14 +227,8 @@ int voxelise_call(const char* who, int device, const float* atoms_xyz, const int
     if (gaussian && n_atoms && !atom_sigma) TH_FAIL(TH_EINVAL, "%s: Gaussian frames need per-atom sigmas", who);
     if ((n_atoms || n_structures) && !atom_offsets) TH_FAIL(TH_EINVAL, "%s: atom_offsets is NULL (n_structures + 1 entries)", who);
     if (n_frames && (!frames_rt || !out)) TH_FAIL(TH_EINVAL, "%s: %lld frames need frames_rt and out", who, (long long)n_frames);
-    if (atom_offsets) {
-        if (atom_offsets[0] != 0 || atom_offsets[n_structures] != n_atoms)
-            TH_FAIL(TH_EINVAL, "%s: atom_offsets run from %lld to %lld, not from 0 to n_atoms = %lld", who, (long long)atom_offsets[0],
-                    (long long)atom_offsets[n_structures], (long long)n_atoms);
-        for (int64_t s = 0; s < n_structures; ++s)
-            if (atom_offsets[s + 1] < atom_offsets[s])
-                TH_FAIL(TH_EINVAL, "%s: atom_offsets[%lld] > atom_offsets[%lld]", who, (long long)s, (long long)s + 1);
-    }
+    if (atom_offsets)
+        if (int rc = th_check_offsets(who, "atom_offsets", "n_atoms", atom_offsets, n_structures, n_atoms)) return rc;
     if (frame_structure)
         for (int64_t r = 0; r < n_frames; ++r)
             if (frame_structure[r] < 0 || frame_structure[r] >= n_structures)
@@ -257,29 +250,18 @@ int voxelise_call(const char* who, int device, const float* atoms_xyz, const int
     const size_t na = (size_t)n_atoms, ns = (size_t)n_structures, nf = (size_t)n_frames;
     const size_t V3 = (size_t)voxels_per_side * voxels_per_side * voxels_per_side;
     const size_t out_bytes = nf * V3 * n_channels * (gaussian ? sizeof(float) : 1);
-    const size_t off_chn = vb_align(na * 12);
-    const size_t off_sig = off_chn + vb_align(na * 4);
-    const size_t off_wgt = off_sig + vb_align(na * 4);
-    const size_t off_offsets = off_wgt + vb_align(na * 4);
-    const size_t off_fs = off_offsets + vb_align((ns + 1) * sizeof(int64_t));
-    const size_t off_frt = off_fs + vb_align(nf * 4);
-    const size_t off_flag = off_frt + vb_align(nf * 48);
-    const size_t off_out = off_flag + 256;
-    const size_t bytes = off_out + (out_on_device ? 0 : vb_align(out_bytes));
-    hipError_t e = th_malloc_retry(&call.mem, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        call.mem = nullptr;
-        th_set_error("%s: hipMalloc of %zu bytes: %s", who, bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? TH_ENOMEM : TH_EHIP;
-    }
+    ThLayout lay;
+    const size_t off_xyz = lay.take(na * 12), off_chn = lay.take(na * 4), off_sig = lay.take(na * 4), off_wgt = lay.take(na * 4);
+    const size_t off_offsets = lay.take((ns + 1) * sizeof(int64_t)), off_fs = lay.take(nf * 4), off_frt = lay.take(nf * 48), off_flag = lay.take(4);
+    const size_t off_out = lay.take(out_on_device ? 0 : out_bytes);
+    if (int rc = th_alloc_or_fail(who, &call.mem, lay.bytes)) return rc;
     HIP_TRY(borrow_stream(device, &call.st));
     if (kernel_ms)
         for (hipEvent_t& ev : call.ev) HIP_TRY(hipEventCreate(&ev));
     hipStream_t st = call.st;
     unsigned char* m = call.mem;
     if (na) {
-        HIP_TRY(hipMemcpyAsync(m, atoms_xyz, na * 12, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m + off_xyz, atoms_xyz, na * 12, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(m + off_chn, atom_channel, na * 4, hipMemcpyHostToDevice, st));
         if (atom_sigma) HIP_TRY(hipMemcpyAsync(m + off_sig, atom_sigma, na * 4, hipMemcpyHostToDevice, st));
         if (atom_weight) HIP_TRY(hipMemcpyAsync(m + off_wgt, atom_weight, na * 4, hipMemcpyHostToDevice, st));
@@ -290,7 +272,7 @@ int voxelise_call(const char* who, int device, const float* atoms_xyz, const int
     HIP_TRY(hipMemcpyAsync(m + off_frt, frames_rt, nf * 48, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(m + off_flag, 0, 4, st));
     void* d_out = out_on_device ? out : (void*)(m + off_out);
-    VoxBatchArgs a{(const float*)m, (const int*)(m + off_chn), (const float*)(m + off_sig), atom_weight ? (const float*)(m + off_wgt) : nullptr,
+    VoxBatchArgs a{(const float*)(m + off_xyz), (const int*)(m + off_chn), (const float*)(m + off_sig), atom_weight ? (const float*)(m + off_wgt) : nullptr,
                    (const long long*)(m + off_offsets), (const int*)(m + off_fs), (const float*)(m + off_frt), voxels_per_side,
                    frame_edge_length / (float)voxels_per_side, n_channels, gaussian, d_out, (int*)(m + off_flag)};
     if (kernel_ms) HIP_TRY(hipEventRecord(call.ev[0], st));
