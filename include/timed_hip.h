@@ -814,6 +814,70 @@ int th_cealign(int device, const double* ref_xyz, int64_t ref_total, const int64
                const int64_t* mob_offsets, int64_t n_pairs, double d0, double d1, int gap_max, int32_t* align_out, double* score_out,
                int64_t* count_out, double* transform_out, double* kernel_ms);
 
+/* ---- *** PARITY UNPINNED AGAINST DSSP *** secondary structure of protein backbones: analyse_properties.py --secondary_structure and
+ * analyse_models.py --secondary_structure — where the helices and strands are, by the DSSP rule (Kabsch & Sander 1983): backbone
+ * hydrogen bonds by an electrostatic energy, then turns, helices, bridges, ladders and bends as patterns of those bonds.  What the
+ * reference leaves to PyMOL pictures.  Here for a BATCH of structures in one call: an all-pairs float64 pass over the residues of
+ * each structure, then integer pattern matching.
+ *
+ *     *** PARITY UNPINNED AGAINST DSSP ***  (mkdssp, PyMOL's dss, STRIDE.)  None of them is available where this project is built.
+ *     The rule below is this project's reading of the PUBLISHED definition and not their code.  Those programs' tie rules, bulges,
+ *     G / I precedence and bond caps differ in detail: assignments can differ at helix ends and sheet edges, and no test can pin
+ *     this rule against mkdssp.
+ *
+ * All arrays are host memory.
+ *   backbone           double[total][4][3]: N, CA, C, O of every residue, structure after structure, in the caller's order (any value;
+ *                      NaN for an atom the residue lacks);
+ *   chain              int32[total]: a chain id; a change of id is a chain break;
+ *   no_h               uint8[total]: non-zero for a residue whose N carries no hydrogen (proline);
+ *   total              number of residues, 0 <= total <= 2^31 - 1;
+ *   offsets            int64[n_structures + 1]: structure s owns residues offsets[s] .. offsets[s + 1]; offsets[0] = 0, non-decreasing,
+ *                      offsets[n_structures] = total.  A structure may be empty.  There is no length limit;
+ *   n_structures       0 <= n_structures <= 2^31 - 1;
+ *   class_out          uint8[total]: 0 '-', 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S;
+ *   residue_out        int32[total][6]: the two lowest bridge partners as structure-local indices (or -1); flags (bits 0-2: a 3-, 4-,
+ *                      5-turn starts here, 3: bend, 4: has a parallel bridge, 5: has an antiparallel bridge, 6: conn(i), 7: valid);
+ *                      bonds accepted (as C=O); bonds donated (as N-H); the number of bridge partners;
+ *   structure_out      int64[n_structures][10]: n_valid, n_hbonds, then the number of residues of each of the eight classes;
+ *   hbond_bits_out     NULL, or uint64[sum over s of L_s * ceil(L_s / 64)]: the hydrogen bonds.  Structure s has L_s rows of
+ *                      ceil(L_s / 64) words, row = acceptor, bit (d & 63) of word (d >> 6) = donor d, both structure-local, and starts
+ *                      at word sum over t < s of L_t * ceil(L_t / 64);
+ *   kernel_ms          NULL, or double[3]: the device time (events) of the hydrogen-bond pass (with the per-residue preparation), of
+ *                      the assignment and of the totals, in milliseconds.
+ * The rule, for one structure of residues 0 .. L-1, all arithmetic float64 and no fused multiply-add:
+ *   - VALID(i): all 12 coordinates are finite.  An invalid residue makes no bond, is a break on both sides and gets class '-';
+ *   - CONN(i), the link i -> i+1: both residues are valid, have the same chain id, and the squared C(i)-N(i+1) distance is <= 6.25;
+ *   - H(i) = N(i) + v / |v| with v = C(i-1) - O(i-1), each component divided by |v| = sqrt((vx*vx + vy*vy) + vz*vz).  It exists only
+ *     where conn(i-1) holds, no_h is false and its three components are finite (a C on its own O has none).  A residue without H
+ *     donates nothing;
+ *   - ENERGY of acceptor a (C=O) and donor d (N-H), taken only when a is valid, d has H, d != a, d != a + 1 and the squared CA-CA
+ *     distance is < 81.0.  Every distance is sqrt((dx*dx + dy*dy) + dz*dz).  q = ((1/rON + 1/rCH) - 1/rOH) - 1/rCN;
+ *     e = (int)floor((27.888 * q) * 1000 + 0.5), in milli-kcal/mol; if any of the four distances is < 0.5 then e = -9900; e is never
+ *     below -9900.  HB(a, d) <=> e < -500.  ALL bonds count: there is no "two best per residue" cap, which is mkdssp's book-keeping
+ *     and not the definition;
+ *   - TURN_n(i), n = 3, 4, 5: hb(i, i+n) and conn(i) .. conn(i+n-1);
+ *   - HELICES: turn_4(i-1) and turn_4(i) => H at i .. i+3; turn_3(i-1) and turn_3(i) => G at i .. i+2; turn_5(i-1) and turn_5(i) => I
+ *     at i .. i+4; turn_n(i) => T at i+1 .. i+n-1;
+ *   - BRIDGES, for |i - j| >= 3 with conn(i-1), conn(i), conn(j-1), conn(j); the chains may differ.
+ *     parallel <=> [hb(i-1, j) and hb(j, i+1)] or [hb(j-1, i) and hb(i, j+1)];
+ *     antiparallel <=> [hb(i, j) and hb(j, i)] or [hb(i-1, j+1) and hb(j-1, i+1)];
+ *   - E or B: residue i is E when it has a parallel bridge to some j and (i+1, j+1) or (i-1, j-1) is also a parallel bridge, or an
+ *     antiparallel bridge to some j and (i+1, j-1) or (i-1, j+1) is also an antiparallel bridge.  A bridged residue that is not E
+ *     is B.  Beta-bulges are NOT bridged over (out of scope), and sheets are not labelled;
+ *   - S: conn(i-2) .. conn(i+1) hold and dot(a, b) / (|a| * |b|) < 0.3420201433256688 with a = CA(i) - CA(i-2), b = CA(i+2) - CA(i):
+ *     a bend of more than 70 degrees.  No trigonometry anywhere;
+ *   - PRIORITY per residue: H > E > B > G > I > T > S > '-'.  Three-state reduction (the caller's): H, G, I -> helix; E, B -> strand;
+ *     the rest -> coil.
+ * All outputs are integers decided by float64 comparisons: a structure's outputs depend on its own residues alone — not on its place
+ * in the batch or on its neighbours — and two calls give the same bytes.  No atomics.  Device memory: 151 bytes per residue, 8 per
+ * 256 residues of every structure, 96 per structure and the bitmap, L * ceil(L / 64) * 8 bytes per structure; a device that cannot
+ * hold them is TH_ENOMEM.  TH_EINVAL, before anything is launched or written: a negative or too large size, a NULL that is required
+ * (offsets, structure_out; with total > 0 also backbone, chain, no_h, class_out and residue_out), offsets that decrease, do not start
+ * at 0 or do not end at total.  n_structures = 0 (with total = 0) is success without a launch. */
+int th_secondary_structure(int device, const double* backbone, const int32_t* chain, const uint8_t* no_h, int64_t total,
+                           const int64_t* offsets, int64_t n_structures, uint8_t* class_out, int32_t* residue_out, int64_t* structure_out,
+                           uint64_t* hbond_bits_out, double* kernel_ms);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

@@ -61,6 +61,18 @@ mismatch is then no error, and what either side has outside the alignment counts
 PARITY UNPINNED AGAINST PYMOL: the rule of --cealign is this project's reading of the published CE algorithm with cealign's documented
 defaults (window 8, d0 3.0, d1 4.0, gap_max 30, the best 20 paths re-scored by RMSD), written out in include/timed_hip.h and
 timed_hip/cealign.py.
+
+--secondary_structure additionally writes ``model_secstruct.csv``, one row per pair — label, reference, model, n_paired, q8 and q3 (the
+share of the paired positions whose DSSP class, and whose three-state reduction helix / strand / coil, agree), the helix and strand
+fractions and the number of backbone hydrogen bonds of either structure (over ALL of its residues that have a CA atom, paired or
+not), error — and ``residue_secstruct.csv`` — label, chain, number and residue of the reference's residue of every paired position, its
+class and the model's, both three-state letters, and the chain and number of the model's residue.  Did the model keep the native's
+helices and strands?  Each distinct file is assigned once, from the structures already parsed for the superposition, so a native
+shared by a thousand models is one structure in the batch; the pairing is that of model_scores.csv (--pair_by, or --pair_by_cealign).
+
+PARITY UNPINNED AGAINST DSSP (mkdssp, PyMOL's dss, STRIDE): none of them is available to pin this against.  The rule is this project's
+reading of the published definition (Kabsch & Sander 1983), written out in include/timed_hip.h and timed_hip/secstruct.py: every
+hydrogen bond below -0.5 kcal/mol counts, beta-bulges are not bridged over, priority H > E > B > G > I > T > S.
 """
 import argparse
 import csv
@@ -71,6 +83,7 @@ import numpy as np
 
 from timed_hip import cealign as cealign_module
 from timed_hip import lddt as lddt_module
+from timed_hip import secstruct as secstruct_module
 from timed_hip import superpose
 from timed_hip import tmscore as tmscore_module
 from timed_hip.pdbio import find_structures
@@ -85,6 +98,10 @@ RESIDUE_LDDT_COLUMNS = ["label", "chain", "number", "residue", "n_included", "ld
 CEALIGN_COLUMNS = ["label", "reference", "model", "n_ref", "n_model", "n_starts", "n_afps", "n_aligned", "rmsd", "path_score", "error"]
 RESIDUE_CEALIGN_COLUMNS = ["label", "chain", "number", "residue", "model_chain", "model_number", "model_residue", "distance"]
 TMSCORE_COLUMNS = ["label", "reference", "model", "n_valid", "norm_length", "d0", "tm_score", "tm_global_fit", "n_seeds", "n_fits", "error"]
+SECSTRUCT_COLUMNS = ["label", "reference", "model", "n_paired", "q8", "q3", "reference_helix_fraction", "reference_strand_fraction",
+                     "model_helix_fraction", "model_strand_fraction", "reference_n_hbonds", "model_n_hbonds", "error"]
+RESIDUE_SECSTRUCT_COLUMNS = ["label", "chain", "number", "residue", "reference_class", "model_class", "reference_three_state", "model_three_state",
+                             "model_chain", "model_number"]
 
 
 def read_pairs(path):
@@ -115,6 +132,40 @@ def write_lddt(out, todo, scores):
                         + [_fmt(known.mean() if len(known) else float("nan")), res.error or ""])
             for r, n, score, b in zip(res.residues, res.n_i.tolist(), res.lddt_i, res.model_bfactor):
                 wr.writerow([label, r.chain, r.number, r.name, n, _fmt(score), _fmt(b)])
+
+
+def write_secstruct(out, todo, prepared, device, stats):
+    """model_secstruct.csv and residue_secstruct.csv: every distinct structure of ``prepared`` is assigned once, in one batch"""
+    distinct = {}
+    for item in prepared.pairs:
+        if not isinstance(item, str):
+            for side in item[:2]:
+                distinct.setdefault(id(side), side)
+    assigned = secstruct_module.secondary_structure_layouts([secstruct_module.layout_of_residues(side.residues) for side in distinct.values()],
+                                                            device=device, stats=stats)
+    assigned = dict(zip(distinct, assigned))
+    nan = float("nan")
+    with open(out / "model_secstruct.csv", "w", newline="") as fs, open(out / "residue_secstruct.csv", "w", newline="") as fr:
+        ws, wr = csv.writer(fs), csv.writer(fr)
+        ws.writerow(SECSTRUCT_COLUMNS)
+        wr.writerow(RESIDUE_SECSTRUCT_COLUMNS)
+        for (label, ref, model), item in zip(todo, prepared.pairs):
+            if isinstance(item, str):
+                ws.writerow([label, str(ref), str(model), 0] + [_fmt(nan)] * 6 + [0, 0, item])
+                continue
+            ours, theirs = np.asarray(item[2], dtype=np.int64), np.asarray(item[3], dtype=np.int64)
+            a, b = assigned[id(item[0])], assigned[id(item[1])]
+            mine, other = a.cls[ours], b.cls[theirs]
+            n = len(ours)
+            q8 = float((mine == other).sum()) / n if n else nan
+            q3 = float((secstruct_module.three_state(mine) == secstruct_module.three_state(other)).sum()) / n if n else nan
+            ws.writerow([label, str(ref), str(model), n, _fmt(q8), _fmt(q3)] + [_fmt(f) for f in a.fractions[:2] + b.fractions[:2]]
+                        + [a.n_hbonds, b.n_hbonds, ""])
+            letters, three = (secstruct_module.as_string(mine), secstruct_module.as_string(other)), (
+                secstruct_module.as_string(mine, three=True), secstruct_module.as_string(other, three=True))
+            for k, (i, j) in enumerate(zip(ours.tolist(), theirs.tolist())):
+                r, m = a.residues[i], b.residues[j]
+                wr.writerow([label, r.chain, r.number, r.name, letters[0][k], letters[1][k], three[0][k], three[1][k], m.chain, m.number])
 
 
 def tm_sum(dist, d0, norm_length):
@@ -199,6 +250,8 @@ def main(args):
         write_cealign(out, todo, aligned)
     if args.lddt:
         write_lddt(out, todo, lddt_module.lddt(prepared, radius=args.lddt_radius, device=args.device, stats=stats))
+    if args.secondary_structure:
+        write_secstruct(out, todo, prepared, args.device, stats)
     if args.tmscore:
         write_tmscore(out, todo, tmscore_module.tmscore(prepared, rounds=args.tm_rounds, device=args.device, stats=stats),
                       superpose.superpose(prepared, cycles=0, device=args.device, stats=stats))
@@ -251,6 +304,11 @@ CLI_FLAGS = (
     ("--pair_by_cealign", dict(action="store_true",
                                help="pair the positions of model_scores.csv, --lddt and --tmscore by the alignment of --cealign in place of "
                                     "--pair_by: a length mismatch is then no error")),
+    ("--secondary_structure", dict(action="store_true",
+                                   help="also write model_secstruct.csv and residue_secstruct.csv: the DSSP class of every residue of both "
+                                        "structures, the share of paired positions whose class (q8) and whose helix / strand / coil state (q3) "
+                                        "agree, and the helix and strand fractions and hydrogen bonds of either side.  PARITY UNPINNED AGAINST "
+                                        "DSSP")),
 )
 
 

@@ -14,6 +14,22 @@ residues are reported is the structure rule of timed_hip/structure.py (first mod
 neighbour, the non-hetero residues of the first chain reported; --all_chains reports every chain).  B-factor: of the residue's
 first atom, as the reference reads the pLDDT of an AlphaFold2 model.
 
+--secondary_structure additionally writes ``residue_secondary_structure.csv`` — structure, chain, residue number, residue name, the
+class letter (H alpha-helix, G 3-10 helix, I pi-helix, E strand, B isolated bridge, T turn, S bend, - none), the three-state letter (H
+helix: H G I; E strand: E B; C coil: the rest), the two lowest bridge partners as chain:number, the hydrogen bonds the residue accepts
+(C=O) and donates (N-H) — and ``structure_secondary_structure.csv`` — structure, residues, n_hbonds, the number of residues of each
+of the eight classes and the helix / strand / coil fractions; with --path_to_pred_matrix + --path_to_datasetmap also the mean
+prediction entropy over the helix, the strand and the coil residues (NaN where a state is empty or no row pairs).  Rows pair with
+residues by chain and residue number: with --support_old_datasetmap every map row names them, and the rows used are those whose pdb
+code, or pdb code + chain, equals the file's stem; the two-column map names neither, so the rows of the key that equals the stem pair
+by position, and only when there are as many as residues.  The residues are the non-hetero residues of EVERY chain (bridges pair
+chains), whatever --all_chains says about the packing density.  The other two files keep their bytes.
+
+PARITY UNPINNED AGAINST DSSP (mkdssp, PyMOL's dss, STRIDE): none of them is available to pin this against.  The rule is this project's
+reading of the published definition (Kabsch & Sander 1983), written out in include/timed_hip.h and timed_hip/secstruct.py: every
+hydrogen bond below -0.5 kcal/mol counts (no cap per residue), beta-bulges are not bridged over, priority H > E > B > G > I > T > S.
+Assignments can differ from those programs' at helix ends and sheet edges.
+
 Out of scope here: the reference script's CE-align RMSD (PyMOL), which is analyse_models.py --cealign, and its parsing of AlphaFold2
 file names into model / temperature / sample / rank columns — the ``structure`` column is the file's path relative to the
 --path_to_pdb entry it was found under.
@@ -25,12 +41,67 @@ from pathlib import Path
 
 import numpy as np
 
-from timed_hip import batching, structure
+from timed_hip import batching, secstruct, structure
 from timed_hip.pdbio import PDB_SUFFIXES, find_structures, is_pdb_name, stem_of  # noqa: F401  (their home; kept importable from here)
 from timed_hip.textio import float_repr as _fmt
 
 
+SECSTRUCT_RESIDUE_COLUMNS = ["structure", "chain", "residue_number", "residue_name", "class", "three_state", "bridge_partner_1", "bridge_partner_2",
+                             "bonds_accepted", "bonds_donated"]
+SECSTRUCT_COLUMNS = ["structure", "residues", "n_hbonds", "n_none", "n_H", "n_B", "n_E", "n_G", "n_I", "n_T", "n_S", "helix_fraction",
+                     "strand_fraction", "coil_fraction"]
+SECSTRUCT_ENTROPY_COLUMNS = ["entropy_helix_mean", "entropy_strand_mean", "entropy_coil_mean"]
+
+
+def state_entropy(label, res, entropy, map_rows):
+    """The mean prediction entropy over the helix, strand and coil residues of one assigned structure (NaN for an empty state).
+    ``entropy``: {map key: entropy of each of its rows}; ``map_rows``: {map key: its (pdb, chain, number, label) rows} of an
+    old-format map, or None for a two-column map.  See the module docstring for how rows pair with residues."""
+    stem = stem_of(label)
+    values = {}
+    if map_rows is not None:
+        index = {}
+        for k, r in enumerate(res.residues):
+            index.setdefault((r.chain, r.number), k)
+        for key, rows in map_rows.items():
+            if key != stem and str(rows[0][0]) != stem:
+                continue
+            for row, v in zip(rows, entropy[key]):
+                k = index.get((str(row[1]).strip(), str(row[2]).strip()))
+                if k is not None:
+                    values.setdefault(k, float(v))
+    else:
+        e = entropy.get(stem)
+        if e is not None and len(e) == len(res.residues):
+            values = {k: float(v) for k, v in enumerate(e)}
+    states = secstruct.three_state(res.cls).tolist()
+    out = []
+    for state in (1, 2, 0):
+        mine = [values[k] for k, s in enumerate(states) if s == state and k in values]
+        out.append(float(np.mean(mine)) if mine else float("nan"))
+    return out
+
+
+def write_secondary_structure(out, found, assigned, entropy=None, map_rows=None):
+    """residue_secondary_structure.csv and structure_secondary_structure.csv"""
+    with open(out / "residue_secondary_structure.csv", "w", newline="") as fr, open(out / "structure_secondary_structure.csv", "w", newline="") as fs:
+        wr, ws = csv.writer(fr), csv.writer(fs)
+        wr.writerow(SECSTRUCT_RESIDUE_COLUMNS)
+        ws.writerow(SECSTRUCT_COLUMNS + (SECSTRUCT_ENTROPY_COLUMNS if entropy is not None else []))
+        for (label, _), res in zip(found, assigned):
+            names = [f"{r.chain}:{r.number}" for r in res.residues]
+            letters, three = secstruct.as_string(res.cls), secstruct.as_string(res.cls, three=True)
+            for k, r in enumerate(res.residues):
+                first, second = (names[j] if j >= 0 else "" for j in res.partners[k].tolist())
+                wr.writerow([label, r.chain, r.number, r.name, letters[k], three[k], first, second, int(res.accepted[k]), int(res.donated[k])])
+            row = [label, len(res.residues), res.n_hbonds] + [int(c) for c in res.counts] + [_fmt(f) for f in res.fractions]
+            if entropy is not None:
+                row += [_fmt(v) for v in state_entropy(label, res, entropy, map_rows)]
+            ws.writerow(row)
+
+
 def main(args):
+    with_secstruct = getattr(args, "secondary_structure", False)
     found = find_structures(args.path_to_pdb)
     if not found:
         sys.exit(f"no *.pdb / *.pdb1 / *.ent (.gz) file under {args.path_to_pdb}")
@@ -44,13 +115,24 @@ def main(args):
 
     def parse(item):
         model = structure.first_model(item[1])
-        return model, structure.layout(model, args.atom_filter_function, include_hetero=True, all_chains=args.all_chains)
+        return (model, structure.layout(model, args.atom_filter_function, include_hetero=True, all_chains=args.all_chains),
+                secstruct.backbone_layout(model) if with_secstruct else None)
     parsed = batching.parse_each(parse, found, args.workers)
     stats = {}
-    results = structure.packing_density_layouts([l for _, l in parsed], radius=args.radius, device=args.device,
+    results = structure.packing_density_layouts([l for _, l, _ in parsed], radius=args.radius, device=args.device,
                                                 budget_bytes=int(args.batch_mb * (1 << 20)), stats=stats)
     out = Path(args.path_to_output)
     out.mkdir(parents=True, exist_ok=True)
+    if with_secstruct:
+        assigned = secstruct.secondary_structure_layouts([b for _, _, b in parsed], device=args.device, budget_bytes=int(args.batch_mb * (1 << 20)),
+                                                         stats=stats)
+        map_rows = None
+        if entropy is not None and args.support_old_datasetmap:
+            from design_utils.utils import load_datasetmap
+            map_rows = {}
+            for row in load_datasetmap(Path(args.path_to_datasetmap), is_old=True):
+                map_rows.setdefault(str(row[0]) + str(row[1]), []).append(row)
+        write_secondary_structure(out, found, assigned, entropy, map_rows)
     with open(out / "residue_properties.csv", "w", newline="") as fr, open(out / "structure_properties.csv", "w", newline="") as fs:
         wr, ws = csv.writer(fr), csv.writer(fs)
         wr.writerow(["structure", "chain", "residue_number", "residue_name", "packing_density", "bfactor"])
@@ -91,6 +173,12 @@ CLI_FLAGS = (
     ("--path_to_datasetmap", dict(type=str, default=None, help="its dataset map; a structure is matched by its file stem")),
     ("--rotamer_mode", dict(default=False, action="store_true", help="the prediction matrix has 338 columns")),
     ("--support_old_datasetmap", dict(default=False, action="store_true", help="the dataset map is the old 4-column csv")),
+    # absent from the namespace unless given: a namespace built by an older caller has no such attribute either
+    ("--secondary_structure", dict(default=argparse.SUPPRESS, action="store_true",
+                                   help="also write residue_secondary_structure.csv and structure_secondary_structure.csv: the DSSP class "
+                                        "(H G I E B T S -) and three-state letter of every residue of every chain, its bridge partners and "
+                                        "hydrogen bonds, and per structure the counts and the helix / strand / coil fractions (with a prediction "
+                                        "matrix: the mean entropy of each state).  PARITY UNPINNED AGAINST DSSP")),
 )
 
 
