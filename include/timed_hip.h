@@ -878,6 +878,67 @@ int th_secondary_structure(int device, const double* backbone, const int32_t* ch
                            const int64_t* offsets, int64_t n_structures, uint8_t* class_out, int32_t* residue_out, int64_t* structure_out,
                            uint64_t* hbond_bits_out, double* kernel_ms);
 
+/* ---- *** PARITY UNPINNED AGAINST FREESASA / NACCESS / DSSP / BIOPYTHON *** solvent-accessible surface area of structures:
+ * analyse_properties.py --sasa and analyse_models.py --sasa — which atoms and residues are buried and which face the solvent, by the
+ * numerical method of Shrake & Rupley (1973): every atom carries a sphere of its van der Waals radius plus a probe radius with test
+ * points on it, and a point is exposed unless it lies inside the sphere of another atom.  The only burial measure the reference has
+ * is its contact number (th_packing_density).  Here for a BATCH of structures in one call.
+ *
+ *     *** PARITY UNPINNED AGAINST FREESASA / NACCESS / DSSP / BIOPYTHON ***  None of them is available where this project is built
+ *     (verified absent: the Python modules Bio, freesasa and mdtraj).  The rule below is this project's own.  Those programs use
+ *     their own radii, point sets (or Lee-Richards slices) and tie rules: areas differ from theirs by the usual few per cent between
+ *     SASA programs, and no test can pin this rule against them.
+ *
+ * All arrays are host memory.
+ *   xyz                double[total][3]: the atoms, structure after structure, in the caller's order (any value);
+ *   radius             double[total]: the van der Waals radius of each atom (any value);
+ *   total              number of atoms, 0 <= total <= 2^31 - 257;
+ *   offsets            int64[n_structures + 1]: structure s owns atoms offsets[s] .. offsets[s + 1]; offsets[0] = 0, non-decreasing,
+ *                      offsets[n_structures] = total.  A structure may be empty.  There is no length limit;
+ *   n_structures       0 <= n_structures <= 2^31 - 1;
+ *   probe              the probe radius (1.4 for water; 0 gives the van der Waals surface; any value);
+ *   points             double[n_points][3]: the directions u_k, the caller's, normally of unit length (th_sasa_sphere); all finite;
+ *   n_points           1 <= n_points <= 1024;
+ *   exposed_out        int32[total]: the number of exposed points of every atom, -1 for an invalid atom;
+ *   mask_out           NULL, or uint64[total][ceil(n_points / 64)]: bit (k & 63) of word (k >> 6) is set where point k is exposed;
+ *                      padding bits are 0, all words of an invalid atom are 0;
+ *   structure_out      int64[n_structures][3]: valid atoms, valid atoms with no exposed point, the sum of exposed_out over valid atoms;
+ *   kernel_ms_out      NULL, or double[2]: the device time (events) of the occlusion pass and of the totals, in milliseconds.
+ * The rule, for one structure of atoms 0 .. n-1, all arithmetic float64, every product, sum and difference rounded on its own in the
+ * written order (no fused multiply-add):
+ *   - EXPANDED RADIUS: R_i = radius_i + probe;
+ *   - VALID(i): the three coordinates and R_i are finite and R_i > 0.  An invalid atom occludes nothing, its count is -1 and its mask
+ *     words are 0;
+ *   - NEAR(i, j): j != i, the same structure, both valid, and s < t*t, strict, with dx = x_j - x_i, dy = y_j - y_i, dz = z_j - z_i,
+ *     s = (dx*dx + dy*dy) + dz*dz and t = R_i + R_j.  This pre-filter is PART OF THE RULE, not an optimisation assumed harmless: an
+ *     atom that is not near occludes nothing, whatever its sphere does in rounded arithmetic;
+ *   - SPHERE POINT k of atom i: p_k = (x_i + R_i*u_kx, y_i + R_i*u_ky, z_i + R_i*u_kz);
+ *   - OCCLUSION: point k of atom i is buried <=> some j with near(i, j) has (ex*ex + ey*ey) + ez*ez < R_j*R_j, strict, with
+ *     e = p_k - c_j, the centre of j.  A point exactly on a neighbour's sphere is exposed;
+ *   - COUNT: exposed_out[i] = the number of points that are not buried.  MASK: which ones.
+ *   Consequences: coincident atoms of equal radius bury each other's points only as far as the rounding of |u_k| decides (of 96
+ *   golden-spiral points 76 survive for two atoms of R = 3.1 at the origin, 80 for R = 3 at (1, 2, 3), 51 inside a protein's
+ *   coordinates): deterministic and physically meaningless.  A sphere wholly inside another gets 0.  Distances that
+ *   overflow to infinity are not near.  The neighbours are all pairs of the structure: no cell grid and no neighbour list, so no
+ *   capacity either — 300 atoms on one spot are 300 neighbours.
+ * AREAS are the caller's, in float64: area_i = exposed_i * (4 * pi * R_i * R_i / n_points), multiplied left to right (0 for an
+ * invalid atom), and a residue's area is the sequential sum over its atoms in file order (timed_hip/sasa.py).
+ * All device outputs are integers and bit sets decided by float64 comparisons, and an AND over neighbours whose order cannot change a
+ * bit: a structure's outputs depend on its own atoms alone — not on its place in the batch or on its neighbours — and two calls give
+ * the same bytes.  No atomics.  Device memory: 32 bytes per atom in, 4 + 8 * ceil(n_points / 64) bytes per atom out (4 without
+ * mask_out), 2 per atom of work items, 32 per structure and 24 per point; a device that cannot hold them is TH_ENOMEM.  TH_EINVAL,
+ * before anything is launched or written: a negative or too large size, n_points outside 1 .. 1024, a point coordinate that is not
+ * finite, a NULL that is required (points; with n_structures > 0 offsets and structure_out; with total > 0 also xyz, radius and
+ * exposed_out), offsets that decrease, do not start at 0 or do not end at total.  total = 0 is success without a launch. */
+int th_sasa(int device, const double* xyz, const double* radius, int64_t total, const int64_t* offsets, int64_t n_structures,
+            double probe, const double* points, int32_t n_points, int32_t* exposed_out, uint64_t* mask_out, int64_t* structure_out,
+            double* kernel_ms_out);
+/* The golden spiral: n_points directions spread evenly over the unit sphere, computed with the host's libm (host code, no GPU).  For
+ * k = 0 .. n_points - 1: z = 1 - (2k + 1) / n_points, rho = sqrt(1 - z*z), phi = k * (pi * (3 - sqrt(5))), u_k = (rho cos phi,
+ * rho sin phi, z) into points_out[3k ..].  The points are an INPUT of th_sasa so that the kernel and whoever checks it see the same
+ * doubles.  TH_EINVAL: n_points outside 1 .. 1024 or points_out NULL. */
+int th_sasa_sphere(int32_t n_points, double* points_out);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

@@ -73,6 +73,20 @@ shared by a thousand models is one structure in the batch; the pairing is that o
 PARITY UNPINNED AGAINST DSSP (mkdssp, PyMOL's dss, STRIDE): none of them is available to pin this against.  The rule is this project's
 reading of the published definition (Kabsch & Sander 1983), written out in include/timed_hip.h and timed_hip/secstruct.py: every
 hydrogen bond below -0.5 kcal/mol counts, beta-bulges are not bridged over, priority H > E > B > G > I > T > S.
+
+--sasa additionally writes ``model_sasa.csv``, one row per pair — label, reference, model, n_paired, the total and the apolar
+solvent-accessible area of either structure (over ALL of its residues that have a CA atom, paired or not), burial_agreement (the share of
+the paired positions in the same burial class: core, boundary, surface), mean_abs_rsa_difference and rsa_correlation (Pearson; NaN under
+2 positions) of the relative accessibilities of the paired positions, error — and ``residue_sasa.csv`` — label, chain, number and residue
+of the reference's residue of every paired position, the area, the relative accessibility and the burial letter (C, B, S, ?) of both
+sides, and the chain and number of the model's residue.  Did the model bury what the native buries?  Shrake & Rupley (1973) with
+--sasa_points golden-spiral points per atom and a probe of --sasa_probe (th_sasa); the atoms are the non-hydrogen atoms of the residues
+already parsed for the superposition (hetero atoms never occlude here, and chains are not measured alone: analyse_properties.py has
+--sasa_hetero and --sasa_interface).  Each distinct file goes through the kernel once; the pairing is that of model_scores.csv.
+
+PARITY UNPINNED AGAINST FREESASA / NACCESS / DSSP / BIOPYTHON: none of them is available to pin this against.  The rule is this
+project's own, written out in include/timed_hip.h and timed_hip/sasa.py; the maximum areas behind the relative accessibility (after
+Tien et al. 2013) are WRITTEN FROM MEMORY, NOT FETCHED.
 """
 import argparse
 import csv
@@ -83,6 +97,7 @@ import numpy as np
 
 from timed_hip import cealign as cealign_module
 from timed_hip import lddt as lddt_module
+from timed_hip import sasa as sasa_module
 from timed_hip import secstruct as secstruct_module
 from timed_hip import superpose
 from timed_hip import tmscore as tmscore_module
@@ -102,6 +117,10 @@ SECSTRUCT_COLUMNS = ["label", "reference", "model", "n_paired", "q8", "q3", "ref
                      "model_helix_fraction", "model_strand_fraction", "reference_n_hbonds", "model_n_hbonds", "error"]
 RESIDUE_SECSTRUCT_COLUMNS = ["label", "chain", "number", "residue", "reference_class", "model_class", "reference_three_state", "model_three_state",
                              "model_chain", "model_number"]
+SASA_COLUMNS = ["label", "reference", "model", "n_paired", "reference_total_area", "reference_apolar_area", "model_total_area", "model_apolar_area",
+                "burial_agreement", "mean_abs_rsa_difference", "rsa_correlation", "error"]
+RESIDUE_SASA_COLUMNS = ["label", "chain", "number", "residue", "reference_area", "model_area", "reference_rsa", "model_rsa", "reference_burial",
+                        "model_burial", "model_chain", "model_number"]
 
 
 def read_pairs(path):
@@ -168,6 +187,52 @@ def write_secstruct(out, todo, prepared, device, stats):
                 wr.writerow([label, r.chain, r.number, r.name, letters[0][k], letters[1][k], three[0][k], three[1][k], m.chain, m.number])
 
 
+def pearson(a, b):
+    """the Pearson correlation of two equally long sequences of numbers; NaN under 2 numbers or where either does not vary"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if len(a) < 2:
+        return float("nan")
+    da, db = a - a.mean(), b - b.mean()
+    norm = float(np.sqrt((da * da).sum() * (db * db).sum()))
+    return float((da * db).sum()) / norm if norm > 0 else float("nan")
+
+
+def write_sasa(out, todo, prepared, args, stats):
+    """model_sasa.csv and residue_sasa.csv: every distinct structure of ``prepared`` goes through the kernel once, in one batch"""
+    distinct = {}
+    for item in prepared.pairs:
+        if not isinstance(item, str):
+            for side in item[:2]:
+                distinct.setdefault(id(side), side)
+    measured = sasa_module.sasa_layouts([sasa_module.layout_of_residues(side.residues) for side in distinct.values()],
+                                        probe=getattr(args, "sasa_probe", 1.4), n_points=getattr(args, "sasa_points", 96), device=args.device,
+                                        core=getattr(args, "rsa_core", 0.2), surface=getattr(args, "rsa_surface", 0.5), stats=stats)
+    measured = dict(zip(distinct, measured))
+    nan = float("nan")
+    with open(out / "model_sasa.csv", "w", newline="") as fs, open(out / "residue_sasa.csv", "w", newline="") as fr:
+        ws, wr = csv.writer(fs), csv.writer(fr)
+        ws.writerow(SASA_COLUMNS)
+        wr.writerow(RESIDUE_SASA_COLUMNS)
+        for (label, ref, model), item in zip(todo, prepared.pairs):
+            if isinstance(item, str):
+                ws.writerow([label, str(ref), str(model), 0] + [_fmt(nan)] * 7 + [item])
+                continue
+            ours, theirs = np.asarray(item[2], dtype=np.int64), np.asarray(item[3], dtype=np.int64)
+            a, b = measured[id(item[0])], measured[id(item[1])]
+            n = len(ours)
+            mine, other = a.rsa[ours], b.rsa[theirs]
+            known = ~(np.isnan(mine) | np.isnan(other))
+            agreement = float((a.burial[ours] == b.burial[theirs]).sum()) / n if n else nan
+            difference = float(np.abs(mine[known] - other[known]).mean()) if known.any() else nan
+            ws.writerow([label, str(ref), str(model), n, _fmt(a.total_area), _fmt(a.total_apolar_area), _fmt(b.total_area), _fmt(b.total_apolar_area),
+                         _fmt(agreement), _fmt(difference), _fmt(pearson(mine[known], other[known])), ""])
+            letters = a.burial_letters, b.burial_letters
+            for i, j in zip(ours.tolist(), theirs.tolist()):
+                r, m = a.residues[i], b.residues[j]
+                wr.writerow([label, r.chain, r.number, r.name, _fmt(a.residue_area[i]), _fmt(b.residue_area[j]), _fmt(a.rsa[i]), _fmt(b.rsa[j]),
+                             letters[0][i], letters[1][j], m.chain, m.number])
+
+
 def tm_sum(dist, d0, norm_length):
     """sum over the numbers of ``dist``, in index order, of 1 / (1 + (d / d0)^2), divided by ``norm_length``: NaN when there is none"""
     total, seen = 0.0, False
@@ -226,6 +291,8 @@ def main(args):
         sys.exit("no pair to score: no *.pdb / *.pdb1 / *.ent (.gz) file under --path_to_models, or an empty --pairs file")
     if args.lddt and not (args.lddt_radius > 0 and args.lddt_radius < float("inf")):
         sys.exit(f"--lddt_radius {args.lddt_radius} is not a positive finite number")
+    if getattr(args, "sasa", False) and not 1 <= getattr(args, "sasa_points", 96) <= sasa_module.MAX_POINTS:
+        sys.exit(f"--sasa_points {args.sasa_points} is outside 1 .. {sasa_module.MAX_POINTS}")
     if args.tmscore and args.tm_rounds < 0:
         sys.exit(f"--tm_rounds {args.tm_rounds} is negative")
     aligning = args.cealign or args.pair_by_cealign
@@ -252,6 +319,8 @@ def main(args):
         write_lddt(out, todo, lddt_module.lddt(prepared, radius=args.lddt_radius, device=args.device, stats=stats))
     if args.secondary_structure:
         write_secstruct(out, todo, prepared, args.device, stats)
+    if getattr(args, "sasa", False):
+        write_sasa(out, todo, prepared, args, stats)
     if args.tmscore:
         write_tmscore(out, todo, tmscore_module.tmscore(prepared, rounds=args.tm_rounds, device=args.device, stats=stats),
                       superpose.superpose(prepared, cycles=0, device=args.device, stats=stats))
@@ -309,6 +378,15 @@ CLI_FLAGS = (
                                         "structures, the share of paired positions whose class (q8) and whose helix / strand / coil state (q3) "
                                         "agree, and the helix and strand fractions and hydrogen bonds of either side.  PARITY UNPINNED AGAINST "
                                         "DSSP")),
+    # absent from the namespace unless given: a namespace built by an older caller has no such attribute either
+    ("--sasa", dict(default=argparse.SUPPRESS, action="store_true",
+                    help="also write model_sasa.csv and residue_sasa.csv: the solvent-accessible surface area (Shrake & Rupley) of both "
+                         "structures, the share of paired positions in the same burial class, the mean absolute difference and the "
+                         "correlation of their relative accessibilities.  PARITY UNPINNED AGAINST FREESASA / NACCESS / DSSP / BIOPYTHON")),
+    ("--sasa_points", dict(default=argparse.SUPPRESS, type=int, help="--sasa: golden-spiral points per atom, 1 .. 1024 (default 96)")),
+    ("--sasa_probe", dict(default=argparse.SUPPRESS, type=float, help="--sasa: probe radius in Angstrom (default 1.4; 0: the van der Waals surface)")),
+    ("--rsa_core", dict(default=argparse.SUPPRESS, type=float, help="--sasa: a residue is core below this relative accessibility (default 0.2)")),
+    ("--rsa_surface", dict(default=argparse.SUPPRESS, type=float, help="--sasa: a residue is surface from this relative accessibility (default 0.5)")),
 )
 
 

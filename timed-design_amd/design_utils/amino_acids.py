@@ -40,6 +40,19 @@ PROPERTIES = ("polarity", "charge")      # the reference's accepted_properties (
 PROPERTY_VALUES = {"polarity": (0, 1), "charge": (-1, 0, 1)}
 PROPERTY_TABLE = {"polarity": residue_polarity, "charge": residue_charge}
 
+# Solvent-accessible surface area (timed_hip/sasa.py).  Van der Waals radii by element in Angstrom (Bondi 1964); an element that is
+# not listed takes VDW_RADIUS_OTHER.  A caller may pass a dict of their own.
+vdw_radii = {"C": 1.70, "N": 1.55, "O": 1.52, "S": 1.80, "P": 1.80, "SE": 1.90}
+VDW_RADIUS_OTHER = 1.80
+# Maximum solvent-accessible area of each residue in Angstrom^2, after Tien et al. 2013 (their theoretical values): the divisor of
+# the relative accessibility.  WRITTEN FROM MEMORY, NOT FETCHED: nothing here could be checked against the paper.
+max_asa = {
+    "ALA": 129.0, "ARG": 274.0, "ASN": 195.0, "ASP": 193.0, "CYS": 167.0, "GLN": 225.0, "GLU": 223.0, "GLY": 104.0, "HIS": 224.0,
+    "ILE": 197.0, "LEU": 201.0, "LYS": 236.0, "MET": 224.0, "PHE": 240.0, "PRO": 159.0, "SER": 155.0, "THR": 172.0, "TRP": 285.0,
+    "TYR": 263.0, "VAL": 174.0,
+}
+WATER_NAMES = ("HOH", "WAT", "DOD")
+
 # Stand-in for aposteriori.config.UNCOMMON_RESIDUE_DICT (used at reference utils.py:381-385 to map a
 # non-standard residue label onto its parent amino acid while the dataset map is built).  aposteriori
 # 2.4.0 is not in the reference tree nor in this image, so its exact table is UNPINNED; this one holds

@@ -151,6 +151,23 @@ def extract_packdensity_from_ampal(pdb, load_pdb: bool = True, atom_filter: str 
     return [[float(v) for v in res.residue_density]]
 
 
+def extract_sasa_from_ampal(pdb, load_pdb: bool = True, probe: float = 1.4, n_points: int = 96, include_hetero: bool = False,
+                            device: int = 0) -> t.List[t.List[float]]:
+    """No counterpart in the reference, named after its siblings: one list per chain (non-hetero residues, chains in order of
+    appearance) with the solvent-accessible surface area of each residue in square Angstrom — Shrake & Rupley (1973) with
+    ``n_points`` golden-spiral points per atom, element radii after Bondi plus ``probe``, on the GPU through
+    ``timed_hip.sasa.sasa``.  ``pdb`` is a path (plain or gzipped PDB file) or, with ``load_pdb=False``, a ``timed_hip.pdbio.Model``.
+    PARITY UNPINNED AGAINST FREESASA / NACCESS / DSSP / BIOPYTHON: the rule is this project's own (include/timed_hip.h, th_sasa).
+    For many structures call ``sasa`` itself: it batches them."""
+    from timed_hip import sasa, structure
+    model = structure.first_model(pdb) if load_pdb else pdb
+    (res,) = sasa.sasa([model], probe=probe, n_points=n_points, include_hetero=include_hetero, device=device)
+    chains: dict = {}
+    for r, a in zip(res.residues, res.residue_area.tolist()):
+        chains.setdefault(r.chain, []).append(float(a))
+    return list(chains.values())
+
+
 def extract_bfactor_from_ampal(pdb_path, load_pdb: bool = True) -> t.List[t.List[float]]:
     """reference analyse_utils.py:112-146: one list per chain with the B-factor of the first atom of each residue (AlphaFold2
     models carry the pLDDT there).  ``pdb_path`` is a path or, with ``load_pdb=False``, a ``timed_hip.pdbio.Model``.  Differs
