@@ -301,6 +301,13 @@ def test_header_ctypes_build_list_and_the_unpinned_parity_phrase():
     assert "cealign.hip" in __graft_entry__.HIP_SOURCES
     source = open(os.path.join(ROOT, "timed-design_amd", "csrc", "cealign.hip")).read()
     assert PHRASE in source and '#include "horn_fit.h"' in source and "fp contract(off)" in source and "horn_rotation(C, F)" in source
+    shared = open(os.path.join(ROOT, "timed-design_amd", "csrc", "horn_fit.h")).read()
+    for only_shared in ("f.cr[x] - ((f.R[3 * x]", "+ f.cr[0]) - ref[0]", "S[x][y] += a[x] * b[y]", "sm[a] += mob[a]"):     # the transform store, the
+        assert shared.count(only_shared) == 1, only_shared                                                             # distance, the two sums
+    for piece in ("add_position(", "add_covariance(", "distance(fit,", "store(best_fit,"):          # the shared steps, in path order
+        assert piece in source, piece
+    for copied in ("cr[x] - ((", "[3 * x] *", "+ cr[0]) -", "+ fr[0]) -", "+= u[x] * v[y]", "+= a[x] * b[y]"):
+        assert copied not in source, copied
     assert "atomic" not in source.replace("No atomics", "") and "asm" not in source
     for kernel in ("k_ce_windows", "k_ce_similarity", "k_ce_paths", "k_ce_best"):
         assert f"hipLaunchKernelGGL({kernel}" in source, kernel

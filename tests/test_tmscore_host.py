@@ -271,6 +271,17 @@ def test_header_ctypes_build_list_and_the_unpinned_parity_phrase():
     shared = open(os.path.join(ROOT, "timed-design_amd", "csrc", "horn_fit.h")).read()
     assert "horn_rotation" in shared and "fp contract(off)" in shared
     assert "horn_rotation(const" not in open(os.path.join(ROOT, "timed-design_amd", "csrc", "superpose.hip")).read()      # moved, not copied
+    # so are the transform store, the distance under a fit and the two accumulation steps: once in horn_fit.h, in no kernel file
+    moved = ("f.cr[x] - ((f.R[3 * x]", "+ f.cr[0]) - ref[0]", "S[x][y] += a[x] * b[y]", "sm[a] += mob[a]")
+    old = ("cr[x] - ((R[3 * x]", "+ cr[0]) -", "+ fr[0]) -", "[x][y] += ", "sm[a] +=", "fm[x] +=")
+    for text in moved:
+        assert shared.count(text) == 1, text
+    for unit in ("superpose.hip", "tmscore.hip", "cealign.hip"):
+        kernel_file = open(os.path.join(ROOT, "timed-design_amd", "csrc", unit)).read()
+        for text in moved + old:
+            assert text not in kernel_file, (unit, text)
+        assert "store(" in kernel_file and "distance(" in kernel_file and "Fit " in kernel_file, unit
+    assert "wave_fit(" in source and "tm_dist" not in source and "bcm" not in source
     import analyse_models
     text = re.sub(r"\s+", " ", analyse_models.build_parser().format_help())
     assert PHRASE in text and "--tmscore" in text and "4096" in text

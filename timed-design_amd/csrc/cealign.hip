@@ -26,6 +26,7 @@
 
 #include <climits>
 #include <cmath>
+#include <new>
 #include <vector>
 
 #include "common.h"
@@ -227,8 +228,7 @@ __global__ void __launch_bounds__(kWave) k_ce_best(const double* __restrict__ ca
     const int n_cand = n_starts < TH_CE_KEEP ? n_starts : TH_CE_KEEP;
 
     const double nan = __builtin_nan("");
-    double cm[3] = {0.0, 0.0, 0.0}, cr[3] = {0.0, 0.0, 0.0};
-    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    Fit best_fit;
     double best_rmsd = nan, best_score = nan;
     int best_n = 0;
     int prev_len = INT_MAX, prev_at = -1;                              // the candidate taken last: before every start
@@ -267,47 +267,23 @@ __global__ void __launch_bounds__(kWave) k_ce_best(const double* __restrict__ ca
         // candidates differ by rounding alone, and the order of addition decides among them.  Every lane forms the same sums itself
         // (the loads are one address per wave); 20 candidates of at most 2048 pairs are nothing beside the paths.
         const int count = kW * n;
-        double fm[3] = {0.0, 0.0, 0.0}, fr[3] = {0.0, 0.0, 0.0};
-        for (int i = 0; i < count; ++i) {
-            const int afp = traced[i / kW];
-            const int ia = (afp >> 16) + i % kW, ib = (afp & 0xffff) + i % kW;
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                fm[x] += B[3 * ib + x];
-                fr[x] += A[3 * ia + x];
-            }
-        }
+        const auto ref_at = [&](int i) { return A + 3 * ((traced[i / kW] >> 16) + i % kW); };          // position pair i of the path:
+        const auto mob_at = [&](int i) { return B + 3 * ((traced[i / kW] & 0xffff) + i % kW); };       // its reference and its mobile side
+        Fit fit;
+        double sr[3] = {0.0, 0.0, 0.0}, sm[3] = {0.0, 0.0, 0.0};
+        for (int i = 0; i < count; ++i) add_position(ref_at(i), mob_at(i), sr, sm);
 #pragma unroll
         for (int x = 0; x < 3; ++x) {
-            fm[x] = fm[x] / (double)count;
-            fr[x] = fr[x] / (double)count;
+            fit.cm[x] = sm[x] / (double)count;
+            fit.cr[x] = sr[x] / (double)count;
         }
         double C[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-        for (int i = 0; i < count; ++i) {
-            const int afp = traced[i / kW];
-            const int ia = (afp >> 16) + i % kW, ib = (afp & 0xffff) + i % kW;
-            double u[3], v[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                u[x] = B[3 * ib + x] - fm[x];
-                v[x] = A[3 * ia + x] - fr[x];
-            }
-#pragma unroll
-            for (int x = 0; x < 3; ++x)
-#pragma unroll
-                for (int y = 0; y < 3; ++y) C[x][y] += u[x] * v[y];
-        }
-        double F[9];
+        for (int i = 0; i < count; ++i) add_covariance(fit, ref_at(i), mob_at(i), C);
+        double (&F)[9] = fit.R;                                        // this candidate's rotation
         horn_rotation(C, F);
         double sq = 0.0;
         for (int i = 0; i < count; ++i) {
-            const int afp = traced[i / kW];
-            const int ia = (afp >> 16) + i % kW, ib = (afp & 0xffff) + i % kW;
-            const double ax = B[3 * ib] - fm[0], ay = B[3 * ib + 1] - fm[1], az = B[3 * ib + 2] - fm[2];
-            const double dx = (((F[0] * ax + F[1] * ay) + F[2] * az) + fr[0]) - A[3 * ia];
-            const double dy = (((F[3] * ax + F[4] * ay) + F[5] * az) + fr[1]) - A[3 * ia + 1];
-            const double dz = (((F[6] * ax + F[7] * ay) + F[8] * az) + fr[2]) - A[3 * ia + 2];
-            const double d = sqrt((dx * dx + dy * dy) + dz * dz);
+            const double d = distance(fit, ref_at(i), mob_at(i));
             sq += d * d;
         }
         const double rmsd = sqrt(sq / (double)count);
@@ -315,13 +291,7 @@ __global__ void __launch_bounds__(kWave) k_ce_best(const double* __restrict__ ca
             best_rmsd = rmsd;
             best_score = score;
             best_n = n;
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                cm[x] = fm[x];
-                cr[x] = fr[x];
-            }
-#pragma unroll
-            for (int x = 0; x < 9; ++x) R[x] = F[x];
+            best_fit = fit;
             for (int k = lane; k < n; k += kWave) winner[k] = traced[k];
         }
         __syncthreads();
@@ -345,16 +315,7 @@ __global__ void __launch_bounds__(kWave) k_ce_best(const double* __restrict__ ca
     count[3] = best_n;
     count[4] = kW * best_n;
     count[5] = n_cand;
-    if (transform_out) {                                               // moved = R mob + t, t = cr - R cm; the identity when there is no start
-        double* t = transform_out + 12 * pair;
-#pragma unroll
-        for (int x = 0; x < 3; ++x) {
-            t[4 * x] = R[3 * x];
-            t[4 * x + 1] = R[3 * x + 1];
-            t[4 * x + 2] = R[3 * x + 2];
-            t[4 * x + 3] = cr[x] - ((R[3 * x] * cm[0] + R[3 * x + 1] * cm[1]) + R[3 * x + 2] * cm[2]);
-        }
-    }
+    if (transform_out) store(best_fit, transform_out + 12 * pair);     // the identity when there is no start
 }
 
 // offsets of one of the two lists: from 0 to total, never decreasing, no structure above the limit
@@ -372,7 +333,7 @@ long long ce_compact(const double* xyz, long long lo, long long n, std::vector<d
     long long m = 0;
     for (long long i = 0; i < n; ++i) {
         const double* r = xyz + 3 * (lo + i);
-        if (std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2])) {
+        if (finite3(r)) {
             out.insert(out.end(), r, r + 3);
             orig.push_back((int)i);
             ++m;
@@ -409,35 +370,40 @@ extern "C" int th_cealign(int device, const double* ref_xyz, int64_t ref_total, 
     if (int rc = ce_check_offsets("mob", "mob_offsets", "mob_total", mob_offsets, mob_total, n_pairs)) return rc;
 
     const size_t np = (size_t)n_pairs, nr = (size_t)ref_total;
-    std::vector<CePair> pairs(np + 1);
+    std::vector<CePair> pairs;
     std::vector<double> ca, cb;
     std::vector<int> orig_a, orig_b;
-    ca.reserve(3 * nr);
-    cb.reserve(3 * (size_t)mob_total);
     long long rows_a = 0, rows_b = 0, n_windows = 0, n_tiles = 0;
-    for (size_t p = 0; p < np; ++p) {
-        CePair& q = pairs[p];
-        q.alo = ref_offsets[p];
-        q.na = ref_offsets[p + 1] - ref_offsets[p];
-        q.blo = mob_offsets[p];
-        q.nb = mob_offsets[p + 1] - mob_offsets[p];
-        q.calo = (long long)orig_a.size();
-        q.cblo = (long long)orig_b.size();
-        q.ma = ce_compact(ref_xyz, q.alo, q.na, ca, orig_a);
-        q.mb = ce_compact(mob_xyz, q.blo, q.nb, cb, orig_b);
-        q.ralo = rows_a;
-        q.rblo = rows_b;
-        q.wlo = n_windows;
-        q.tlo = n_tiles;
-        if (q.ma >= kW && q.mb >= kW) {                                // otherwise the pair has no window start at all
-            const long long ra = q.ma - kW + 1, rb = q.mb - kW + 1;
-            rows_a += ra;
-            rows_b += rb;
-            n_windows += ra * rb;
-            n_tiles += ((ra + kTile - 1) / kTile) * ((rb + kTile - 1) / kTile);
+    try {
+        pairs.resize(np + 1);
+        ca.reserve(3 * nr);
+        cb.reserve(3 * (size_t)mob_total);
+        for (size_t p = 0; p < np; ++p) {
+            CePair& q = pairs[p];
+            q.alo = ref_offsets[p];
+            q.na = ref_offsets[p + 1] - ref_offsets[p];
+            q.blo = mob_offsets[p];
+            q.nb = mob_offsets[p + 1] - mob_offsets[p];
+            q.calo = (long long)orig_a.size();
+            q.cblo = (long long)orig_b.size();
+            q.ma = ce_compact(ref_xyz, q.alo, q.na, ca, orig_a);
+            q.mb = ce_compact(mob_xyz, q.blo, q.nb, cb, orig_b);
+            q.ralo = rows_a;
+            q.rblo = rows_b;
+            q.wlo = n_windows;
+            q.tlo = n_tiles;
+            if (q.ma >= kW && q.mb >= kW) {                            // otherwise the pair has no window start at all
+                const long long ra = q.ma - kW + 1, rb = q.mb - kW + 1;
+                rows_a += ra;
+                rows_b += rb;
+                n_windows += ra * rb;
+                n_tiles += ((ra + kTile - 1) / kTile) * ((rb + kTile - 1) / kTile);
+            }
         }
+        pairs[np] = CePair{ref_total, 0, mob_total, 0, (long long)orig_a.size(), 0, (long long)orig_b.size(), 0, rows_a, rows_b, n_windows, n_tiles};
+    } catch (const std::bad_alloc&) {
+        TH_FAIL(TH_ENOMEM, "th_cealign: out of host memory for the valid positions of %lld + %lld positions", (long long)ref_total, (long long)mob_total);
     }
-    pairs[np] = CePair{ref_total, 0, mob_total, 0, (long long)orig_a.size(), 0, (long long)orig_b.size(), 0, rows_a, rows_b, n_windows, n_tiles};
     if ((n_windows + kPerBlock - 1) / kPerBlock > INT_MAX)
         TH_FAIL(TH_EINVAL, "th_cealign: %lld window pairs in one call (limit 2^33 - 4): submit fewer pairs at once", n_windows);
     const size_t nca = orig_a.size(), ncb = orig_b.size(), nw = (size_t)n_windows;

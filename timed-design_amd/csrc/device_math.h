@@ -1,6 +1,11 @@
-// Device helpers shared by every kernel: the wave-wide sums, Keras activations and the fused epilogue.
+// Device helpers shared by every kernel: the wave-wide sums, the finiteness test of a position, Keras activations and the fused
+// epilogue.
 #pragma once
 #include "common.h"
+
+// a position whose three coordinates are finite: the kernels and the host's preparation ask it the same way
+__host__ __device__ inline bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
+__host__ __device__ inline bool finite3(const double* p) { return __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]); }
 
 // the sum of v over the 64 lanes of a wavefront, in every lane (xor butterfly: every lane adds in the same order)
 __device__ inline double wave_sum(double v) {

@@ -1,6 +1,9 @@
-// The least-squares fit shared by th_superpose (superpose.hip) and th_tmscore (tmscore.hip): the finiteness test of a position, one
-// Jacobi rotation and Horn's quaternion route from a 3 x 3 cross-covariance to the proper rotation; the wave-wide sums are
-// device_math.h's.  Device code for one 64-lane wavefront; every lane computes the same bits.
+// The one least-squares superposition of th_superpose (superpose.hip), th_tmscore (tmscore.hip) and th_cealign (cealign.hip):
+// Fit is its state, moved = R (mob - cm) + cr; distance() and store() are the only places that expression and its [R | t] form are
+// written; add_position() and add_covariance() are the two accumulation steps on a lane's own partial sums; wave_fit() runs them
+// lane-strided over one 64-lane wavefront with device_math.h's wave_sum between them (k_ce_best runs them serially, in path order,
+// itself); horn_rotation() is one cyclic Jacobi and Horn's quaternion route from the 3 x 3 cross-covariance to the proper
+// rotation.  Every lane computes the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,8 +16,6 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kSweeps = 10;                       // Jacobi sweeps at most (a 4 x 4 matrix is diagonal to the last bit after 5 or 6)
-
-__device__ inline bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 
 // one Jacobi rotation in the (P, Q) plane: A <- J^T A J, V <- V J
 template <int P, int Q>
@@ -101,6 +102,74 @@ __device__ inline void horn_rotation(const double (&S)[3][3], double (&R)[9]) {
     R[6] = 2.0 * (x * z - w * y);
     R[7] = 2.0 * (y * z + w * x);
     R[8] = ((ww - xx) - yy) + zz;
+}
+
+// a superposition: moved = R (mob - cm) + cr, R row-major; the identity until something has been fitted
+struct Fit {
+    double cm[3] = {0.0, 0.0, 0.0}, cr[3] = {0.0, 0.0, 0.0};
+    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+};
+
+// the distance of one position pair (three doubles each) under f
+__device__ inline double distance(const Fit& f, const double* ref, const double* mob) {
+    const double ax = mob[0] - f.cm[0], ay = mob[1] - f.cm[1], az = mob[2] - f.cm[2];
+    const double dx = (((f.R[0] * ax + f.R[1] * ay) + f.R[2] * az) + f.cr[0]) - ref[0];
+    const double dy = (((f.R[3] * ax + f.R[4] * ay) + f.R[5] * az) + f.cr[1]) - ref[1];
+    const double dz = (((f.R[6] * ax + f.R[7] * ay) + f.R[8] * az) + f.cr[2]) - ref[2];
+    return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
+// f as the 12 doubles [R | t] of moved = R mob + t, t = cr - R cm
+__device__ inline void store(const Fit& f, double* t) {
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        t[4 * x] = f.R[3 * x];
+        t[4 * x + 1] = f.R[3 * x + 1];
+        t[4 * x + 2] = f.R[3 * x + 2];
+        t[4 * x + 3] = f.cr[x] - ((f.R[3 * x] * f.cm[0] + f.R[3 * x + 1] * f.cm[1]) + f.R[3 * x + 2] * f.cm[2]);
+    }
+}
+
+// the two passes of a fit over one position pair: the sums behind the centroids, then the cross-covariance of the centred pair
+__device__ inline void add_position(const double* ref, const double* mob, double (&sr)[3], double (&sm)[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        sm[a] += mob[a];
+        sr[a] += ref[a];
+    }
+}
+
+__device__ inline void add_covariance(const Fit& f, const double* ref, const double* mob, double (&S)[3][3]) {
+    double a[3], b[3];
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        a[x] = mob[x] - f.cm[x];
+        b[x] = ref[x] - f.cr[x];
+    }
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 3; ++y) S[x][y] += a[x] * b[y];
+}
+
+// The fit of one wavefront over `count` selected positions of ref / mob.  each(visit) calls visit(i) for the selected positions i
+// that this lane owns, in increasing order: the order of a lane's own additions; the lanes then meet in wave_sum's butterfly.
+template <class Each>
+__device__ inline void wave_fit(const double* ref, const double* mob, Each each, double count, Fit& f) {
+    double sr[3] = {0.0, 0.0, 0.0}, sm[3] = {0.0, 0.0, 0.0};
+    each([&](auto i) { add_position(ref + 3 * i, mob + 3 * i, sr, sm); });
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        f.cm[a] = wave_sum(sm[a]) / count;
+        f.cr[a] = wave_sum(sr[a]) / count;
+    }
+    double S[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};          // two-pass: of the centred coordinates
+    each([&](auto i) { add_covariance(f, ref + 3 * i, mob + 3 * i, S); });
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 3; ++y) S[x][y] = wave_sum(S[x][y]);
+    horn_rotation(S, f.R);
 }
 
 }  // namespace

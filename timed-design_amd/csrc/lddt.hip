@@ -46,8 +46,8 @@ constexpr int kTile = 256;                     // positions i per work item = th
 constexpr int kWave = 64;
 constexpr int kPerBlock = kTile / kWave;       // pairs per workgroup of k_lddt_totals
 
-struct Item { int pair, tile; };               // positions offsets[pair] + tile * kTile ... of that pair
-
+// finite3(a) && finite3(b) of device_math.h, kept as one chain of six: written with finite3, hipcc folds each half into selects
+// before it inlines, and k_lddt's staging loop comes out as other code in other registers (58 -> 56 VGPRs)
 __device__ inline bool finite6(const double* a, const double* b) {
     return __builtin_isfinite(a[0]) && __builtin_isfinite(a[1]) && __builtin_isfinite(a[2]) && __builtin_isfinite(b[0]) &&
            __builtin_isfinite(b[1]) && __builtin_isfinite(b[2]);
@@ -56,12 +56,12 @@ __device__ inline bool finite6(const double* a, const double* b) {
 struct Limits { double t[4]; };
 
 __global__ void __launch_bounds__(kTile) k_lddt(const double* __restrict__ ref_xyz, const double* __restrict__ mob_xyz,
-                                                const long long* __restrict__ offsets, const Item* __restrict__ items, double threshold,
+                                                const long long* __restrict__ offsets, const ThTile* __restrict__ items, double threshold,
                                                 Limits lim, int* __restrict__ residue_out) {
     __shared__ __attribute__((aligned(16))) double rx[kTile], ry[kTile], rz[kTile], mx[kTile], my[kTile], mz[kTile];
     const int tid = threadIdx.x;
-    const Item it = items[blockIdx.x];
-    const long long begin = offsets[it.pair], end = offsets[it.pair + 1];
+    const ThTile it = items[blockIdx.x];       // positions offsets[range] + tile * kTile ... of that pair
+    const long long begin = offsets[it.range], end = offsets[it.range + 1];
     const long long i = begin + (long long)it.tile * kTile + tid;
     const bool live = i < end;
     const double nan = __builtin_nan("");
@@ -183,33 +183,25 @@ extern "C" int th_lddt(int device, const double* ref_xyz, const double* mob_xyz,
         TH_FAIL(TH_EINVAL, "th_lddt: n_pairs = %lld needs offsets and pair_out, total = %lld needs ref_xyz, mob_xyz and residue_out",
                 (long long)n_pairs, (long long)total);
     if (int rc = th_check_offsets("th_lddt", "offsets", "total", offsets, n_pairs, total)) return rc;
-    std::vector<Item> items;
-    try {
-        for (int64_t p = 0; p < n_pairs; ++p) {
-            const int64_t tiles = (offsets[p + 1] - offsets[p] + kTile - 1) / kTile;
-            for (int64_t t = 0; t < tiles; ++t) items.push_back(Item{(int)p, (int)t});
-        }
-    } catch (const std::bad_alloc&) {
-        TH_FAIL(TH_ENOMEM, "th_lddt: out of host memory for the work items of %lld positions", (long long)total);
-    }
-    if (items.size() > (size_t)INT_MAX) TH_FAIL(TH_EINVAL, "th_lddt: %zu work items in one call (limit 2^31 - 1)", items.size());
+    std::vector<ThTile> items;
+    if (int rc = th_tile_items("th_lddt", "positions", offsets, n_pairs, kTile, items)) return rc;
 
     const size_t n = (size_t)total, np = (size_t)n_pairs;
     ThLayout lay;
     const size_t o_ref = lay.take(n * 3 * sizeof(double)), o_mob = lay.take(n * 3 * sizeof(double));
-    const size_t o_offsets = lay.take((np + 1) * sizeof(int64_t)), o_items = lay.take(items.size() * sizeof(Item));
+    const size_t o_offsets = lay.take((np + 1) * sizeof(int64_t)), o_items = lay.take(items.size() * sizeof(ThTile));
     const size_t o_res = lay.take(n * 5 * sizeof(int32_t)), o_pair = lay.take(np * 6 * sizeof(int64_t));
     ThCall call;
     if (int rc = call.open("th_lddt", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
     double *d_ref = call.at<double>(o_ref), *d_mob = call.at<double>(o_mob);
     long long *d_offsets = call.at<long long>(o_offsets), *d_pair = call.at<long long>(o_pair);
-    Item* d_items = call.at<Item>(o_items);
+    ThTile* d_items = call.at<ThTile>(o_items);
     int* d_res = call.at<int>(o_res);
     hipStream_t st = call.st[0];
     if (n) {
         HIP_TRY(hipMemcpyAsync(d_ref, ref_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_mob, mob_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ThTile), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(call.mark(0));

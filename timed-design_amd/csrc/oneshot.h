@@ -1,7 +1,11 @@
 // Host scaffolding of the one-shot entry points (th_superpose, th_lddt, th_tmscore, ...): a call validates its arguments, lays one
 // device allocation out, opens a scope, copies in, launches, copies out and returns; whatever it holds on the device goes with the
-// scope on every return path.  Three plain pieces and no driver: the entry point itself stays the list of HIP calls, top to bottom.
+// scope on every return path.  Four plain pieces and no driver: the entry point itself stays the list of HIP calls, top to bottom.
 #pragma once
+#include <climits>
+#include <new>
+#include <vector>
+
 #include "common.h"
 
 // Byte offsets inside the call's one allocation: every array starts on a 256-byte boundary.
@@ -69,5 +73,23 @@ inline int th_check_offsets(const char* who, const char* name, const char* total
                 total_name, (long long)total);
     for (int64_t p = 0; p < n; ++p)
         if (offsets[p + 1] < offsets[p]) TH_FAIL(TH_EINVAL, "%s: %s[%lld] > %s[%lld]", who, name, (long long)p, name, (long long)p + 1);
+    return TH_OK;
+}
+
+// A work item of the kernels that stream a range past a tile of it: elements offsets[range] + tile * length ... of that range.
+struct ThTile { int range, tile; };
+
+// items: one per started tile of `length` elements of each of the n ranges of offsets, in range order; `what` names the elements
+inline int th_tile_items(const char* who, const char* what, const int64_t* offsets, int64_t n, int64_t length, std::vector<ThTile>& items) {
+    try {
+        items.reserve((size_t)(offsets[n] / length + (n < offsets[n] ? n : offsets[n])));      // a range with elements has one partial tile at most
+        for (int64_t r = 0; r < n; ++r) {
+            const int64_t tiles = (offsets[r + 1] - offsets[r] + length - 1) / length;
+            for (int64_t t = 0; t < tiles; ++t) items.push_back(ThTile{(int)r, (int)t});
+        }
+    } catch (const std::bad_alloc&) {
+        TH_FAIL(TH_ENOMEM, "%s: out of host memory for the work items of %lld %s", who, (long long)offsets[n], what);
+    }
+    if (items.size() > (size_t)INT_MAX) TH_FAIL(TH_EINVAL, "%s: %zu work items in one call (limit 2^31 - 1)", who, items.size());
     return TH_OK;
 }

@@ -47,7 +47,6 @@ constexpr int kXyz = kScMaxAtoms * 3;          // doubles per candidate / per re
 
 struct Ladder { int n; double thr[TH_PACK_MAX_LEVELS]; double top; };
 struct PackTab { int n_chi[kScTypes], class_base[kScTypes], sg_slot[kScTypes]; };
-struct PItem { int structure, tile; };
 
 __constant__ PackTab c_pack;
 
@@ -102,12 +101,12 @@ __device__ inline int levels_under(const Ladder& lad, double s) {
 __global__ void __launch_bounds__(kBlock) k_pack_backbone(const double* __restrict__ backbone, int nb, const int* __restrict__ chain_id,
                                                           const long long* __restrict__ offsets, const long long* __restrict__ cand_off,
                                                           const int* __restrict__ cand_res, const double* __restrict__ cand_xyz,
-                                                          const PItem* __restrict__ items, Ladder lad, int* __restrict__ bb_pen) {
+                                                          const ThTile* __restrict__ items, Ladder lad, int* __restrict__ bb_pen) {
     __shared__ double jx[kBlock], jy[kBlock], jz[kBlock];
     __shared__ int jres[kBlock], jchain[kBlock], cnt[kBlock];
     const int tid = threadIdx.x;
-    const PItem it = items[blockIdx.x];
-    const long long begin = offsets[it.structure], end = offsets[it.structure + 1];
+    const ThTile it = items[blockIdx.x];       // candidates tile * kBbCand ... of the residues offsets[range] ... of that structure
+    const long long begin = offsets[it.range], end = offsets[it.range + 1];
     const int len = (int)(end - begin);
     const long long c = cand_off[begin] + (long long)it.tile * kBbCand + tid / kScMaxAtoms;
     const int slot = tid % kScMaxAtoms;
@@ -428,7 +427,7 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     // the candidates: 3^n_chi per residue that has a side chain and a finite N, CA, C, in a structure within the limit
     std::vector<long long> cand_off;
     std::vector<int> cand_res;
-    std::vector<PItem> items;
+    std::vector<ThTile> items;
     int max_len = 0;
     try {
         cand_off.assign(nr + 1, 0);
@@ -448,7 +447,7 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
                 for (int k = 0; k < nc; ++k) cand_res.push_back((int)r);
             }
             const int64_t tiles = (cand_off[hi] - cand_off[lo] + kBbCand - 1) / kBbCand;
-            for (int64_t t = 0; t < tiles; ++t) items.push_back(PItem{(int)s, (int)t});
+            for (int64_t t = 0; t < tiles; ++t) items.push_back(ThTile{(int)s, (int)t});
         }
     } catch (const std::bad_alloc&) {
         TH_FAIL(TH_ENOMEM, "th_pack_sidechains: out of host memory for the candidates of %lld residues", (long long)n_res);
@@ -466,7 +465,7 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     const size_t o_bb = lay.take(nr * nb * 3 * sizeof(double)), o_type = lay.take(nr), o_chain = lay.take(chain_id ? nr * sizeof(int32_t) : 0);
     const size_t o_soff = lay.take((ns + 1) * sizeof(int64_t)), o_coff = lay.take((nr + 1) * sizeof(long long)), o_cres = lay.take(ncand * sizeof(int));
     const size_t o_cxyz = lay.take(ncand * kXyz * sizeof(double)), o_cok = lay.take(ncand), o_bbpen = lay.take(ncand * sizeof(int));
-    const size_t o_prior = lay.take(prior_cost ? nr * kMaxCand * sizeof(int32_t) : 0), o_items = lay.take(items.size() * sizeof(PItem));
+    const size_t o_prior = lay.take(prior_cost ? nr * kMaxCand * sizeof(int32_t) : 0), o_items = lay.take(items.size() * sizeof(ThTile));
     const size_t o_cur = lay.take(nr * kXyz * sizeof(double)), o_curk = lay.take(nr * sizeof(int)), o_cls = lay.take(nr * sizeof(int16_t));
     const size_t o_c0 = lay.take(nr * sizeof(int64_t)), o_c1 = lay.take(nr * sizeof(int64_t)), o_e0 = lay.take(ns * sizeof(int64_t));
     const size_t o_e1 = lay.take(ns * sizeof(int64_t)), o_search = lay.take(ns * 4 * sizeof(int32_t));
@@ -479,7 +478,7 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     int *d_cres = call.at<int>(o_cres), *d_bbpen = call.at<int>(o_bbpen);
     unsigned char* d_cok = call.at<unsigned char>(o_cok);
     int* d_prior = prior_cost ? call.at<int>(o_prior) : nullptr;
-    PItem* d_items = call.at<PItem>(o_items);
+    ThTile* d_items = call.at<ThTile>(o_items);
     hipStream_t st = call.st[0];
     const DevTable& dev_tab = host_table();
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_tab), &dev_tab, sizeof dev_tab, 0, hipMemcpyHostToDevice, st));   // the same bytes every call
@@ -493,7 +492,7 @@ extern "C" int th_pack_sidechains(int device, const double* backbone, const int8
     HIP_TRY(hipMemcpyAsync(d_soff, struct_offsets, (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_coff, cand_off.data(), (nr + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     if (ncand) HIP_TRY(hipMemcpyAsync(d_cres, cand_res.data(), ncand * sizeof(int), hipMemcpyHostToDevice, st));
-    if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(PItem), hipMemcpyHostToDevice, st));
+    if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ThTile), hipMemcpyHostToDevice, st));
     HIP_TRY(call.mark(0));
     if (ncand) {
         hipLaunchKernelGGL(k_pack_candidates, dim3((unsigned)((ncand + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_bb, nb, d_type, d_coff, d_cres,

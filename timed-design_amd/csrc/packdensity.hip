@@ -116,10 +116,7 @@ extern "C" int th_packing_density(int device, const double* xyz, int64_t total, 
         TH_FAIL(TH_EINVAL, "th_packing_density: n_groups = %lld needs group, selected and residue_out", (long long)n_groups);
     if (total > INT_MAX - kTile || n_groups > INT_MAX)
         TH_FAIL(TH_EINVAL, "th_packing_density: %lld atoms / %lld residues in one call (limit 2^31 - 257)", (long long)total, (long long)n_groups);
-    if (offsets[0] != 0 || offsets[n_structures] != total)
-        TH_FAIL(TH_EINVAL, "th_packing_density: offsets must run from 0 to total = %lld", (long long)total);
-    for (int64_t s = 0; s < n_structures; ++s)
-        if (offsets[s + 1] < offsets[s]) TH_FAIL(TH_EINVAL, "th_packing_density: offsets[%lld] > offsets[%lld]", (long long)s, (long long)s + 1);
+    if (int rc = th_check_offsets("th_packing_density", "offsets", "total", offsets, n_structures, total)) return rc;
     std::vector<Span> spans;
     std::vector<Item> items;
     try {

@@ -52,17 +52,15 @@ constexpr int kTile = kAtoms * kWave;          // candidates per LDS tile = thre
 constexpr int kMaxPoints = 1024;
 constexpr long long kMaxTotal = 2147483647LL - 256;
 
-struct Item { int structure, tile; };          // atoms offsets[structure] + tile * kAtoms ... of that structure
-
 template <int SLOTS>
 __global__ void __launch_bounds__(kTile) k_sasa_points(const double* __restrict__ xyz, const double* __restrict__ radius, double probe,
-                                                       const long long* __restrict__ offsets, const Item* __restrict__ items,
+                                                       const long long* __restrict__ offsets, const ThTile* __restrict__ items,
                                                        const double* __restrict__ points, int n_points, int words,
                                                        int* __restrict__ exposed_out, unsigned long long* __restrict__ mask_out) {
     __shared__ __attribute__((aligned(16))) double cx[kTile], cy[kTile], cz[kTile], cr[kTile], crr[kTile];
     const int tid = threadIdx.x, lane = tid % kWave;
-    const Item it = items[blockIdx.x];
-    const long long begin = offsets[it.structure], end = offsets[it.structure + 1];
+    const ThTile it = items[blockIdx.x];                          // atoms offsets[range] + tile * kAtoms ... of that structure
+    const long long begin = offsets[it.range], end = offsets[it.range + 1];
     const int len = (int)(end - begin);
     const int a = it.tile * kAtoms + tid / kWave;                 // this wavefront's atom, structure-local
     const bool live = a < len;                                    // the same for all 64 lanes
@@ -75,7 +73,7 @@ __global__ void __launch_bounds__(kTile) k_sasa_points(const double* __restrict_
         z = p[2];
         R = radius[begin + a] + probe;
     }
-    const bool valid = __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && __builtin_isfinite(R) && R > 0.0;
+    const bool valid = finite3(x, y, z) && __builtin_isfinite(R) && R > 0.0;
     int count = 0;
     for (int k0 = 0; k0 < n_points; k0 += kWave * SLOTS) {        // a round: points k0 + lane + 64 * s
         double px[SLOTS], py[SLOTS], pz[SLOTS];
@@ -99,6 +97,8 @@ __global__ void __launch_bounds__(kTile) k_sasa_points(const double* __restrict_
                 qy = p[1];
                 qz = p[2];
                 qr = radius[begin + j] + probe;
+                // finite3(qx, qy, qz) spelled out: through the function hipcc folds the chain into selects before it inlines, and
+                // this loop's code and registers change (2 SGPRs at SLOTS 2 and 4) — not in a change that promises the same kernel
                 if (!(__builtin_isfinite(qx) && __builtin_isfinite(qy) && __builtin_isfinite(qz) && __builtin_isfinite(qr) && qr > 0.0)) qr = nan;
             }
             if (!__syncthreads_or(testing)) break;                // the previous tile is no longer read; nobody has anything left to test
@@ -210,21 +210,13 @@ extern "C" int th_sasa(int device, const double* xyz, const double* radius, int6
         if (kernel_ms_out) kernel_ms_out[0] = kernel_ms_out[1] = 0.0;
         return TH_OK;
     }
-    std::vector<Item> items;
-    try {
-        items.reserve((size_t)(total / kAtoms + (n_structures < total ? n_structures : total)));     // a structure with atoms has one partial item at most
-        for (int64_t s = 0; s < n_structures; ++s) {
-            const int64_t tiles = (offsets[s + 1] - offsets[s] + kAtoms - 1) / kAtoms;
-            for (int64_t t = 0; t < tiles; ++t) items.push_back(Item{(int)s, (int)t});
-        }
-    } catch (const std::bad_alloc&) {
-        TH_FAIL(TH_ENOMEM, "th_sasa: out of host memory for the work items of %lld atoms", (long long)total);
-    }
+    std::vector<ThTile> items;
+    if (int rc = th_tile_items("th_sasa", "atoms", offsets, n_structures, kAtoms, items)) return rc;
 
     const size_t n = (size_t)total, ns = (size_t)n_structures, words = ((size_t)n_points + 63) / 64;
     ThLayout lay;
     const size_t o_xyz = lay.take(n * 3 * sizeof(double)), o_radius = lay.take(n * sizeof(double));
-    const size_t o_offsets = lay.take((ns + 1) * sizeof(int64_t)), o_items = lay.take(items.size() * sizeof(Item));
+    const size_t o_offsets = lay.take((ns + 1) * sizeof(int64_t)), o_items = lay.take(items.size() * sizeof(ThTile));
     const size_t o_points = lay.take((size_t)n_points * 3 * sizeof(double)), o_exposed = lay.take(n * sizeof(int32_t));
     const size_t o_mask = lay.take(mask_out ? n * words * sizeof(uint64_t) : 0), o_struct = lay.take(ns * 3 * sizeof(int64_t));
     ThCall call;
@@ -233,12 +225,12 @@ extern "C" int th_sasa(int device, const double* xyz, const double* radius, int6
     long long *d_offsets = call.at<long long>(o_offsets), *d_struct = call.at<long long>(o_struct);
     int* d_exposed = call.at<int>(o_exposed);
     unsigned long long* d_mask = mask_out ? call.at<unsigned long long>(o_mask) : nullptr;
-    Item* d_items = call.at<Item>(o_items);
+    ThTile* d_items = call.at<ThTile>(o_items);
     hipStream_t st = call.st[0];
     HIP_TRY(hipMemcpyAsync(d_xyz, xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_radius, radius, n * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ThTile), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_points, points, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     const dim3 grid((unsigned)items.size()), block(kTile);
     HIP_TRY(call.mark(0));

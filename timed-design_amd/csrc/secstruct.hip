@@ -58,10 +58,6 @@ constexpr int kPerBlock = kTile / kWave;       // structures per workgroup of k_
 constexpr unsigned char kValid = 1, kConn = 2, kHasH = 4;      // the bits of meta[]
 constexpr double kCos70 = 0.3420201433256688;
 
-struct Item { int structure, tile; };          // residues offsets[structure] + tile * kTile ... of that structure
-
-__device__ inline bool finite3(const double* p) { return __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]); }
-
 __device__ inline double dist(const double* a, double bx, double by, double bz) {
     const double dx = a[0] - bx, dy = a[1] - by, dz = a[2] - bz;
     return sqrt((dx * dx + dy * dy) + dz * dz);
@@ -69,9 +65,9 @@ __device__ inline double dist(const double* a, double bx, double by, double bz) 
 
 __global__ void __launch_bounds__(kTile) k_ss_prepare(const double* __restrict__ backbone, const int* __restrict__ chain,
                                                       const unsigned char* __restrict__ no_h, const long long* __restrict__ offsets,
-                                                      const Item* __restrict__ items, double* __restrict__ hxyz, unsigned char* __restrict__ meta) {
-    const Item it = items[blockIdx.x];
-    const long long begin = offsets[it.structure], end = offsets[it.structure + 1];
+                                                      const ThTile* __restrict__ items, double* __restrict__ hxyz, unsigned char* __restrict__ meta) {
+    const ThTile it = items[blockIdx.x];
+    const long long begin = offsets[it.range], end = offsets[it.range + 1];
     const long long i = begin + (long long)it.tile * kTile + threadIdx.x;
     if (i >= end) return;
     auto valid = [&](long long r) {
@@ -109,12 +105,12 @@ __global__ void __launch_bounds__(kTile) k_ss_prepare(const double* __restrict__
 
 __global__ void __launch_bounds__(kTile) k_ss_hbonds(const double* __restrict__ backbone, const double* __restrict__ hxyz,
                                                      const unsigned char* __restrict__ meta, const long long* __restrict__ offsets,
-                                                     const long long* __restrict__ word_start, const Item* __restrict__ items,
+                                                     const long long* __restrict__ word_start, const ThTile* __restrict__ items,
                                                      unsigned long long* __restrict__ bits) {
     __shared__ __attribute__((aligned(16))) double nx[kTile], ny[kTile], nz[kTile], hx[kTile], hy[kTile], hz[kTile], ax[kTile], ay[kTile], az[kTile];
     const int tid = threadIdx.x;
-    const Item it = items[blockIdx.x];
-    const long long begin = offsets[it.structure], end = offsets[it.structure + 1];
+    const ThTile it = items[blockIdx.x];
+    const long long begin = offsets[it.range], end = offsets[it.range + 1];
     const int len = (int)(end - begin), words = (len + kWave - 1) / kWave;
     const int a = it.tile * kTile + tid;       // this thread's acceptor, structure-local
     const bool live = a < len;
@@ -129,7 +125,7 @@ __global__ void __launch_bounds__(kTile) k_ss_hbonds(const double* __restrict__ 
             o[k] = p[9 + k];
         }
     }
-    unsigned long long* row = bits + word_start[it.structure] + (long long)a * words;       // dereferenced by live threads only
+    unsigned long long* row = bits + word_start[it.range] + (long long)a * words;       // dereferenced by live threads only
     for (int j0 = 0; j0 < len; j0 += kTile) {
         const int j = j0 + tid;
         const bool donor = j < len && (meta[begin + j] & kHasH);
@@ -207,14 +203,14 @@ struct Structure {                             // what k_ss_assign knows of the 
 
 __global__ void __launch_bounds__(kTile) k_ss_assign(const double* __restrict__ backbone, const unsigned char* __restrict__ meta,
                                                      const long long* __restrict__ offsets, const long long* __restrict__ word_start,
-                                                     const Item* __restrict__ items, const unsigned long long* __restrict__ bits,
+                                                     const ThTile* __restrict__ items, const unsigned long long* __restrict__ bits,
                                                      unsigned char* __restrict__ class_out, int* __restrict__ residue_out) {
-    const Item it = items[blockIdx.x];
-    const long long begin = offsets[it.structure], end = offsets[it.structure + 1];
+    const ThTile it = items[blockIdx.x];
+    const long long begin = offsets[it.range], end = offsets[it.range + 1];
     Structure s;
     s.len = (int)(end - begin);
     s.words = (s.len + kWave - 1) / kWave;
-    s.bits = bits + word_start[it.structure];
+    s.bits = bits + word_start[it.range];
     s.meta = meta + begin;
     const int i = it.tile * kTile + threadIdx.x;
     // Bonds donated, by the whole wavefront before any lane leaves: its 64 residues are the 64 bits of ONE word of every row.  Lane l
@@ -332,20 +328,19 @@ extern "C" int th_secondary_structure(int device, const double* backbone, const 
                 "th_secondary_structure: n_structures = %lld needs offsets and structure_out, total = %lld needs backbone, chain, no_h, "
                 "class_out and residue_out", (long long)n_structures, (long long)total);
     if (int rc = th_check_offsets("th_secondary_structure", "offsets", "total", offsets, n_structures, total)) return rc;
-    std::vector<Item> items;
+    std::vector<ThTile> items;                 // residues offsets[range] + tile * kTile ... of that structure
+    if (int rc = th_tile_items("th_secondary_structure", "residues", offsets, n_structures, kTile, items)) return rc;
     std::vector<long long> word_start;
     try {
         word_start.reserve((size_t)n_structures + 1);
         word_start.push_back(0);
         for (int64_t s = 0; s < n_structures; ++s) {
-            const int64_t len = offsets[s + 1] - offsets[s], tiles = (len + kTile - 1) / kTile;
-            for (int64_t t = 0; t < tiles; ++t) items.push_back(Item{(int)s, (int)t});
+            const int64_t len = offsets[s + 1] - offsets[s];
             word_start.push_back(word_start.back() + len * ((len + kWave - 1) / kWave));   // < 2^31 * 2^25
         }
     } catch (const std::bad_alloc&) {
         TH_FAIL(TH_ENOMEM, "th_secondary_structure: out of host memory for the work items of %lld residues", (long long)total);
     }
-    if (items.size() > (size_t)INT_MAX) TH_FAIL(TH_EINVAL, "th_secondary_structure: %zu work items in one call (limit 2^31 - 1)", items.size());
     if (word_start.back() > (long long)1 << 50)
         TH_FAIL(TH_ENOMEM, "th_secondary_structure: %lld words of hydrogen-bond bitmap (L * ceil(L / 64) per structure) fit no device", word_start.back());
 
@@ -353,7 +348,7 @@ extern "C" int th_secondary_structure(int device, const double* backbone, const 
     ThLayout lay;
     const size_t o_backbone = lay.take(n * 12 * sizeof(double)), o_chain = lay.take(n * sizeof(int32_t)), o_no_h = lay.take(n);
     const size_t o_offsets = lay.take((ns + 1) * sizeof(int64_t)), o_start = lay.take((ns + 1) * sizeof(long long));
-    const size_t o_items = lay.take(items.size() * sizeof(Item)), o_h = lay.take(n * 3 * sizeof(double)), o_meta = lay.take(n);
+    const size_t o_items = lay.take(items.size() * sizeof(ThTile)), o_h = lay.take(n * 3 * sizeof(double)), o_meta = lay.take(n);
     const size_t o_bits = lay.take(n_words * sizeof(uint64_t)), o_class = lay.take(n), o_res = lay.take(n * 6 * sizeof(int32_t));
     const size_t o_struct = lay.take(ns * 10 * sizeof(int64_t));
     ThCall call;
@@ -363,13 +358,13 @@ extern "C" int th_secondary_structure(int device, const double* backbone, const 
     unsigned char *d_no_h = call.at<unsigned char>(o_no_h), *d_meta = call.at<unsigned char>(o_meta), *d_class = call.at<unsigned char>(o_class);
     long long *d_offsets = call.at<long long>(o_offsets), *d_start = call.at<long long>(o_start), *d_struct = call.at<long long>(o_struct);
     unsigned long long* d_bits = call.at<unsigned long long>(o_bits);
-    Item* d_items = call.at<Item>(o_items);
+    ThTile* d_items = call.at<ThTile>(o_items);
     hipStream_t st = call.st[0];
     if (n) {
         HIP_TRY(hipMemcpyAsync(d_backbone, backbone, n * 12 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_chain, chain, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_no_h, no_h, n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ThTile), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_start, word_start.data(), (ns + 1) * sizeof(long long), hipMemcpyHostToDevice, st));

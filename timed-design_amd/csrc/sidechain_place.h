@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "device_math.h"
 #include "sidechain_table.h"
 
 // every float64 product and sum below is rounded separately, as the NumPy restatement's are
@@ -60,8 +61,6 @@ const DevTable& host_table() {
     }();
     return tab;
 }
-
-__device__ inline bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 
 // One group of kLanes lanes places one residue.  On entry lanes 0..2 hold N, CA, C in (px, py, pz) and every other lane NaN; `mine`
 // says that this lane (3 + j) owns atom j of the type, `row` is that atom's row (any row that exists otherwise) and `chi_k` the

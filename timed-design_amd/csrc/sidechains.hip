@@ -116,17 +116,15 @@ __global__ void __launch_bounds__(kBlock) k_build_sidechains(const double* __res
     }
 }
 
-struct Item { int structure, tile; };          // residues offsets[structure] + tile * kTileRes ... of that structure
-
 __global__ void __launch_bounds__(kTile) k_sidechain_clashes(const double* __restrict__ backbone, int nb, const double* __restrict__ sc_xyz,
                                                              const signed char* __restrict__ res_type, const int* __restrict__ chain_id,
-                                                             const long long* __restrict__ offsets, const Item* __restrict__ items,
+                                                             const long long* __restrict__ offsets, const ThTile* __restrict__ items,
                                                              double threshold, int* __restrict__ res_count) {
     __shared__ double jx[kTile], jy[kTile], jz[kTile];
     __shared__ int jmeta[kTile], jchain[kTile], cnt_sc[kTile], cnt_bb[kTile];
     const int tid = threadIdx.x;
-    const Item it = items[blockIdx.x];
-    const long long begin = offsets[it.structure], end = offsets[it.structure + 1];
+    const ThTile it = items[blockIdx.x];       // residues offsets[range] + tile * kTileRes ... of that structure
+    const long long begin = offsets[it.range], end = offsets[it.range + 1];
     const int len = (int)(end - begin);
     const int ri = it.tile * kTileRes + tid / kScMaxAtoms, slot = tid % kScMaxAtoms;
     const bool live = tid < kTileRes * kScMaxAtoms && ri < len;
@@ -291,17 +289,9 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
         if (out_struct_pairs) std::memset(out_struct_pairs, 0, (size_t)n_struct * sizeof(int64_t));
         return TH_OK;
     }
-    std::vector<Item> items;
-    if (want_clashes) {
-        try {
-            for (int64_t s = 0; s < n_struct; ++s) {
-                const int64_t tiles = (struct_offsets[s + 1] - struct_offsets[s] + kTileRes - 1) / kTileRes;
-                for (int64_t t = 0; t < tiles; ++t) items.push_back(Item{(int)s, (int)t});
-            }
-        } catch (const std::bad_alloc&) {
-            TH_FAIL(TH_ENOMEM, "th_build_sidechains: out of host memory for the work items of %lld residues", (long long)n_res);
-        }
-    }
+    std::vector<ThTile> items;
+    if (want_clashes)
+        if (int rc = th_tile_items("th_build_sidechains", "residues", struct_offsets, n_struct, kTileRes, items)) return rc;
 
     const int nb = (flags & TH_SC_BACKBONE_O) ? 4 : 3;
     const size_t nr = (size_t)n_res, ns = (size_t)n_struct, nn = native ? (size_t)native_total : 0;
@@ -312,7 +302,7 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
     const size_t o_noff = lay.take(native ? (nr + 1) * sizeof(int64_t) : 0), o_ntype = lay.take(native ? nr : 0);
     const size_t o_xyz = lay.take(nr * kScMaxAtoms * 3 * sizeof(double)), o_built = lay.take(nr * sizeof(int32_t));
     const size_t o_matched = lay.take(native ? nr * sizeof(int32_t) : 0), o_sq = lay.take(native ? nr * sizeof(double) : 0);
-    const size_t o_items = lay.take(items.size() * sizeof(Item)), o_count = lay.take(want_clashes ? nr * 2 * sizeof(int32_t) : 0);
+    const size_t o_items = lay.take(items.size() * sizeof(ThTile)), o_count = lay.take(want_clashes ? nr * 2 * sizeof(int32_t) : 0);
     const size_t o_clashes = lay.take(want_clashes ? nr * sizeof(int32_t) : 0), o_pairs = lay.take(want_clashes ? ns * sizeof(int64_t) : 0);
     ThCall call;
     if (int rc = call.open("th_build_sidechains", device, lay.bytes, kernel_ms ? 2 : 0)) return rc;
@@ -326,7 +316,7 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
     int *d_built = call.at<int>(o_built), *d_count = call.at<int>(o_count), *d_clashes = call.at<int>(o_clashes);
     int* d_matched = native ? call.at<int>(o_matched) : nullptr;
     double* d_sq = native ? call.at<double>(o_sq) : nullptr;
-    Item* d_items = call.at<Item>(o_items);
+    ThTile* d_items = call.at<ThTile>(o_items);
     hipStream_t st = call.st[0];
     const DevTable& tab = host_table();
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_tab), &tab, sizeof tab, 0, hipMemcpyHostToDevice, st));       // the same bytes every call
@@ -343,7 +333,7 @@ extern "C" int th_build_sidechains(int device, const double* backbone, const int
         HIP_TRY(hipMemcpyAsync(d_noff, native_res_offsets, (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_ntype, native_type, nr, hipMemcpyHostToDevice, st));
     }
-    if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
+    if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ThTile), hipMemcpyHostToDevice, st));
     HIP_TRY(call.mark(0));
     hipLaunchKernelGGL(k_build_sidechains, dim3((unsigned)((nr + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_bb, nb, d_type, d_chi,
                        (long long)n_res, d_nxyz, d_nname, d_noff, d_ntype, d_xyz, d_built, d_matched, d_sq);

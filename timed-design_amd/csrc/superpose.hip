@@ -54,56 +54,20 @@ __global__ void __launch_bounds__(kBlock) k_superpose(const double* __restrict__
 
     int n_kept = n_valid, cycles_run = 0;
     double fit_all = nan, rms_kept = nan, sq_all = 0.0;
-    double cm[3] = {0.0, 0.0, 0.0}, cr[3] = {0.0, 0.0, 0.0};
-    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    Fit fit;
     while (n_valid > 0) {
-        // centroids of the kept set
-        double sm[3] = {0.0, 0.0, 0.0}, sr[3] = {0.0, 0.0, 0.0};
-        for (long long i = lane; i < n; i += kWave)
-            if (kept[i]) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    sm[a] += mob[3 * i + a];
-                    sr[a] += ref[3 * i + a];
-                }
-            }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            cm[a] = wave_sum(sm[a]) / (double)n_kept;
-            cr[a] = wave_sum(sr[a]) / (double)n_kept;
-        }
-        // cross-covariance of the centred coordinates (two-pass)
-        double S[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-        for (long long i = lane; i < n; i += kWave)
-            if (kept[i]) {
-                double a[3], b[3];
-#pragma unroll
-                for (int x = 0; x < 3; ++x) {
-                    a[x] = mob[3 * i + x] - cm[x];
-                    b[x] = ref[3 * i + x] - cr[x];
-                }
-#pragma unroll
-                for (int x = 0; x < 3; ++x)
-#pragma unroll
-                    for (int y = 0; y < 3; ++y) S[x][y] += a[x] * b[y];
-            }
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-#pragma unroll
-            for (int y = 0; y < 3; ++y) S[x][y] = wave_sum(S[x][y]);
-        horn_rotation(S, R);
+        // the fit of the kept set
+        wave_fit(ref, mob, [&](auto visit) {
+            for (long long i = lane; i < n; i += kWave)
+                if (kept[i]) visit(i);
+        }, (double)n_kept, fit);
         // distances of every valid position under this fit
         double sq_kept = 0.0;
         sq_all = 0.0;
         for (long long i = lane; i < n; i += kWave) {
-            const double mx = mob[3 * i], my = mob[3 * i + 1], mz = mob[3 * i + 2];
-            const double rx = ref[3 * i], ry = ref[3 * i + 1], rz = ref[3 * i + 2];
-            if (!(finite3(mx, my, mz) && finite3(rx, ry, rz))) continue;
-            const double ax = mx - cm[0], ay = my - cm[1], az = mz - cm[2];
-            const double dx = (((R[0] * ax + R[1] * ay) + R[2] * az) + cr[0]) - rx;
-            const double dy = (((R[3] * ax + R[4] * ay) + R[5] * az) + cr[1]) - ry;
-            const double dz = (((R[6] * ax + R[7] * ay) + R[8] * az) + cr[2]) - rz;
-            const double d = sqrt((dx * dx + dy * dy) + dz * dz);
+            const double m[3] = {mob[3 * i], mob[3 * i + 1], mob[3 * i + 2]}, r[3] = {ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]};
+            if (!(finite3(m[0], m[1], m[2]) && finite3(r[0], r[1], r[2]))) continue;   // all six loads are issued before the first test
+            const double d = distance(fit, r, m);
             dist[i] = d;
             sq_all += d * d;
             if (kept[i]) sq_kept += d * d;
@@ -145,16 +109,7 @@ __global__ void __launch_bounds__(kBlock) k_superpose(const double* __restrict__
     count[2] = cycles_run;
 #pragma unroll
     for (int k = 0; k < 4; ++k) count[3 + k] = within[k];
-    if (transform_out) {                                               // moved = R mob + t, t = cr - R cm; the identity when nothing is valid
-        double* t = transform_out + 12 * pair;
-#pragma unroll
-        for (int x = 0; x < 3; ++x) {
-            t[4 * x] = R[3 * x];
-            t[4 * x + 1] = R[3 * x + 1];
-            t[4 * x + 2] = R[3 * x + 2];
-            t[4 * x + 3] = cr[x] - ((R[3 * x] * cm[0] + R[3 * x + 1] * cm[1]) + R[3 * x + 2] * cm[2]);
-        }
-    }
+    if (transform_out) store(fit, transform_out + 12 * pair);          // the identity when nothing is valid
 }
 
 }  // namespace

@@ -21,6 +21,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
+#include <new>
 #include <vector>
 
 #include "common.h"
@@ -41,16 +42,6 @@ struct TmPair {                                   // one per pair, and one more 
     double d0;
 };
 
-// d of compacted position c under moved = R (mob - cm) + cr
-__device__ inline double tm_dist(const double* __restrict__ ref, const double* __restrict__ mob, int c, const double (&cm)[3],
-                                 const double (&cr)[3], const double (&R)[9]) {
-    const double ax = mob[3 * c] - cm[0], ay = mob[3 * c + 1] - cm[1], az = mob[3 * c + 2] - cm[2];
-    const double dx = (((R[0] * ax + R[1] * ay) + R[2] * az) + cr[0]) - ref[3 * c];
-    const double dy = (((R[3] * ax + R[4] * ay) + R[5] * az) + cr[1]) - ref[3 * c + 1];
-    const double dz = (((R[6] * ax + R[7] * ay) + R[8] * az) + cr[2]) - ref[3 * c + 2];
-    return sqrt((dx * dx + dy * dy) + dz * dz);
-}
-
 // (W, s) of seed k of a pair with m valid positions: the window lengths m, m div 2, ... >= 4, every start of each
 __device__ inline void tm_window(int m, long long k, int& W, int& s) {
     W = m;
@@ -65,7 +56,7 @@ __device__ inline void tm_window(int m, long long k, int& W, int& s) {
 // counts its fits and, with kKeep, leaves the superposition of the first round that reached that score.
 template <bool kKeep>
 __device__ inline double tm_seed(const double* __restrict__ ref, const double* __restrict__ mob, int m, int W, int s, double d0,
-                                 double d_search, double L, int rounds, int lane, int& fits, double (&bcm)[3], double (&bcr)[3], double (&bR)[9]) {
+                                 double d_search, double L, int rounds, int lane, int& fits, Fit& best_fit) {
     const int nb = lane < m ? (m - lane + kWave - 1) / kWave : 0;      // positions this lane owns, <= 64
     const int need = m < 3 ? m : 3;
     unsigned long long cur = 0;
@@ -77,49 +68,19 @@ __device__ inline double tm_seed(const double* __restrict__ ref, const double* _
     fits = 0;
     for (int r = 0;; ++r) {
         const double count = (double)wave_sum((int)__popcll(cur));
-        double sm[3] = {0.0, 0.0, 0.0}, sr[3] = {0.0, 0.0, 0.0}, cm[3], cr[3];
-        for (int b = 0; b < nb; ++b)
-            if ((cur >> b) & 1) {
-                const int c = lane + kWave * b;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    sm[a] += mob[3 * c + a];
-                    sr[a] += ref[3 * c + a];
-                }
-            }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            cm[a] = wave_sum(sm[a]) / count;
-            cr[a] = wave_sum(sr[a]) / count;
-        }
-        double S[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-        for (int b = 0; b < nb; ++b)
-            if ((cur >> b) & 1) {
-                const int c = lane + kWave * b;
-                double a[3], e[3];
-#pragma unroll
-                for (int x = 0; x < 3; ++x) {
-                    a[x] = mob[3 * c + x] - cm[x];
-                    e[x] = ref[3 * c + x] - cr[x];
-                }
-#pragma unroll
-                for (int x = 0; x < 3; ++x)
-#pragma unroll
-                    for (int y = 0; y < 3; ++y) S[x][y] += a[x] * e[y];
-            }
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-#pragma unroll
-            for (int y = 0; y < 3; ++y) S[x][y] = wave_sum(S[x][y]);
-        double R[9];
-        horn_rotation(S, R);
+        Fit fit;
+        wave_fit(ref, mob, [&](auto visit) {
+            for (int b = 0; b < nb; ++b)
+                if ((cur >> b) & 1) visit(lane + kWave * b);
+        }, count, fit);
         ++fits;
         // the score of this superposition over every valid position, and the next set in the same pass
         double cut = r == 0 ? d_search - 1.0 : d_search + 1.0;
         double sum = 0.0;
         unsigned long long next = 0;
         for (int b = 0; b < nb; ++b) {
-            const double d = tm_dist(ref, mob, lane + kWave * b, cm, cr, R);
+            const int c = lane + kWave * b;
+            const double d = distance(fit, ref + 3 * c, mob + 3 * c);
             const double q = d / d0;
             sum += 1.0 / (1.0 + q * q);
             if (d < cut) next |= 1ull << b;
@@ -127,23 +88,17 @@ __device__ inline double tm_seed(const double* __restrict__ ref, const double* _
         const double score = wave_sum(sum) / L;
         if (score > best) {
             best = score;
-            if (kKeep) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    bcm[a] = cm[a];
-                    bcr[a] = cr[a];
-                }
-#pragma unroll
-                for (int a = 0; a < 9; ++a) bR[a] = R[a];
-            }
+            if (kKeep) best_fit = fit;
         }
         if (r >= rounds) break;
         int chosen = wave_sum((int)__popcll(next));
         for (int widened = 0; chosen < need && widened < kWidenings; ++widened) {      // uniform: both are the same in every lane
             cut += 0.5;
             next = 0;
-            for (int b = 0; b < nb; ++b)
-                if (tm_dist(ref, mob, lane + kWave * b, cm, cr, R) < cut) next |= 1ull << b;
+            for (int b = 0; b < nb; ++b) {
+                const int c = lane + kWave * b;
+                if (distance(fit, ref + 3 * c, mob + 3 * c) < cut) next |= 1ull << b;
+            }
             chosen = wave_sum((int)__popcll(next));
         }
         if (chosen < need || __all(next == cur)) break;
@@ -171,7 +126,8 @@ __global__ void __launch_bounds__(kBlock) k_tm_seeds(const double* __restrict__ 
     int W, s, fits;
     tm_window((int)p.m, mine - p.slo, W, s);
     const double d_search = fmin(fmax(p.d0, 4.5), 8.0);
-    double cm[3], cr[3], R[9], best;
+    Fit unused;                                                        // tm_seed<false> keeps none
+    double best;
 #if TH_KNOCKOUTS
     if (kStage) {
         extern __shared__ double staged[];
@@ -186,7 +142,7 @@ __global__ void __launch_bounds__(kBlock) k_tm_seeds(const double* __restrict__ 
         __syncthreads();
         if (g >= n_seeds) return;
         if (lo == first_pair) {
-            best = tm_seed<false>(staged, staged + 3 * stage_positions, (int)p.m, W, s, p.d0, d_search, (double)p.L, rounds, lane, fits, cm, cr, R);
+            best = tm_seed<false>(staged, staged + 3 * stage_positions, (int)p.m, W, s, p.d0, d_search, (double)p.L, rounds, lane, fits, unused);
             if (lane == 0) {
                 seed_score[g] = best;
                 seed_fits[g] = fits;
@@ -195,7 +151,7 @@ __global__ void __launch_bounds__(kBlock) k_tm_seeds(const double* __restrict__ 
         }
     }
 #endif
-    best = tm_seed<false>(cref + 3 * p.clo, cmob + 3 * p.clo, (int)p.m, W, s, p.d0, d_search, (double)p.L, rounds, lane, fits, cm, cr, R);
+    best = tm_seed<false>(cref + 3 * p.clo, cmob + 3 * p.clo, (int)p.m, W, s, p.d0, d_search, (double)p.L, rounds, lane, fits, unused);
     if (lane == 0) {
         seed_score[g] = best;
         seed_fits[g] = fits;
@@ -232,8 +188,7 @@ __global__ void __launch_bounds__(kBlock) k_tm_best(const double* __restrict__ c
     }
     fits_all = wave_sum(fits_all);
     const double nan = __builtin_nan("");
-    double cm[3] = {0.0, 0.0, 0.0}, cr[3] = {0.0, 0.0, 0.0};
-    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    Fit fit;
     double tm = nan;
     const double* ref = cref + 3 * p.clo;
     const double* mob = cmob + 3 * p.clo;
@@ -241,12 +196,12 @@ __global__ void __launch_bounds__(kBlock) k_tm_best(const double* __restrict__ c
     if (found) {
         int W, s, fits;
         tm_window((int)p.m, at, W, s);
-        tm = tm_seed<true>(ref, mob, (int)p.m, W, s, p.d0, fmin(fmax(p.d0, 4.5), 8.0), (double)p.L, rounds, lane, fits, cm, cr, R);
+        tm = tm_seed<true>(ref, mob, (int)p.m, W, s, p.d0, fmin(fmax(p.d0, 4.5), 8.0), (double)p.L, rounds, lane, fits, fit);
     }
     if (dist_out)
         for (long long i = lane; i < p.n; i += kWave) {
             const int c = cidx[p.lo + i];                              // the compacted index of position i, -1 at an invalid one
-            dist_out[p.lo + i] = found && c >= 0 ? tm_dist(ref, mob, c, cm, cr, R) : nan;
+            dist_out[p.lo + i] = found && c >= 0 ? distance(fit, ref + 3 * c, mob + 3 * c) : nan;
         }
     if (lane != 0) return;
     tm_out[2 * pair] = tm;
@@ -256,16 +211,7 @@ __global__ void __launch_bounds__(kBlock) k_tm_best(const double* __restrict__ c
     count[1] = p.L;
     count[2] = n_seeds;
     count[3] = fits_all;
-    if (transform_out) {                                               // moved = R mob + t, t = cr - R cm; the identity when nothing is valid
-        double* t = transform_out + 12 * pair;
-#pragma unroll
-        for (int x = 0; x < 3; ++x) {
-            t[4 * x] = R[3 * x];
-            t[4 * x + 1] = R[3 * x + 1];
-            t[4 * x + 2] = R[3 * x + 2];
-            t[4 * x + 3] = cr[x] - ((R[3 * x] * cm[0] + R[3 * x + 1] * cm[1]) + R[3 * x + 2] * cm[2]);
-        }
-    }
+    if (transform_out) store(fit, transform_out + 12 * pair);          // the identity when nothing is valid
 }
 
 long long tm_seed_count(long long m) {
@@ -311,34 +257,40 @@ extern "C" int th_tmscore(int device, const double* ref_xyz, const double* mob_x
 
     // the valid positions of every pair, compacted in index order; a pair's seeds follow from their number
     const size_t n = (size_t)total, np = (size_t)n_pairs;
-    std::vector<TmPair> pairs(np + 1);
-    std::vector<int> cidx(n);
+    std::vector<TmPair> pairs;
+    std::vector<int> cidx;
     std::vector<double> cref, cmob;
-    cref.reserve(3 * n);
-    cmob.reserve(3 * n);
     long long n_seeds = 0;
-    for (size_t p = 0; p < np; ++p) {
-        TmPair& q = pairs[p];
-        q.lo = offsets[p];
-        q.n = offsets[p + 1] - offsets[p];
-        q.clo = (long long)(cref.size() / 3);
-        for (long long i = q.lo; i < q.lo + q.n; ++i) {
-            const double* r = ref_xyz + 3 * i;
-            const double* m = mob_xyz + 3 * i;
-            const bool ok = std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(m[2]);
-            cidx[(size_t)i] = ok ? (int)(cref.size() / 3 - (size_t)q.clo) : -1;
-            if (ok) {
-                cref.insert(cref.end(), r, r + 3);
-                cmob.insert(cmob.end(), m, m + 3);
+    try {
+        pairs.resize(np + 1);
+        cidx.resize(n);
+        cref.reserve(3 * n);
+        cmob.reserve(3 * n);
+        for (size_t p = 0; p < np; ++p) {
+            TmPair& q = pairs[p];
+            q.lo = offsets[p];
+            q.n = offsets[p + 1] - offsets[p];
+            q.clo = (long long)(cref.size() / 3);
+            for (long long i = q.lo; i < q.lo + q.n; ++i) {
+                const double* r = ref_xyz + 3 * i;
+                const double* m = mob_xyz + 3 * i;
+                const bool ok = finite3(r) && finite3(m);
+                cidx[(size_t)i] = ok ? (int)(cref.size() / 3 - (size_t)q.clo) : -1;
+                if (ok) {
+                    cref.insert(cref.end(), r, r + 3);
+                    cmob.insert(cmob.end(), m, m + 3);
+                }
             }
+            q.m = (long long)(cref.size() / 3) - q.clo;
+            q.slo = n_seeds;
+            q.L = norm_len ? norm_len[p] : q.n;
+            q.d0 = th_tm_d0(q.L);
+            n_seeds += tm_seed_count(q.m);
         }
-        q.m = (long long)(cref.size() / 3) - q.clo;
-        q.slo = n_seeds;
-        q.L = norm_len ? norm_len[p] : q.n;
-        q.d0 = th_tm_d0(q.L);
-        n_seeds += tm_seed_count(q.m);
+        pairs[np] = TmPair{total, 0, (long long)(cref.size() / 3), 0, n_seeds, 0, 0.5};
+    } catch (const std::bad_alloc&) {
+        TH_FAIL(TH_ENOMEM, "th_tmscore: out of host memory for the valid positions of %lld positions", (long long)total);
     }
-    pairs[np] = TmPair{total, 0, (long long)(cref.size() / 3), 0, n_seeds, 0, 0.5};
     if (n_seeds > INT_MAX)
         TH_FAIL(TH_EINVAL, "th_tmscore: %lld seeds in one call (limit 2^31 - 1): submit fewer pairs at once", n_seeds);
     const size_t nc = cref.size() / 3, ns = (size_t)n_seeds;
