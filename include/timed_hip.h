@@ -97,6 +97,16 @@ int th_conv_gl_row_tiles(int64_t rows);
  * instantiation, one name per line. */
 int th_conv_pw_pick(int Cin, int Cout, int pool, int in_cs, int in_coff, int out_blk, int relu_chain, char* buf, size_t len);
 int th_conv_pw_kernels(char* buf, size_t len);
+/* The planner's rule for the two brick kernels (k_conv_n16, k_conv_mfma), for tests.  th_conv_brick_pick writes the plan label of a
+ * kd x kh x kw convolution Cin -> Cout with this stride and dilation, Keras 'same' (same != 0) or 'valid' padding, on a D x H x W volume
+ * with a fused 2x2x2 pool (0 none, 1 max, 2 avg; one pool value, as the planner tries it), read from an input view of voxel stride
+ * in_cs floats (<= 0: a dense tensor) at channel offset in_coff:
+ * "conv_mfma<w8,4x2,nt2,ci16,stream,pool1> FB1 ZB6/12 rows96 lds150K [k_conv_mfma<8,4,2,2,16,2,1,0>]", two such labels joined by
+ * " x2 + " when the last block of output channels runs on a narrower instantiation, the empty string when neither kernel plans the
+ * layer.  Default knobs.  th_conv_brick_kernels lists every compiled instantiation of both kernels, one name per line.  Host code. */
+int th_conv_brick_pick(int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, const int stride[3], const int dilation[3],
+                       int same, int pool, int in_cs, int in_coff, char* buf, size_t len);
+int th_conv_brick_kernels(char* buf, size_t len);
 
 /* ---- forward: replaces frame_model.predict(X_batch) — predict.py:142 --------------------- */
 /* host frames [n,D,H,W,C] of `dtype` -> host probs_out [n,n_classes] fp32 (rows sum to 1) */

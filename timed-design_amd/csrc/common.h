@@ -228,6 +228,14 @@ void conv_n16_pack_weights(const ConvN16Plan& p, int Cin, int Cout, const float*
 int launch_conv_n16(hipStream_t s, int64_t n, const ConvN16Plan& p, TView in, TView out, ConvGeom g, int Cin, int Cout, const float* wpk,
                     const float* bias, PreOp pre, PostOps post);
 
+// ---- the two brick kernels together: the planner's rule and what th_conv_brick_pick / th_conv_brick_kernels export (planner.hip) ----
+// one pool value: the 16-wide kernel's variants, then the 32-wide kernel's configurations.  0: neither plans the layer, 1: `np`, 2: `mp`
+int conv_brick_plan(const TView& in, const TView& out_conv, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn,
+                    ConvN16Plan* np, ConvMfmaPlan* mp);
+std::string conv_mfma_tailed_label(const ConvMfmaPlan& main, const ConvMfmaPlan& tail);   // `main` with all its Cout blocks, as planned
+void conv_mfma_kernel_names(std::string* out);   // appends every instantiation's name and a newline
+void conv_n16_kernel_names(std::string* out);
+
 // ---- Cook-Toom / Winograd convolution for 3x3x3 'same' layers on 5^3 volumes (conv_wino.hip) ----
 struct ConvWinoPlan {
     int P = 9;                                   // evaluation points per in-plane axis: 9 = F(3,3)+F(2,3) (default), 7 = F(5,3)

@@ -687,6 +687,13 @@ const MfmaGeo kMfmaGeo[] = {
     {kS4N64, 0, 7, k_conv_mfma<4, 4, 2, 2, 16, 2, 0, 7>},     // 5^3, 64-column tail block
 };
 
+// the full instantiation, as rocprofv3 prints it: what the plan label and th_conv_brick_kernels name
+std::string mfma_kernel_name(const CfgDesc& c, int pool, int geo) {
+    char buf[64];
+    snprintf(buf, sizeof buf, "k_conv_mfma<%d,%d,%d,%d,%d,%d,%d,%d>", c.WAVES, c.TM, c.TN, c.NT, c.CI, c.BRES, pool, geo);
+    return buf;
+}
+
 }  // namespace
 
 static bool plan_with_cfg(int cfg, size_t lds_limit, bool whole_frames_only, const TView& in, const TView& oc,
@@ -771,13 +778,24 @@ static bool plan_with_cfg(int cfg, size_t lds_limit, bool whole_frames_only, con
     if (g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && p->Hp == p->Wp && p->CS == 20)
         for (const MfmaGeo& ge : kMfmaGeo)
             if (ge.cfg == cfg && ge.pool == pool && ge.geo == p->Hp) p->geo = ge.geo;
-    char buf[224], geo[16];
-    snprintf(geo, sizeof geo, ",%d", p->geo);   // the full instantiation, as rocprofv3 prints it
-    snprintf(buf, sizeof buf, "conv_mfma<w%d,%dx%d,nt%d,ci%d,%s,pool%d> FB%d ZB%d/%d rows%d lds%zuK [k_conv_mfma<%d,%d,%d,%d,%d,%d,%d%s>]",
+    char buf[224];
+    snprintf(buf, sizeof buf, "conv_mfma<w%d,%dx%d,nt%d,ci%d,%s,pool%d> FB%d ZB%d/%d rows%d lds%zuK [%s]",
              c.WAVES, c.TM, c.TN, c.NT, c.CI, c.BRES == 2 ? "stream" : "res", pool, FB, ZB, p->Dc, p->rows_pf,
-             p->lds_bytes / 1024, c.WAVES, c.TM, c.TN, c.NT, c.CI, c.BRES, pool, geo);
+             p->lds_bytes / 1024, mfma_kernel_name(c, pool, p->geo).c_str());
     p->label = buf;
     return true;
+}
+
+// every compiled instantiation, one name per line: kCfgs x pool, then kMfmaGeo
+void conv_mfma_kernel_names(std::string* out) {
+    for (const CfgDesc& c : kCfgs)
+        for (int pool = 0; pool < 3; ++pool) *out += mfma_kernel_name(c, pool, 0) + "\n";
+    for (const MfmaGeo& ge : kMfmaGeo) *out += mfma_kernel_name(kCfgs[ge.cfg], ge.pool, ge.geo) + "\n";
+}
+
+// the label of a layer whose last Cout block runs on `tail` (conv_mfma_plan_tail); `main` as conv_mfma_plan left it
+std::string conv_mfma_tailed_label(const ConvMfmaPlan& main, const ConvMfmaPlan& tail) {
+    return main.label + " x" + std::to_string(main.nnb - 1) + " + " + tail.label;
 }
 
 

@@ -488,6 +488,13 @@ const N16Geo kN16Geo[] = {
 };
 constexpr int kCS = 20;   // floats per staged voxel: 16 channels + the three tables (see the kernel)
 
+// the full instantiation, as rocprofv3 prints it: what the plan label and th_conv_brick_kernels name (variant 2: XC = 4)
+std::string n16_kernel_name(int variant, int pool, int geo) {
+    char buf[64];
+    snprintf(buf, sizeof buf, "k_conv_n16<%d,%d,%d,%d,%d>", kN16[variant].WAVES, kN16[variant].TM, pool, variant == 2 ? 4 : 0, geo);
+    return buf;
+}
+
 bool plan_n16(int variant, size_t lds_limit, const TView& in, const TView& oc, int Cin, int pool, const ThKnobs& kn, ConvN16Plan* p) {
     const N16Cfg& c = kN16[variant];
     p->knobs = &kn;
@@ -521,11 +528,10 @@ bool plan_n16(int variant, size_t lds_limit, const TView& in, const TView& oc, i
     if (pool == 0 && p->Hp == p->Wp)
         for (const N16Geo& ge : kN16Geo)
             if (ge.variant == variant && ge.geo == p->Hp) p->geo = ge.geo;
-    char buf[224], geo[24];
-    snprintf(geo, sizeof geo, "%s,%d", xc ? "" : ",0", p->geo);   // the full instantiation, as rocprofv3 prints it
-    snprintf(buf, sizeof buf, "conv_n16<w%d,tm%d,pool%d%s> FB%d ZB%d/%d rows%d lds%zuK (16x16x4 MFMA, weight ring%s) [k_conv_n16<%d,%d,%d%s%s>]",
+    char buf[224];
+    snprintf(buf, sizeof buf, "conv_n16<w%d,tm%d,pool%d%s> FB%d ZB%d/%d rows%d lds%zuK (16x16x4 MFMA, weight ring%s) [%s]",
              c.WAVES, c.TM, pool, xc ? ",xc4" : "", FB, ZB, p->Dc, p->rows_pf, p->lds_bytes / 1024,
-             xc ? ", channels 16.. on 4x4x1 MFMA blocks" : "", c.WAVES, c.TM, pool, xc ? ",4" : "", geo);
+             xc ? ", channels 16.. on 4x4x1 MFMA blocks" : "", n16_kernel_name(variant, pool, p->geo).c_str());
     p->label = buf;
     return true;
 }
@@ -540,6 +546,14 @@ bool conv_n16_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin,
     if (Cout <= 16) return plan_n16(1, kLdsLimit / 2, in, oc, Cin, pool, kn, p) || plan_n16(0, kLdsLimit, in, oc, Cin, pool, kn, p);
     if (Cout <= 20 && pool == 0) return plan_n16(2, kLdsLimit / 2, in, oc, Cin, pool, kn, p);
     return false;
+}
+
+// every compiled instantiation, one name per line: the non-null entries of kN16 x pool, then kN16Geo
+void conv_n16_kernel_names(std::string* out) {
+    for (int v = 0; v < kNumN16; ++v)
+        for (int pool = 0; pool < 3; ++pool)
+            if (kN16[v].k[pool]) *out += n16_kernel_name(v, pool, 0) + "\n";
+    for (const N16Geo& ge : kN16Geo) *out += n16_kernel_name(ge.variant, 0, ge.geo) + "\n";
 }
 
 // Keras [3,3,3,Cin,Cout] -> [chunk][tap][q][j][t] with ci = chunk*16 + 4q + t, co = j

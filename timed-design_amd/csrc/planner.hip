@@ -348,8 +348,9 @@ void choose_family(const Planner& P, int i, LayerPlan& L) {
     if (k == Kern::None && stem && conv_first_plan(src.D, src.H, src.W, src.C, ov, g, n.C, pool, P.kn, &L.fp)) k = Kern::First;
     if (k == Kern::None && P.use_mfma && g.kd * g.kh * g.kw == 1 && conv_pw_plan(iv, ov, g, src.C, n.C, pool, P.kn, &L.pw))
         k = Kern::Pointwise;
-    auto brick = [&](int pl) {    // one pool value: the 16-wide kernel's variants, then the 32-wide kernel's configurations
-        return conv_n16_plan(iv, ov, g, src.C, n.C, pl, P.kn, &L.np) ? Kern::N16 : conv_mfma_plan(iv, ov, g, src.C, n.C, pl, P.kn, &L.mp) ? Kern::Mfma : Kern::None;
+    auto brick = [&](int pl) {    // one pool value (conv_brick_plan, which th_conv_brick_pick exports)
+        const int b = conv_brick_plan(iv, ov, g, src.C, n.C, pl, P.kn, &L.np, &L.mp);
+        return b == 1 ? Kern::N16 : b == 2 ? Kern::Mfma : Kern::None;
     };
     if (k == Kern::None && P.use_mfma) {
         if (f.pool >= 0) k = brick(pool);
@@ -767,7 +768,7 @@ int emit_mfma(const ConvArgs& c, const LayerPlan& L, Step& st) {
     const PostOps pot = post_from(c.po, cout_main);
     const float* bias_t = c.bias ? c.bias + cout_main : nullptr;
     st.exec_flops = mp.exec_flops + tp.exec_flops;
-    st.label = conv_label(c, mp.label + " x" + std::to_string(mp.nnb) + " + " + tp.label, false, false);
+    st.label = conv_label(c, conv_mfma_tailed_label(L.mp, tp), false, false);
     st.run = [=](hipStream_t s, int64_t cnt) {
         int r1 = launch_conv_mfma(s, cnt, mp, c.in(), c.out(), c.g, c.Cin, cout_main, dw, c.bias, c.pre, c.po);
         if (r1) return r1;
@@ -1094,5 +1095,61 @@ int th_rt::plan(th_model* m) {
         if (rc) return rc;
     }
     for (const Step& s : m->steps) { m->algo_flops += s.direct_flops >= 0 ? s.direct_flops : s.flops; m->exec_flops += s.exec_flops; }
+    return TH_OK;
+}
+
+// ---- the brick kernels' rule: choose_family's decision, and its export for tests (include/timed_hip.h) -----------------------
+int conv_brick_plan(const TView& in, const TView& oc, const ConvGeom& g, int Cin, int Cout, int pool, const ThKnobs& kn,
+                    ConvN16Plan* np, ConvMfmaPlan* mp) {
+    return conv_n16_plan(in, oc, g, Cin, Cout, pool, kn, np) ? 1 : conv_mfma_plan(in, oc, g, Cin, Cout, pool, kn, mp) ? 2 : 0;
+}
+
+// the plan label of a kd x kh x kw convolution, Cin -> Cout, on a D x H x W volume with this pool value (0 none, 1 max, 2 avg) under
+// the default knobs: conv_brick_plan, and for a k_conv_mfma plan conv_mfma_plan_tail, joined as the step label joins them; "" when
+// neither kernel plans the layer.  in_cs (<= 0: a dense tensor of its own) and in_coff describe the input view.
+extern "C" int th_conv_brick_pick(int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, const int stride[3], const int dilation[3],
+                                  int same, int pool, int in_cs, int in_coff, char* buf, size_t len) {
+    if (!buf || !len || !stride || !dilation || pool < 0 || pool > 2 || D < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || kd < 1 || kh < 1 ||
+        kw < 1 || stride[0] < 1 || stride[1] < 1 || stride[2] < 1 || dilation[0] < 1 || dilation[1] < 1 || dilation[2] < 1)
+        TH_FAIL(TH_EINVAL, "th_conv_brick_pick: bad arguments");
+    static const ThKnobs kn;
+    Node src, cv;
+    src.D = D; src.H = H; src.W = W; src.C = Cin;
+    const int k[3] = {kd, kh, kw}, ext[3] = {D, H, W};
+    int out[3];
+    for (int a = 0; a < 3; ++a) {
+        const int ke = (k[a] - 1) * dilation[a] + 1;
+        out[a] = same ? (ext[a] + stride[a] - 1) / stride[a] : (ext[a] - ke) / stride[a] + 1;
+        if (ext[a] < ke && !same) out[a] = 0;
+        cv.ip[a] = k[a]; cv.ip[3 + a] = stride[a]; cv.ip[6 + a] = dilation[a];
+    }
+    cv.ip[9] = same ? 1 : 0;
+    cv.D = out[0]; cv.H = out[1]; cv.W = out[2]; cv.C = Cout;
+    buf[0] = 0;
+    if (out[0] < 1 || out[1] < 1 || out[2] < 1) return TH_OK;
+    const ConvGeom g = conv_geom(cv, src);
+    TView iv = shape_of(src);
+    const TView ov = shape_of(cv);
+    if (in_cs > 0) { iv.cs = in_cs; iv.coff = in_coff; iv.fs = (int64_t)iv.V() * in_cs; }
+    ConvN16Plan np;
+    ConvMfmaPlan mp, tp;
+    int cout_main = 0;
+    const int b = conv_brick_plan(iv, ov, g, Cin, Cout, pool, kn, &np, &mp);
+    std::string label;
+    if (b == 1) label = np.label;
+    else if (b == 2) label = conv_mfma_plan_tail(iv, ov, g, Cin, Cout, mp.pool, mp, kn, &tp, &cout_main) ? conv_mfma_tailed_label(mp, tp) : mp.label;
+    if (label.size() + 1 > len) TH_FAIL(TH_EINVAL, "th_conv_brick_pick: %zu bytes needed", label.size() + 1);
+    std::memcpy(buf, label.c_str(), label.size() + 1);
+    return TH_OK;
+}
+
+// every compiled instantiation of the two brick kernels, one name per line: generated from the dispatch tables of conv_mfma.hip and conv_n16.hip
+extern "C" int th_conv_brick_kernels(char* buf, size_t len) {
+    if (!buf || !len) TH_FAIL(TH_EINVAL, "th_conv_brick_kernels: bad arguments");
+    std::string all;
+    conv_mfma_kernel_names(&all);
+    conv_n16_kernel_names(&all);
+    if (all.size() + 1 > len) TH_FAIL(TH_EINVAL, "th_conv_brick_kernels: %zu bytes needed", all.size() + 1);
+    std::memcpy(buf, all.c_str(), all.size() + 1);
     return TH_OK;
 }

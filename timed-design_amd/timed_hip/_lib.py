@@ -36,6 +36,8 @@ PROTOTYPES = {
     "th_conv_gl_row_tiles": (_i, [_i64]),
     "th_conv_pw_pick": (_i, [_i, _i, _i, _i, _i, _i, _i, C.c_char_p, _sz]),
     "th_conv_pw_kernels": (_i, [C.c_char_p, _sz]),
+    "th_conv_brick_pick": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _pi, _pi, _i, _i, _i, _i, C.c_char_p, _sz]),
+    "th_conv_brick_kernels": (_i, [C.c_char_p, _sz]),
     "th_predict": (_i, [_vp, _vp, _i, _i64, _vp, _u]),
     "th_predict_device": (_i, [_vp, _vp, _i, _i64, _vp, _u]),
     "th_predict_async": (_i, [_vp, _vp, _i, _i64, _vp, _u, _pi]),
