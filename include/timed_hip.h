@@ -949,6 +949,60 @@ int th_sasa(int device, const double* xyz, const double* radius, int64_t total, 
  * doubles.  TH_EINVAL: n_points outside 1 .. 1024 or points_out NULL. */
 int th_sasa_sphere(int32_t n_points, double* points_out);
 
+/* ---- diversity and native recovery of sampled sequences: analyse_samples.py — what sample.py's draws look like as a set.  The
+ * reference reports, in ui.py, accuracy_score(list(seq), list(native)) as "Sequence Identity", the share of positions with
+ * lookup_blosum62(a, b) > 0 as "Sequence Similarity" and a sequence logo; how different the draws are from one another, which are the
+ * same sequence twice and which few to fold it leaves to the reader.  Here for a BATCH of sets in one call.
+ *
+ *     The clustering below is the incremental scheme of CD-HIT-like tools in its plainest form.  It is THIS PROJECT'S OWN RULE, NOT
+ *     THEIR CODE: no word filter, no length sorting and no alignment — the draws of one structure are position-paired by construction.
+ *
+ * All arrays are host memory.
+ *   codes              uint8[total_codes]: set after set, a set's N sequences of its length L row-major.  A residue is one byte: 0..19
+ *                      are the letters ACDEFGHIKLMNPQRSTVWY, 20 is any other letter; a byte above 20 is refused, naming its index;
+ *   total_codes        the sum of N_s * L_s over the sets;
+ *   seq_offsets        int64[n_sets + 1]: set s owns sequences seq_offsets[s] .. seq_offsets[s + 1]; from 0, non-decreasing, at most
+ *                      2^31 - 1 sequences in all.  A set may be empty (N = 0);
+ *   lengths            int32[n_sets]: L_s >= 1, and N_s * L_s <= 2^31 - 1;
+ *   n_sets             0 <= n_sets <= 2^31 - 1;
+ *   native             NULL, or uint8[sum of L_s]: the native sequence of every set, in the same codes;
+ *   substitution       int8[20 * 20], row = the native's code: required with a native (timed_hip.analysis.BLOSUM62 — the kernel and
+ *                      whoever checks it read the same integers);
+ *   min_matches        NULL (no clustering), or int32[n_sets]: 0 <= min_matches[s] <= L_s;
+ *   seq_out            int32[sequences][8], below;
+ *   profile_out        int32[sum of L_s][21]: how many of the set's sequences hold each code at that position;
+ *   matrix_out         NULL, or int32: the N x N block of M of every set, set s at offset sum_{t<s} N_t^2; at most 2^31 - 1 entries;
+ *   set_out            int64[n_sets][4], below;
+ *   kernel_ms          NULL, or double[3]: the device time (events) of the kernels up to the clustering, of the clustering and of the
+ *                      totals, in milliseconds; their sum is the time from the first kernel to the last.
+ * The rule, for one set of sequences 0 .. N-1:
+ *   - PAIR MATCHES: M(i, j) = the number of positions at which i and j hold the same byte.  Identity is of the letters as written:
+ *     code 20 equals code 20;
+ *   - seq_out[i]: 0 native_identical = positions equal to the native; 1 native_similar = positions where both codes are below 20 and
+ *     substitution[native][seq] > 0; 2 native_score = the sum of substitution[native][seq] over the positions where both codes are
+ *     below 20; 3 pair_sum = sum_{j != i} M(i, j); 4 nearest_matches = max_{j != i} M(i, j), -1 when N = 1; 5 nearest_index = the
+ *     lowest j != i attaining it, -1 when N = 1; 6 first_equal = the lowest j with M(i, j) = L — the self pair counts, so
+ *     first_equal <= i, and i is a distinct sequence iff first_equal == i; 7 cluster.  Without a native columns 0 .. 2 are 0;
+ *   - CLUSTERING, greedy, in input order: sequence n joins the lowest-indexed representative r < n with M(n, r) >= min_matches[s];
+ *     otherwise it becomes a representative.  cluster = the representative's index, its own for a representative; -1 everywhere
+ *     when min_matches is NULL.  The threshold is an integer: an identity is turned into one by the caller (timed_hip/seqset.py:
+ *     ceil(p * L / 1000) of the per-mille p, in integer arithmetic);
+ *   - set_out[s]: sum_{i<j} M(i, j); the number of distinct sequences; the number of clusters (-1 without); sum_i native_identical.
+ * Everything is an integer and no atomics are used: a set's bytes are the same wherever it sits in a batch and whether or not the
+ * matrix is asked for.  All pairs cost N^2 * L residue comparisons, four per packed compare.  Device memory: about 2 L + 36 bytes per
+ * sequence, 85 per position, 56 per set, 4 N^2 with the matrix; a device that cannot hold them is TH_ENOMEM.  TH_EINVAL, before
+ * anything is launched or written: a negative size; total_codes that is not the sum of N_s * L_s; L_s < 1; N_s * L_s, the number of
+ * sequences or (with matrix_out) the sum of N_s^2 above 2^31 - 1; a code above 20 in codes or native; min_matches[s] outside
+ * 0 .. L_s; a NULL that the sizes need (with n_sets > 0 seq_offsets, lengths, set_out and profile_out; with sequences seq_out; with
+ * residues codes); seq_offsets that decrease or do not start at 0; native without substitution.  n_sets = 0 with nothing else is
+ * TH_OK. */
+int th_seqset(int device, const uint8_t* codes, int64_t total_codes, const int64_t* seq_offsets, const int32_t* lengths,
+              int64_t n_sets, const uint8_t* native, const int8_t* substitution, const int32_t* min_matches, int32_t* seq_out,
+              int32_t* profile_out, int32_t* matrix_out, int64_t* set_out, double* kernel_ms);
+/* The tiles of th_seqset's pair kernel into tiles_out[3]: sequences per row tile, sequences per column tile, positions per staged
+ * chunk (host code, no GPU) — so that a test can tell whether its shapes cross them.  TH_EINVAL: tiles_out NULL. */
+int th_seqset_tiles(int32_t* tiles_out);
+
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked
  * datasets that share one geometry (shape[rank], chunk[rank], element size, filter pipeline ids in write order:

@@ -168,6 +168,22 @@ def extract_sasa_from_ampal(pdb, load_pdb: bool = True, probe: float = 1.4, n_po
     return list(chains.values())
 
 
+def calculate_sequence_identity(real_seq: str, predicted_seq: str, device: int = 0) -> float:
+    """The reference's "Sequence Identity" (ui.py, ``accuracy_score(list(seq), list(native))``): the share of positions at which the two
+    equally long sequences hold the same letter, on the GPU through ``timed_hip.seqset``.  For many sequences call
+    ``timed_hip.seqset.analyse`` itself: it scores whole sets in one call."""
+    from timed_hip import seqset
+    return seqset.identity_and_similarity(real_seq, predicted_seq, device=device)[0]
+
+
+def calculate_sequence_similarity(real_seq: str, predicted_seq: str, device: int = 0) -> float:
+    """The reference's "Sequence Similarity" (ui.py ``_calculate_sequence_similarity_wrapper``): the share of positions with
+    ``lookup_blosum62(a, b) > 0``, over the positions at which both letters are among the twenty (the reference's lookup is defined
+    only there; NaN when there is none), on the GPU through ``timed_hip.seqset``."""
+    from timed_hip import seqset
+    return seqset.identity_and_similarity(real_seq, predicted_seq, device=device)[1]
+
+
 def extract_bfactor_from_ampal(pdb_path, load_pdb: bool = True) -> t.List[t.List[float]]:
     """reference analyse_utils.py:112-146: one list per chain with the B-factor of the first atom of each residue (AlphaFold2
     models carry the pLDDT there).  ``pdb_path`` is a path or, with ``load_pdb=False``, a ``timed_hip.pdbio.Model``.  Differs

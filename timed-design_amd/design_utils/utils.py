@@ -6,7 +6,8 @@ Written from scratch: HDF5 access goes through h5py when importable and the bund
 reader otherwise, amino-acid tables are local (design_utils/amino_acids.py), and the per-residue
 Python loops of the reference are vectorised where that cannot change the output.
 
-Out of scope here (UI helpers of the reference module): BLOSUM lookup, alphanumeric map codes, rm_tree.  The
+``lookup_blosum62`` is a host lookup in ``timed_hip.analysis.BLOSUM62``.  Out of scope here (UI helpers of the reference
+module): alphanumeric map codes, rm_tree.  The
 reference's PDB property editing (modify_pdb_with_input_property) is replaced by property maps: ``open_structure_set``
 and timed_hip/voxeliser.py spec item 8; ``convert_seq_to_property`` keeps its name.
 """
@@ -59,6 +60,17 @@ def _as_str(v) -> str:
 # dataset-map flavours: (column delimiter, header lines to skip)
 _MAP_FORMATS = {True: (",", 0),     # old maps: csv rows (pdb, chain, residue_id, label)
                 False: (" ", 3)}    # PDBench maps: three header lines, then "<pdb> <count>"
+
+
+def lookup_blosum62(res_true: str, res_prediction: str) -> int:
+    """reference utils.py:172-187: the BLOSUM62 score of two one-letter residue codes, from ``timed_hip.analysis.BLOSUM62`` (the table
+    is symmetric, so the reference's swapped second look-up is the same entry).  A letter outside the twenty is a KeyError, as in the
+    reference.  Whole sets of sequences are scored against their native on the GPU by ``timed_hip.seqset``."""
+    from timed_hip import analysis
+    for letter in (res_true, res_prediction):
+        if len(letter) != 1 or letter not in analysis.RESIDUES:
+            raise KeyError((res_true, res_prediction))
+    return int(analysis.BLOSUM62[analysis.RESIDUES.index(res_true), analysis.RESIDUES.index(res_prediction)])
 
 
 def load_datasetmap(path_to_datasetmap: Path, is_old: bool = False) -> np.ndarray:
