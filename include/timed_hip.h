@@ -1002,6 +1002,13 @@ int th_seqset(int device, const uint8_t* codes, int64_t total_codes, const int64
 /* The tiles of th_seqset's pair kernel into tiles_out[3]: sequences per row tile, sequences per column tile, positions per staged
  * chunk (host code, no GPU) — so that a test can tell whether its shapes cross them.  TH_EINVAL: tiles_out NULL. */
 int th_seqset_tiles(int32_t* tiles_out);
+/* The tiles of the Winograd GEMM kernels of the 5^3 layers (csrc/conv_wino.hip: k_wino_gemm, k_wino_gemm_b3_16 / _b3_32 and, with
+ * 32-frame row blocks of one 32-column tile, k_wino_gemm_n32) into tiles_out[3]: frames per row block (64; a launch's rows are the
+ * frames rounded up to it), output channels per column block (128; four waves of 32 columns, a wave whose columns are all padding
+ * stays idle), input channels per staged chunk (32; a layer's Cin is padded up to it) — host code, no GPU, so that the case table of
+ * the tests (tests/wino_cases.py) can tell which blocks, chunks and ragged edges its shapes reach, and fails when a tile changes.
+ * TH_EINVAL: tiles_out NULL. */
+int th_conv_wino_tiles(int32_t* tiles_out);
 
 /* ---- frame ingest: replaces the per-residue h5py reads of load_batch — design_utils/utils.py:514-529.  Host code
  * only.  `file` is the whole HDF5 file in memory (an mmap), `base` its superblock offset.  For n_datasets chunked

@@ -20,9 +20,12 @@ a Winograd form a separation of about 3: the unit has to follow the points.)  Th
     natural_unit    the same algorithm on absolute values in float64, times 2^-24
     impulse_frames  frames with one nonzero full-mantissa fp32 voxel, and `expected`, their float64 result in closed form
     separation      E6 (all six products) and E5 (the best of the emulations that lose one small product) in units of u
+    plain_conv      the same transforms with UNSPLIT operands: U rounded once to float32, one fp32 product per multiply-add, fp32
+                    accumulation — what conv_wino.hip's fp32-input GEMM (k_wino_gemm, TH_WINO_SPLIT=0) computes; Eplain in separation
 
 All of it is emulation on the CPU: it says what the scheme of bf16x3.h computes, not what a kernel computes.  The GPU tests
-(tests/test_gpu_split_products.py) hold the kernels to the geometric mean of E6 and E5."""
+(tests/test_gpu_split_products.py) hold the kernels to the geometric mean of E6 and E5 — and the fp32-input GEMM, the plan the
+load-time guard retreats to when the split kernels are off, to the geometric mean of Eplain and E5: the same side of the same line."""
 from __future__ import annotations
 
 import itertools
@@ -92,8 +95,9 @@ def _along(M, a, axis):
 
 
 def _run(x, kernel, segments, mode, keep=KEEP6, dtype=np.float32, plain_taps=()):
-    """mode "split": the piece products of `keep`, accumulated in `dtype`; mode "abs": every product of the same algorithm on
-    absolute values, float64.  x [N, D, H, W, Cin], kernel [kd, kh, kw, Cin, Cout] -> [N, D', H', W', Cout]: a transformed axis has
+    """mode "split": the piece products of `keep`, accumulated in `dtype`; mode "plain": unsplit operands, the weights rounded once
+    to `dtype` after their float64 transform, one product per multiply-add, accumulated in `dtype`; mode "abs": every product of the
+    same algorithm on absolute values, float64.  x [N, D, H, W, Cin], kernel [kd, kh, kw, Cin, Cout] -> [N, D', H', W', Cout]: a transformed axis has
     sum(segments) outputs, a direct one as many as inputs."""
     absolute = mode == "abs"
     dt = np.dtype(np.float64 if absolute else dtype)
@@ -111,6 +115,9 @@ def _run(x, kernel, segments, mode, keep=KEEP6, dtype=np.float32, plain_taps=())
         v = _along(f(ax[i][0]), v, 1 + i)
     if absolute:
         vp, Up = [v], [np.abs(U)]
+        pairs = [(0, 0)]
+    elif mode == "plain":
+        vp, Up = [v], [U.astype(dt)]
         pairs = [(0, 0)]
     else:
         if dt == np.float32:
@@ -158,6 +165,12 @@ def split_conv(x, kernel, segments, keep=KEEP6, dtype=np.float32, plain_taps=())
     Weights are transformed and split in float64, data in `dtype`, accumulation in `dtype`.  With dtype float64 the third piece of
     both operands is the exact remainder, so ALL9 gives the convolution itself.  plain_taps: (dz, dy) taps multiplied unsplit."""
     return _run(x, kernel, segments, "split", keep, dtype, plain_taps)
+
+
+def plain_conv(x, kernel, segments, dtype=np.float32):
+    """The same convolution with unsplit operands: the weights' transform in float64 and ONE rounding to `dtype` (as
+    conv_wino_pack_weights stores U for the fp32-input GEMM), the data's transform, every product and the accumulation in `dtype`."""
+    return _run(x, kernel, segments, "plain", dtype=dtype)
 
 
 def natural_unit(x, kernel, segments):
@@ -258,9 +271,9 @@ def _around_the_impulses(x, kernel, segments, fn):
     return y
 
 
-def separation(x, kernel, segments, exact, post=None, unit_post=None, plain_taps=(), drops=SMALL):
+def separation(x, kernel, segments, exact, post=None, unit_post=None, plain_taps=(), drops=SMALL, plain=False):
     """E6: (max, rms) in units of u of the six-piece emulation of the frames x against `exact`; E5: the smallest max and the
-    smallest rms over the emulations that lose one product of `drops`.  post / unit_post: the epilogue applied to the emulator's
+    smallest rms over the emulations that lose one product of `drops`; with `plain` also Eplain, the unsplit fp32 form (plain_conv).  post / unit_post: the epilogue applied to the emulator's
     output and to the unit (e.g. a crop and a max-pool: max-pooling is 1-Lipschitz, the pooled unit is the window's largest).
     The emulations run on a crop around each frame's nonzero voxels (_around_the_impulses)."""
     post = post or (lambda y: y)
@@ -273,6 +286,10 @@ def separation(x, kernel, segments, exact, post=None, unit_post=None, plain_taps
     e6, stray = in_units(emulate(KEEP6), exact, unit)
     assert stray == 0.0, stray
     res["E6"] = e6
+    if plain:
+        y = _around_the_impulses(x, kernel, segments, lambda w: plain_conv(w, kernel, segments))
+        res["Eplain"], stray = in_units(post(y.astype(np.float64)), exact, unit)
+        assert stray == 0.0, stray
     per = {}
     for d in drops:
         per[d], _ = in_units(emulate(tuple(k for k in KEEP6 if k != d)), exact, unit)
@@ -281,9 +298,10 @@ def separation(x, kernel, segments, exact, post=None, unit_post=None, plain_taps
     return res
 
 
-def bound(sep):
-    """the GPU tests' bound: the geometric mean of "correct" and "one product missing", for max and for rms"""
-    return (float(np.sqrt(sep["E6"][0] * sep["E5"][0])), float(np.sqrt(sep["E6"][1] * sep["E5"][1])))
+def bound(sep, correct="E6"):
+    """the GPU tests' bound: the geometric mean of "correct" and "one product missing", for max and for rms.  correct: "E6" for the
+    split kernels, "Eplain" for the fp32-input GEMM"""
+    return (float(np.sqrt(sep[correct][0] * sep["E5"][0])), float(np.sqrt(sep[correct][1] * sep["E5"][1])))
 
 
 def maxpool2(y):
@@ -395,7 +413,7 @@ def case_frames(name, kind="impulse"):
 
 def case_reference(name, kind="impulse"):
     """everything the CPU knows about a case: frames, model, the float64 expectation behind the case's epilogue, the unit, E6, E5
-    and the bound.  E5 is taken over the small products that exist in the frames: all three on impulse frames; on cancelling
+    and the bound; for the conv_wino cases also Eplain and bound_plain, the fp32-input GEMM's.  E5 is taken over the small products that exist in the frames: all three on impulse frames; on cancelling
     frames m*M and l*H (the two impulses have the same h up to sign — the factor 1 + 2^-12 changes bits below the first piece — so
     h*H, h*M and h*L cancel, and the m and l pieces of the data carry the output); on uint8 frames m*M and h*L (a voxel is one
     bf16 piece, the F(2,3) sum point 255 + 254 two: l = 0 everywhere)."""
@@ -406,6 +424,6 @@ def case_reference(name, kind="impulse"):
     post, unit_post = case_post(name)
     exact = post(expected(imp, kernel, (c["side"],) * 3))
     sep = separation(frames.astype(np.float32), kernel, a["segments"], exact, post, unit_post, a["plain_taps"],
-                     drops={"impulse": SMALL, "cancel": ("lH", "mM"), "u8": ("mM", "hL")}[kind])
+                     drops={"impulse": SMALL, "cancel": ("lH", "mM"), "u8": ("mM", "hL")}[kind], plain=c["alg"] == "wino")
     return dict(cfg=cfg, weights=w, kernel=kernel, frames=frames, impulses=imp, exact=exact, unit=sep["unit"], sep=sep,
-                bound=bound(sep), batch=c["batch"])
+                bound=bound(sep), bound_plain=bound(sep, "Eplain") if "Eplain" in sep else None, batch=c["batch"])

@@ -10,6 +10,11 @@ on the impulse frames and an emulation that loses one small product is E5 = 70..
 output and in the rms — the geometric midpoint between "correct" and "one product missing", taken from the references, never
 from the kernel's own output.  An output that no product reaches, and every output of the all-zero frame, must be exactly 0.
 
+The fp32-input GEMM of conv_wino.hip (k_wino_gemm, TH_WINO_SPLIT=0) runs the same frames: it is the plan the load-time guard retreats
+to when the split kernels are off, so it is held to the same side of the same line — below sqrt(Eplain E5), Eplain the CPU emulation
+of the unsplit form (U rounded once to float32, one fp32 product per multiply-add, fp32 accumulation: split_products.plain_conv).
+Exact zeros there catch stale LDS and stale padding rows of V leaking into real rows.
+
 Every model is one convolution without bias.  Its epilogue ("form", split_products.ALGS):
     k_wino_gemm_b3_16 / _b3_32 / _n32, k_conv_wfs     identity: Conv3D -> Flatten
     k_conv_first_b3                                   Conv3D -> ReLU -> MaxPool 2^3 -> Flatten (the planner gives the kernel only to a
@@ -55,7 +60,8 @@ def _worst(got, r, k=4):
     return "\n".join(out)
 
 
-def _check(gpu, monkeypatch, name, kernel, env=(), kinds=("impulse", "cancel")):
+def _check(gpu, monkeypatch, name, kernel, env=(), kinds=("impulse", "cancel"), plain=False):
+    """plain: the case runs on unsplit fp32 operands — no "bf16x3" in the label, Eplain in the place of E6"""
     for k, v in env:
         monkeypatch.setenv(k, v)
     for kind in kinds:
@@ -64,7 +70,7 @@ def _check(gpu, monkeypatch, name, kernel, env=(), kinds=("impulse", "cancel")):
         labels = [s["label"] for s in model.steps()]
         # the layer's steps carry its name; a Winograd layer has its two transform steps besides the GEMM
         conv = [l for l in labels if l.startswith("conv3d: ") and "[k_wino_in]" not in l and "[k_wino_out]" not in l]
-        assert len(conv) == 1 and kernel in conv[0] and "bf16x3" in conv[0], labels
+        assert len(conv) == 1 and kernel in conv[0] and ("bf16x3" in conv[0]) == (not plain), labels
         knobs, guard = model.knobs(), model.guard()
         assert guard["state"] != 2 and "guard:" not in knobs, (guard, knobs)       # the load-time guard dropped nothing
         for k, v in env:
@@ -77,8 +83,8 @@ def _check(gpu, monkeypatch, name, kernel, env=(), kinds=("impulse", "cancel")):
         model.close()
         got = got.reshape(r["exact"].shape).astype(np.float64)
         (mx, rms), stray = sp.in_units(got, r["exact"], r["unit"])
-        e6, e5, bound = r["sep"]["E6"], r["sep"]["E5"], r["bound"]
-        print(f"\n{name} {kind} {kernel} {dict(env)}: E6 max {e6[0]:.2f} rms {e6[1]:.3f}   E5 max {e5[0]:.1f} rms {e5[1]:.2f}   "
+        e6, e5, bound = r["sep"]["Eplain" if plain else "E6"], r["sep"]["E5"], r["bound_plain" if plain else "bound"]
+        print(f"\n{name} {kind} {kernel} {dict(env)}: {'Eplain' if plain else 'E6'} max {e6[0]:.2f} rms {e6[1]:.3f}   E5 max {e5[0]:.1f} rms {e5[1]:.2f}   "
               f"bound max {bound[0]:.2f} rms {bound[1]:.3f}   GPU max {mx:.2f} rms {rms:.3f} u   off the impulse's reach {stray:g}")
         assert np.isfinite(got).all()
         assert not zero.any(), "the all-zero frame"
@@ -92,6 +98,14 @@ def test_wino_gemm_b3(gpu, monkeypatch, name, var):
     """k_wino_gemm_b3_16 (the default) and k_wino_gemm_b3_32 (TH_WINO_B3VAR=0): one K chunk (32 -> 64), and Cin 40 padded to 64 with
     a ragged column block (72 of 128) — the padding lanes must contribute nothing.  Form: identity"""
     _check(gpu, monkeypatch, name, "[k_wino_gemm_b3]", env=(("TH_WINO_B3VAR", "0"),) if var == "32" else ())
+
+
+@pytest.mark.parametrize("name", ["wino_32_64", "wino_40_72"])
+def test_wino_gemm_fp32(gpu, monkeypatch, name):
+    """k_wino_gemm, the fp32-input GEMM (TH_WINO_SPLIT=0), on the frames of the split kernels: one K chunk, whose last k-slot's weight
+    prefetch re-reads its own slot, and Cin 40 padded to 64 with a ragged column block; 140 frames in two calls of 70, so a row block
+    of 6 real frames above 58 rows of V that hold whatever the call before left.  Form: identity"""
+    _check(gpu, monkeypatch, name, "[k_wino_gemm]", env=(("TH_WINO_SPLIT", "0"),), plain=True)
 
 
 @pytest.mark.parametrize("name", ["n32_128_20", "n32_160_7"])

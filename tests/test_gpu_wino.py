@@ -1,8 +1,10 @@
 """Cook-Toom / Winograd path of the 3x3x3 'same' convolutions on 5^3 volumes (csrc/conv_wino.hip; the default, TH_WINOGRAD=0
-switches it off) against the
-float64 oracle and the torch-fp64 fixtures, through the C ABI.  Same bounds as the direct kernels (tests/test_gpu_cnn.py): the
-transforms are integer / power-of-two matrices and the products run on the fp32 matrix pipe, so the error is accumulation-order
-noise (tests/winograd_numerics.py: 6.8e-7 on the logits of TIMED-synth against 7.7e-7 for the direct form)."""
+switches it off) against the float64 oracle and the torch-fp64 fixtures, through the C ABI.  Same bounds as the direct kernels
+(tests/test_gpu_cnn.py): the transforms are integer / power-of-two matrices, and the products run by default on the bf16 matrix pipe
+with both operands split exactly into three pieces (k_wino_gemm_b3_16 / _n32, six piece products per multiply-add: csrc/bf16x3.h),
+under TH_WINO_SPLIT=0 on the fp32 matrix pipe (k_wino_gemm) — the plan the load-time guard retreats to first.  Either way the error
+is accumulation-order noise (tests/winograd_numerics.py: 6.8e-7 on the logits of TIMED-synth against 7.7e-7 for the direct form).
+The whole-net tests run under the plans of PLANS; tests/test_gpu_wino_cases.py holds every GEMM x scheme cell to the oracle."""
 import numpy as np
 import pytest
 
@@ -15,6 +17,49 @@ TIGHT = 5e-6
 # BatchNorm): the direct kernel's own worst element is 1.0e-5 x max|y| there (a serial fp32 chain over K = 6912), the Winograd
 # path's 3.3e-5 x (rms 1.6e-6 against 5.9e-7; tests/wino_layer_error.py) — both accumulation noise at that scale
 LAYER = 1e-5
+FAST = 2e-5          # F(5, 3): asserted bound of the opt-in 7-point scheme (north star: 1e-4 on the logits)
+LAYER_FAST = 1e-4    # and of a single layer's tensor under it (test_single_layer_seven_point_scheme)
+
+# the plans the whole-net tests run under: the default (split operands on the bf16 pipe), the fp32-input GEMM alone, the documented
+# triple that keeps fp32-input MFMA everywhere (README.md), and the 7-point scheme
+PLANS = {
+    "default": {},
+    "fp32": {"TH_WINO_SPLIT": "0"},
+    "fp32-everywhere": {"TH_WINO_SPLIT": "0", "TH_WF_SPLIT": "0", "TH_FIRST_SPLIT": "0"},
+    "f53": {"TH_WINOGRAD": "2"},
+}
+
+
+def _with_plans(cases, plans, argnames):
+    """cases x plans; the default plan keeps the id the case had before the other plans were added"""
+    out = []
+    for case in cases:
+        cid = "-".join(str(v) for v in (case if isinstance(case, tuple) else (case,)))
+        for plan in plans:
+            out.append(pytest.param(*(case if isinstance(case, tuple) else (case,)), plan, id=cid if plan == "default" else f"{cid}-{plan}"))
+    return pytest.mark.parametrize(argnames + ",plan", out)
+
+
+def _set_plan(monkeypatch, plan):
+    for k, v in PLANS[plan].items():
+        monkeypatch.setenv(k, v)
+
+
+def _check_plan(model, plan):
+    """the handle runs the plan it was asked for — its knobs, the GEMM kernel and the scheme of every Winograd layer — and the
+    load-time guard dropped nothing (a tripped guard would run the direct plan, on which every comparison passes)"""
+    labels = [s["label"] for s in model.steps()]
+    wino = [l for l in labels if "conv_wino<" in l]
+    knobs, guard = model.knobs(), model.guard()
+    assert wino and guard["state"] != 2 and "guard:" not in knobs, (guard, knobs, labels)
+    for k, v in PLANS[plan].items():
+        assert f"{k}={v}" in knobs, knobs
+    if plan.startswith("fp32"):
+        assert all("[k_wino_gemm]" in l and "bf16x3" not in l for l in wino), wino
+    else:
+        assert "TH_WINO_SPLIT" not in knobs and all("bf16x3" in l and "[k_wino_gemm]" not in l for l in wino), (knobs, wino)
+    assert all(("F(5,3)" in l) == (plan == "f53") for l in wino), wino
+    return labels
 
 
 def _one_layer(cin, cout, seed, pre=False, bias=True):
@@ -72,17 +117,32 @@ def test_single_layer_matches_the_float64_oracle(gpu, monkeypatch, cin, cout, n,
         model.close()
 
 
-@pytest.mark.parametrize("name", ["timed20", "timed338", "timed20_c5_bias", "timed20_bool"])
-def test_timed_fixtures_with_winograd(gpu, cnn_golden, monkeypatch, name):
+@_with_plans(["timed20", "timed338", "timed20_c5_bias", "timed20_bool"], ("default", "fp32", "fp32-everywhere"), "name")
+def test_timed_fixtures_with_winograd(gpu, cnn_golden, monkeypatch, name, plan):
     """the torch-fp64 fixtures of tests/test_gpu_cnn.py with the 5^3 layers on the Winograd path: same 5e-6 bound on
-    probabilities and logits, same argmax; small and large chunks (one launch, and launches of 1-3 frames)"""
+    probabilities and logits, same argmax; small and large chunks (one launch, and launches of 1-3 frames).  Under the default plan,
+    with the fp32-input GEMM (k_wino_gemm), and with fp32-input MFMA in every kernel family: there conv3d_2..4 are Winograd layers
+    behind one input transform and two fused mid transforms, and a 20-class head — narrow, which needs split operands — is on a direct
+    kernel behind a plain output transform (the 338-class head stays a Winograd layer, on k_wino_gemm)"""
     monkeypatch.setenv("TH_WINOGRAD", "1")
+    _set_plan(monkeypatch, plan)
     z, meta = cnn_golden
     m = next(x for x in meta if x["name"] == name)
     cfg, weights = getattr(synth, m["builder"])(**m["kwargs"])
     frames = synth.synthetic_frames(m["n"], **m["frame_kwargs"])
     model = engine.HipFrameModel.from_keras(cfg, weights, device=gpu)
     assert sum("conv_wino" in s["label"] for s in model.steps()) >= 3
+    labels = _check_plan(model, plan)
+    if plan != "default":
+        conv = [l for l in labels if l.startswith("conv3d") and not any(k in l for k in ("wino_in", "wino_out", "wino_mid"))]
+        wide_head = m["kwargs"]["n_classes"] > 32
+        assert [("[k_wino_gemm]" in l) for l in conv] == [False, False, True, True, True, wide_head], conv
+        assert not any("k_wino" in l for l in conv[:2]) and ("k_wino" in conv[-1]) == wide_head, conv
+        assert [sum(k in l for l in labels) for k in ("k_wino_in", "k_wino_mid", "k_wino_out")] == [1, 3 if wide_head else 2, 1], labels
+        tail = [l for l in labels if "[k_wino_out]" in l][0]
+        assert ("global_avg_pool" in tail) == wide_head, tail             # 20 classes: a plain k_wino_out that feeds the direct head
+        if plan == "fp32-everywhere":
+            assert not any("bf16x3" in l for l in labels), labels
     for chunk in (1024, 3):
         model.set_chunk(chunk)
         probs = model.predict(frames)
@@ -118,9 +178,6 @@ def test_winograd_is_not_taken_where_it_does_not_apply(gpu, monkeypatch):
     assert [("k_wino_gemm" in l) for l in conv] == [False, False, True, True, True, False]
     assert [sum(k in l for l in labels) for k in ("k_wino_in", "k_wino_mid", "k_wino_out")] == [1, 2, 1]
     model.close()
-
-
-FAST = 2e-5          # F(5, 3): asserted bound of the opt-in 7-point scheme (north star: 1e-4 on the logits)
 
 
 @pytest.mark.parametrize("name", ["timed20", "timed338"])
@@ -164,10 +221,14 @@ def test_single_layer_seven_point_scheme(gpu, monkeypatch, cin, cout, n):
     model.close()
 
 
-def test_winograd_layers_on_concat_arenas(gpu):
+@pytest.mark.parametrize("plan", ["default", "fp32", "f53"])
+def test_winograd_layers_on_concat_arenas(gpu, monkeypatch, plan):
     """a Winograd layer that WRITES into a channel slice of a zero-copy concat arena (voxel stride 96, first channel 32), one
     that READS the whole arena (Cin = 96) and one that reads only the slice its sibling wrote: strided views on both sides of
-    the transform kernels, against the float64 oracle"""
+    the transform kernels, against the float64 oracle; also with the fp32-input GEMM and under the 7-point scheme (its bounds:
+    FAST on the probabilities, LAYER_FAST on a layer's tensor)"""
+    _set_plan(monkeypatch, plan)
+    tight, layer_bound = (FAST, LAYER_FAST) if plan == "f53" else (TIGHT, LAYER)
     b = synth.KerasGraphBuilder((5, 5, 5, 32), seed=11)
     x = b.input_name
     a = b.batchnorm(b.elu(b.conv3d(x, 64, 3, padding="same")))
@@ -181,13 +242,14 @@ def test_winograd_layers_on_concat_arenas(gpu):
     frames = (rng.standard_normal((9, 5, 5, 5, 32)) * (rng.random((9, 5, 5, 5, 32)) < 0.4)).astype(np.float32)
     model = engine.HipFrameModel.from_keras(cfg, w, device=gpu)
     assert sum("k_wino_gemm" in s["label"] for s in model.steps()) == 3, [s["label"] for s in model.steps()]
+    _check_plan(model, plan)
     probs = model.predict(frames)
     ref = cnn_oracle.forward(cfg, w, frames, np.float64, return_all=True)
-    np.testing.assert_allclose(probs, ref[list(ref)[-1]], atol=TIGHT, rtol=0)
+    np.testing.assert_allclose(probs, ref[list(ref)[-1]], atol=tight, rtol=0)
     for name in (y1, y2):
         want = ref[name]
         got = model.fetch(name, 9, want.shape[1:])
-        np.testing.assert_allclose(got, want, atol=LAYER * max(1.0, float(np.abs(want).max())), rtol=0, err_msg=name)
+        np.testing.assert_allclose(got, want, atol=layer_bound * max(1.0, float(np.abs(want).max())), rtol=0, err_msg=name)
     model.close()
 
 
@@ -220,38 +282,45 @@ def test_transform_launches_in_pieces(gpu):
     assert np.isfinite(outs[0]).all() and np.array_equal(outs[0], outs[1])
 
 
-@pytest.mark.parametrize("name", ["timed20", "timed338"])
-def test_fused_mid_transform_is_bit_identical(gpu, cnn_golden, monkeypatch, name):
+@_with_plans(["timed20", "timed338"], ("default", "fp32", "f53"), "name")
+def test_fused_mid_transform_is_bit_identical(gpu, cnn_golden, monkeypatch, name, plan):
     """k_wino_mid (output transform of one Winograd layer + input transform of the next, the tensor between them never written) against
-    the separate k_wino_out / k_wino_in launches (TH_WINO_NOMID=1): same arithmetic in the same order, so the same bits"""
+    the separate k_wino_out / k_wino_in launches (TH_WINO_NOMID=1): same arithmetic in the same order, so the same bits — behind the
+    split GEMMs, behind the fp32-input GEMM (two mid steps with a 20-class head) and in the 7-point scheme (k_wino_mid<7>)"""
+    _set_plan(monkeypatch, plan)
     z, meta = cnn_golden
     m = next(x for x in meta if x["name"] == name)
     cfg, weights = getattr(synth, m["builder"])(**m["kwargs"])
     frames = synth.synthetic_frames(m["n"], **m["frame_kwargs"])
     fused = engine.HipFrameModel.from_keras(cfg, weights, device=gpu)
     assert sum("k_wino_mid" in s["label"] for s in fused.steps()) >= 2
+    _check_plan(fused, plan)
     with pytest.raises(_lib.TimedHipError, match="fused away"):
         fused.predict(frames[:1]); fused.fetch("batch_normalization_2", 1, (5, 5, 5, 128))
     monkeypatch.setenv("TH_WINO_NOMID", "1")
     plain = engine.HipFrameModel.from_keras(cfg, weights, device=gpu)
     assert not any("k_wino_mid" in s["label"] for s in plain.steps())
+    _check_plan(plain, plan)
     assert np.array_equal(fused.predict(frames, logits=True), plain.predict(frames, logits=True))
     assert np.array_equal(fused.predict(frames), plain.predict(frames))
     fused.close(); plain.close()
 
 
-@pytest.mark.parametrize("cin,cout,n", [(64, 338, 9), (32, 64, 70)])
-def test_output_transform_pools_for_a_global_average_tail(gpu, monkeypatch, cin, cout, n):
+@_with_plans([(64, 338, 9), (32, 64, 70)], ("default", "fp32", "f53"), "cin,cout,n")
+def test_output_transform_pools_for_a_global_average_tail(gpu, monkeypatch, cin, cout, n, plan):
     """Conv -> ELU -> BN -> GlobalAveragePooling3D -> Softmax with the convolution on conv_wino.hip: the output transform adds up
     the 125 values of a (frame, channel) itself (k_wino_out<P, true>) and the 5^3 activation is never written.  Same summation
-    order as the pooling kernels: probabilities AND logits equal the unfused tail's bit for bit; against the oracle as usual."""
+    order as the pooling kernels: probabilities AND logits equal the unfused tail's bit for bit; against the oracle as usual (FAST
+    under the 7-point scheme, k_wino_out<7, true>); also behind the fp32-input GEMM."""
     monkeypatch.setenv("TH_WINOGRAD", "1")
+    _set_plan(monkeypatch, plan)
     cfg, w, layer = _one_layer(cin, cout, seed=cin * 3 + cout, pre=False)
     rng = np.random.default_rng(n)
     frames = (rng.standard_normal((n, 5, 5, 5, cin)) * (rng.random((n, 5, 5, 5, cin)) < 0.5)).astype(np.float32)
     fused = engine.HipFrameModel.from_keras(cfg, w, device=gpu)
     labels = [s["label"] for s in fused.steps()]
     assert any("wino_out + global_avg_pool" in l for l in labels) and not any("k_gap_softmax" in l for l in labels), labels
+    _check_plan(fused, plan)
     with pytest.raises(_lib.TimedHipError):
         fused.predict(frames[:1]); fused.fetch(layer, 1, (5, 5, 5, cout))          # that tensor does not exist
     monkeypatch.setenv("TH_NO_TAIL_FUSE", "1")
@@ -261,7 +330,7 @@ def test_output_transform_pools_for_a_global_average_tail(gpu, monkeypatch, cin,
         assert np.array_equal(fused.predict(frames[:k]), plain.predict(frames[:k]))
         assert np.array_equal(fused.predict(frames[:k], logits=True), plain.predict(frames[:k], logits=True))
     ref = cnn_oracle.forward(cfg, w, frames[:8], np.float64)
-    np.testing.assert_allclose(fused.predict(frames[:8]), ref, atol=TIGHT, rtol=0)
+    np.testing.assert_allclose(fused.predict(frames[:8]), ref, atol=FAST if plan == "f53" else TIGHT, rtol=0)
     fused.close(); plain.close()
 
 

@@ -1,7 +1,8 @@
 """The CPU references of the split-operand tests (tests/split_products.py) checked against the oracle and against each other, and
 the condition that gives tests/test_gpu_split_products.py its meaning: on the very frames and weights the GPU tests run, the
 emulation that loses one small piece product (E5) is at least 8 times as far from float64 as the six-product scheme of
-csrc/bf16x3.h (E6), in the worst output and in the rms, both in units of u = 2^-24 sum |a| |U| |v|.  Established on references
+csrc/bf16x3.h (E6), in the worst output and in the rms, both in units of u = 2^-24 sum |a| |U| |v| — and, for the conv_wino cases that
+also run on the fp32-input GEMM (TH_WINO_SPLIT=0), at least 8 times as far as the unsplit fp32 form (Eplain).  Established on references
 alone: no kernel runs here.  Serves reference predict.py:142; uses the CPU oracle (test infrastructure)."""
 import os
 import sys
@@ -20,6 +21,7 @@ SMALL = {
     "b3": (sp.FIRST_B3, (1, 4, 5, 21, 3), 3),
     "f5": (sp.FIRST5, (1, 6, 7, 8, 2), 5),
 }
+PLAIN = ("wino_32_64", "wino_40_72")          # the cases tests/test_gpu_split_products.py runs under TH_WINO_SPLIT=0
 KINDS = [(name, kind) for name in sp.CASES for kind in ("impulse", "cancel")] + [("b3_6_32", "u8")]
 
 
@@ -78,6 +80,22 @@ def test_in_plane_emulation_agrees_with_the_one_the_logit_gates_use(seg, side):
     assert d5 >= 8 * (e_mine + e_other), d5
 
 
+def test_plain_products_in_float64_are_the_convolution():
+    """the unsplit emulation shares transforms and tap geometry with the split one: in float64 it IS cnn_oracle.conv3d, and in
+    float32 it is within a few u of it on dense frames (one rounding of U, one per product and per addition)"""
+    seg, shape, k = SMALL["wino"]
+    rng = np.random.default_rng(6)
+    x, w = rng.standard_normal(shape), rng.standard_normal((k, k, k, shape[-1], 4))
+    want = cnn_oracle.conv3d(x, w, None, 1, 1, "same", np.float64)
+    assert np.abs(sp.plain_conv(x, w, seg, np.float64) - want).max() < 1e-9
+    x32, w32 = x.astype(np.float32), w.astype(np.float32)
+    want = cnn_oracle.conv3d(x32.astype(np.float64), w32.astype(np.float64), None, 1, 1, "same", np.float64)
+    got = sp.plain_conv(x32, w32, seg)
+    assert got.dtype == np.float32
+    (mx, _), _ = sp.in_units(got, want, sp.natural_unit(x32, w32, seg))
+    assert 1e-3 < mx < 4.0, mx
+
+
 @pytest.mark.parametrize("name,kind", KINDS)
 def test_a_lost_product_is_eight_times_the_scheme_s_own_error(name, kind):
     r = sp.case_reference(name, kind)
@@ -86,6 +104,11 @@ def test_a_lost_product_is_eight_times_the_scheme_s_own_error(name, kind):
           + "  ".join(f"-{k} {v[0]:.1f}/{v[1]:.2f}" for k, v in r["sep"]["drop"].items())
           + f"   bound max {r['bound'][0]:.2f} rms {r['bound'][1]:.3f}")
     assert e5[0] >= 8 * e6[0] and e5[1] >= 8 * e6[1], (e6, e5)
+    if name in PLAIN:              # the fp32-input GEMM runs these frames too: its own form is as far from a lost product
+        ep, bp = r["sep"]["Eplain"], r["bound_plain"]
+        print(f"{name} {kind}: Eplain max {ep[0]:.2f} rms {ep[1]:.3f} u   bound max {bp[0]:.2f} rms {bp[1]:.3f}")
+        assert e5[0] >= 8 * ep[0] and e5[1] >= 8 * ep[1], (ep, e5)
+        assert bp == (float(np.sqrt(ep[0] * e5[0])), float(np.sqrt(ep[1] * e5[1])))
     # every channel is visited, and the frames are what they claim to be
     frames, imp = r["frames"], r["impulses"]
     per = 1 if kind == "impulse" else 2

@@ -101,6 +101,7 @@ PROTOTYPES = {
     "th_sasa_sphere": (_i, [C.c_int32, _vp]),
     "th_seqset": (_i, [_i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pd]),
     "th_seqset_tiles": (_i, [_vp]),
+    "th_conv_wino_tiles": (_i, [_vp]),
     "th_tmscore": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _pd]),
     "th_tm_d0": (_d, [_i64]),
     "th_cealign": (_i, [_i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _d, _d, _i, _vp, _vp, _vp, _vp, _pd]),
