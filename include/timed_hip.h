@@ -689,6 +689,67 @@ int th_superpose(int device, const double* ref_xyz, const double* mob_xyz, int64
 int th_lddt(int device, const double* ref_xyz, const double* mob_xyz, int64_t total, const int64_t* offsets, int64_t n_pairs,
             double radius, const double* thresholds, int32_t* residue_out, int64_t* pair_out, double* kernel_ms);
 
+/* ---- *** PARITY UNPINNED AGAINST OPENSTRUCTURE *** All-atom lDDT with symmetric side chains: analyse_models.py --lddt_all_atom,
+ * build_sidechains.py --lddt, pack_sidechains.py --lddt — the local Distance Difference Test (Mariani et al. 2013) over the heavy
+ * atoms of a model against those of its native, the form CASP, CAMEO and OpenStructure quote, and the superposition-free measure of
+ * side-chain placement: the names of chemically equivalent atoms (the ring edges of PHE and TYR, the carboxylate oxygens of ASP and
+ * GLU, ...) are resolved per residue before anything is counted.  Here for a BATCH of atom-paired coordinate lists.
+ *
+ *     *** PARITY UNPINNED AGAINST OPENSTRUCTURE ***  OpenStructure is not available where this project is built.  The rule below is
+ *     this project's reading of the PUBLISHED definition (Mariani et al. 2013) in float64 with fp contract(off): no stereochemistry
+ *     checks, no sequence-separation filter, strict inequalities on both tests, a missing model atom costs score.  It is not
+ *     OpenStructure's code, it aligns no sequences, and no test can pin it against OpenStructure itself.
+ *
+ * All arrays are host memory.
+ *   ref_xyz, mob_xyz   double[total][3]: the reference (native) and the model coordinates of all pairs, pair after pair; atom i of
+ *                      one list is the same atom as atom i of the other (any value, NaN and infinities included);
+ *   residue            int32[total]: the residue index of the atom, local to its pair: 0 at the pair's first atom, non-decreasing, in
+ *                      steps of 0 or 1 (a residue's atoms are contiguous);
+ *   partner            int32[total]: the index, local to the pair, of the atom with which this one may exchange names, -1 when there
+ *                      is none: inside the pair, not the atom itself, in the same residue, and partner[partner[i]] = i.  Under
+ *                      TH_LDDT_NO_SYMMETRY it is neither read nor checked and may be NULL;
+ *   total              number of atoms, 0 <= total <= 2^31 - 1;
+ *   offsets            int64[n_pairs + 1]: pair p owns atoms offsets[p] .. offsets[p + 1]; as for th_lddt.  A pair may be empty;
+ *   n_pairs            0 <= n_pairs <= 2^31 - 1;
+ *   radius             inclusion radius, finite and > 0 (the published default: 15.0);
+ *   thresholds         double[4], each finite and > 0 (the published default: 0.5, 1, 2, 4);
+ *   flags              0 or TH_LDDT_NO_SYMMETRY;
+ *   atom_out           int32[total][5]: n_i, c_i[0..3]; five zeros at an atom that is not reference-valid;
+ *   swapped_out        uint8[total]: 1 where the model coordinates used for this atom were its partner's;
+ *   pair_out           int64[n_pairs][8]: n_ref (reference-valid atoms), n_missing, N, C[0..3], n_swapped_residues;
+ *   kernel_ms          NULL, or double[2]: the device time in milliseconds of the symmetry resolution and of the counting kernels.
+ * The rule, for one pair, all arithmetic float64 and no fused multiply-add:
+ *   - REFERENCE-VALID: an atom whose three reference coordinates are finite.  An atom that is not is never an i and never a j, and
+ *     its row is zeros;
+ *   - MISSING: a reference-valid atom whose model coordinates are not all finite (the kernel makes all three NaN).  It stays in every
+ *     count of included pairs and is preserved at no threshold: a missing atom costs score, which is the published behaviour.  This
+ *     differs on purpose from th_lddt, which drops such a position;
+ *   - DISTANCE  d(a, b) = sqrt((dx*dx + dy*dy) + dz*dz), as for th_lddt;
+ *   - an ordered pair (i, j) is INCLUDED when both atoms are reference-valid, residue[i] != residue[j] and d_ref(i, j) < radius.
+ *     Strict.  (The kernel compares the squared distance with th_packing_threshold(radius), which decides the same for every double,
+ *     and takes square roots of included pairs only.)  There is no self pair to subtract: it lies within one residue;
+ *   - an included pair is PRESERVED at threshold t when |d_ref(i, j) - d_mob(i, j)| < t.  Strict;
+ *   - SYMMETRY RESOLUTION, unless TH_LDDT_NO_SYMMETRY: for every residue R that has atoms with partner >= 0, keep_R and swap_R are
+ *     sums over the atoms a of R that have a partner, over the atoms b with partner[b] < 0 and residue[b] != R, of the (a, b)
+ *     included by the reference distance, and over the four thresholds, of the preserved tests of d(mob[a], mob[b]) for keep and of
+ *     d(mob[partner[a]], mob[b]) for swap.  R is swapped iff swap_R > keep_R; a tie keeps the names.  A swap exchanges the model
+ *     coordinates of all partnered atoms of R together, and all counts are taken on the model after the swaps.  The decisions look
+ *     only at atoms without a partner, so they depend neither on one another nor on their order;
+ *   - per atom: n_i is the number of included j, c_i[k] the number of those preserved at thresholds[k];
+ *   - per pair: n_ref, n_missing, N = sum n_i, C[k] = sum c_i[k] over ORDERED pairs, and the number of swapped residues, 64-bit;
+ *   - the caller forms the fractions as for th_lddt: lddt = sum_k C[k] / (4 N), pair-weighted, NaN when N = 0.
+ * Out of scope: stereochemistry checks, sequence-separation filters, ligands, sequence alignment, hydrogens, NMR ensembles.
+ * All outputs are integers decided by float64 comparisons: a pair's outputs depend on its own arrays alone — not on its place in the
+ * batch or on its neighbours — and two calls give the same bytes.  No atomics.  No length limit beyond the 2^31 - 1 atoms of a call.
+ * Device memory: 77 bytes per atom + 12 per partnered atom + 8 per 256 atoms of every pair + 88 per pair.  TH_EINVAL, before anything
+ * is launched or written: everything th_lddt refuses; a NULL residue, partner (without TH_LDDT_NO_SYMMETRY), atom_out or swapped_out
+ * when total > 0; a residue array that breaks the rule above; a partner that is out of its pair, is the atom itself, lies in another
+ * residue or fails partner[partner[i]] == i; unknown flag bits.  n_pairs = 0 (with total = 0) is success without a launch. */
+#define TH_LDDT_NO_SYMMETRY 1u   /* partner is ignored: the model is scored as named */
+int th_lddt_atoms(int device, const double* ref_xyz, const double* mob_xyz, const int32_t* residue, const int32_t* partner,
+                  int64_t total, const int64_t* offsets, int64_t n_pairs, double radius, const double* thresholds, unsigned flags,
+                  int32_t* atom_out, uint8_t* swapped_out, int64_t* pair_out, double* kernel_ms);
+
 /* ---- *** PARITY UNPINNED AGAINST THE TM-score PROGRAM *** TM-score of models against their native: analyse_models.py --tmscore —
  * the template-modelling score (Zhang & Skolnick 2004), the "scTM against the native" of a design pipeline's self-consistency
  * check.  It is the MAXIMUM over superpositions of sum_i 1 / (1 + (d_i / d0)^2) / L, and the superposition that attains it is in

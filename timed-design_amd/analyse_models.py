@@ -87,6 +87,19 @@ already parsed for the superposition (hetero atoms never occlude here, and chain
 PARITY UNPINNED AGAINST FREESASA / NACCESS / DSSP / BIOPYTHON: none of them is available to pin this against.  The rule is this
 project's own, written out in include/timed_hip.h and timed_hip/sasa.py; the maximum areas behind the relative accessibility (after
 Tien et al. 2013) are WRITTEN FROM MEMORY, NOT FETCHED.
+
+--lddt_all_atom additionally writes ``model_lddt_all_atom.csv``, one row per pair — label, reference, model, n_atoms (the reference's
+heavy atoms of the paired residues with finite coordinates), n_missing (of those, atoms the model lacks: they cost score),
+n_mismatched_residues (paired residues whose names differ: only their N, CA, C, O enter), n_included, lddt, the four preserved
+fractions, lddt_backbone and lddt_sidechain (the same sums over the rows of N, CA, C, O and of the other atoms), n_swapped_residues,
+error — and ``residue_lddt_all_atom.csv`` — label, chain, number and residue of the reference, the model's residue, n_atoms, n_missing,
+n_included, lddt and swapped of every paired residue.  This is the lDDT that CASP, CAMEO and OpenStructure quote (th_lddt_atoms):
+over all heavy atoms, pairs inside one residue excluded, with the names of symmetric side-chain atoms (ASP OD1/OD2, GLU OE1/OE2, PHE
+and TYR CD1/CD2 and CE1/CE2, ARG NH1/NH2, LEU CD1/CD2, VAL CG1/CG2) resolved per residue, so a ring turned by 180 degrees is not
+charged; --lddt_no_symmetry scores the model as named.  It reuses --lddt_radius, --pair_by and --pair_by_cealign and the files parsed
+for the superposition.  PARITY UNPINNED AGAINST OPENSTRUCTURE: the rule is this project's reading of the published definition,
+written out in include/timed_hip.h and timed_hip/lddt_atoms.py; the table of symmetric atoms is WRITTEN FROM MEMORY, NOT FETCHED.  Out
+of scope: stereochemistry checks, sequence-separation filters, ligands, sequence alignment, hydrogens, NMR ensembles.
 """
 import argparse
 import csv
@@ -97,6 +110,7 @@ import numpy as np
 
 from timed_hip import cealign as cealign_module
 from timed_hip import lddt as lddt_module
+from timed_hip import lddt_atoms as lddt_atoms_module
 from timed_hip import sasa as sasa_module
 from timed_hip import secstruct as secstruct_module
 from timed_hip import superpose
@@ -289,7 +303,7 @@ def main(args):
         todo = [(label, reference, path) for label, path in find_structures(args.path_to_models)]
     if not todo:
         sys.exit("no pair to score: no *.pdb / *.pdb1 / *.ent (.gz) file under --path_to_models, or an empty --pairs file")
-    if args.lddt and not (args.lddt_radius > 0 and args.lddt_radius < float("inf")):
+    if (args.lddt or getattr(args, "lddt_all_atom", False)) and not (args.lddt_radius > 0 and args.lddt_radius < float("inf")):
         sys.exit(f"--lddt_radius {args.lddt_radius} is not a positive finite number")
     if getattr(args, "sasa", False) and not 1 <= getattr(args, "sasa_points", 96) <= sasa_module.MAX_POINTS:
         sys.exit(f"--sasa_points {args.sasa_points} is outside 1 .. {sasa_module.MAX_POINTS}")
@@ -317,6 +331,10 @@ def main(args):
         write_cealign(out, todo, aligned)
     if args.lddt:
         write_lddt(out, todo, lddt_module.lddt(prepared, radius=args.lddt_radius, device=args.device, stats=stats))
+    if getattr(args, "lddt_all_atom", False):
+        lddt_atoms_module.write_csv(out / "model_lddt_all_atom.csv", out / "residue_lddt_all_atom.csv", todo,
+                                    lddt_atoms_module.lddt_atoms(prepared, symmetry=not getattr(args, "lddt_no_symmetry", False),
+                                                                 radius=args.lddt_radius, device=args.device, stats=stats))
     if args.secondary_structure:
         write_secstruct(out, todo, prepared, args.device, stats)
     if getattr(args, "sasa", False):
@@ -387,6 +405,12 @@ CLI_FLAGS = (
     ("--sasa_probe", dict(default=argparse.SUPPRESS, type=float, help="--sasa: probe radius in Angstrom (default 1.4; 0: the van der Waals surface)")),
     ("--rsa_core", dict(default=argparse.SUPPRESS, type=float, help="--sasa: a residue is core below this relative accessibility (default 0.2)")),
     ("--rsa_surface", dict(default=argparse.SUPPRESS, type=float, help="--sasa: a residue is surface from this relative accessibility (default 0.5)")),
+    ("--lddt_all_atom", dict(default=argparse.SUPPRESS, action="store_true",
+                             help="also write model_lddt_all_atom.csv and residue_lddt_all_atom.csv: the lDDT over all heavy atoms of the paired "
+                                  "residues, with the names of symmetric side-chain atoms resolved per residue, beside its backbone and "
+                                  "side-chain parts.  PARITY UNPINNED AGAINST OPENSTRUCTURE")),
+    ("--lddt_no_symmetry", dict(default=argparse.SUPPRESS, action="store_true",
+                                help="--lddt_all_atom: score the model as named, a flipped ring or carboxylate included")),
 )
 
 

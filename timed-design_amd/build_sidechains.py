@@ -27,6 +27,12 @@ PARITY UNPINNED AGAINST SCWRL4: the reference packs side chains with SCWRL4's en
 against and is not rebuilt.  The table of internal coordinates and the rules (atoms paired by name without symmetry correction;
 a clash is a side-chain atom within --clash_distance of an atom of another residue, the backbone of chain neighbours and SG-SG
 excepted) are this project's own, written out in timed_hip/sidechains.py.
+
+--lddt additionally writes ``structure_sidechain_lddt.csv`` and ``residue_sidechain_lddt.csv``: the all-atom lDDT (th_lddt_atoms) of
+every built structure against its native, residues paired by chain and number, with the names of symmetric side-chain atoms
+resolved per residue — the symmetry-aware companion of the RMSD columns, which stay as they are.  The columns are those of
+analyse_models.py --lddt_all_atom; ``lddt_sidechain`` is the figure for the built atoms, a side chain that was not built counts as
+missing.  PARITY UNPINNED AGAINST OPENSTRUCTURE.
 """
 import argparse
 import csv
@@ -35,7 +41,7 @@ from pathlib import Path
 
 import numpy as np
 
-from timed_hip import batching, pdbio, sidechains, structure
+from timed_hip import batching, lddt_atoms, pdbio, sidechains, structure
 from timed_hip.pdbio import find_structures, stem_of
 
 STRUCTURE_COLUMNS = ["structure", "residues", "built", "native_type", "atoms_matched", "rmsd", "clashing_pairs", "unmatched_rows"]
@@ -111,6 +117,10 @@ def main(args):
                 wr.writerow([label, native.chain, native.number, native.name, res.built_names[r] or "",
                              "" if res.cls is None or res.cls[r] < 0 else int(res.cls[r])] + [text(x) for x in res.chi[r]] +
                             [int(res.n_built[r]), int(res.n_matched[r]), text(res.rmsd[r]), int(res.clashes[r])])
+    if getattr(args, "lddt", False):
+        scored = lddt_atoms.score_models([res.residues for res in built], [res.to_model().residues for res in built], device=args.device, stats=stats)
+        lddt_atoms.write_csv(out / "structure_sidechain_lddt.csv", out / "residue_sidechain_lddt.csv",
+                             [(label, path, f"{stem_of(label)}_{suffix}.pdb") for label, path in found], scored)
     atoms = sum(int(res.n_matched.sum()) for res in built)
     total = float(np.sqrt(sum(float(res.sum_sq.sum()) for res in built) / atoms)) if atoms else float("nan")
     print(f"{len(found)} structures, {sum(int((res.n_built > 0).sum()) for res in built)} side chains built ({suffix}), {atoms} atoms matched, "
@@ -131,6 +141,9 @@ CLI_FLAGS = (
     ("--clash_distance", dict(type=float, default=sidechains.CLASH_DISTANCE, help="two atoms closer than this (Angstrom) clash")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
     ("--workers", dict(type=int, default=8, help="host threads that read and parse the files (at most 16)")),
+    ("--lddt", dict(default=argparse.SUPPRESS, action="store_true",
+                    help="also write structure_sidechain_lddt.csv and residue_sidechain_lddt.csv: the all-atom lDDT of every built structure "
+                         "against its native, symmetric side-chain names resolved.  PARITY UNPINNED AGAINST OPENSTRUCTURE")),
 )
 
 

@@ -53,6 +53,19 @@ max_asa = {
 }
 WATER_NAMES = ("HOH", "WAT", "DOD")
 
+# All-atom lDDT (timed_hip/lddt_atoms.py).  residue -> the pairs of side-chain atom names that a 180-degree turn of the last chi angle
+# exchanges: the same molecule under either naming.  WRITTEN FROM MEMORY, NOT FETCHED: nothing here could be checked against
+# OpenStructure's table of symmetric atoms.
+SYMMETRIC_ATOMS = {
+    "ASP": (("OD1", "OD2"),),
+    "GLU": (("OE1", "OE2"),),
+    "PHE": (("CD1", "CD2"), ("CE1", "CE2")),
+    "TYR": (("CD1", "CD2"), ("CE1", "CE2")),
+    "ARG": (("NH1", "NH2"),),
+    "LEU": (("CD1", "CD2"),),
+    "VAL": (("CG1", "CG2"),),
+}
+
 # Stand-in for aposteriori.config.UNCOMMON_RESIDUE_DICT (used at reference utils.py:381-385 to map a
 # non-standard residue label onto its parent amino acid while the dataset map is built).  aposteriori
 # 2.4.0 is not in the reference tree nor in this image, so its exact table is UNPINNED; this one holds

@@ -223,6 +223,19 @@ def calculate_cealign_RMSD(pdb_original_path, pdb_predicted_path, device: int = 
     return res.rmsd
 
 
+def calculate_all_atom_lddt(pdb_original_path, pdb_predicted_path, device: int = 0) -> float:
+    """The all-atom lDDT (Mariani et al. 2013) of a predicted structure against its original, over the heavy atoms of the residues
+    paired by position, with the names of symmetric side-chain atoms resolved per residue: ``lddt`` of
+    ``timed_hip.lddt_atoms.lddt_atoms``.  PARITY UNPINNED AGAINST OPENSTRUCTURE: the rule is this project's reading of the published
+    definition (include/timed_hip.h, th_lddt_atoms).  Structures of different length or a file that cannot be read raise ValueError.
+    For many pairs call ``lddt_atoms`` itself: it batches them."""
+    from timed_hip import lddt_atoms
+    (res,) = lddt_atoms.lddt_atoms([(pdb_original_path, pdb_predicted_path)], device=device)
+    if res.error:
+        raise ValueError(f"{pdb_original_path} / {pdb_predicted_path}: {res.error}")
+    return res.lddt
+
+
 # ---- per-class rotamer metrics (analyse_rotamers.py; computed on the GPU by timed_hip.analysis) -------------------------------
 def _narrow(matrix: np.ndarray) -> np.ndarray:
     """float16 / float32 matrices as they are; others to float16 when that is exact (the probability CSVs predict.py writes),

@@ -24,6 +24,12 @@ sterics alone.  Without a matrix the native sequence is packed by sterics alone.
 Writes ``<pdb>_<suffix>.pdb`` per structure (the suffix is ``packed_<matrix name>`` or ``packed``), ``structure_packing.csv``,
 ``residue_packing.csv`` (empty fields stand for absent values) and ``rotamer_labels.json`` of the packed classes, in the format
 analyse_rotamers.py --path_to_rotamer_labels reads.
+
+--lddt additionally writes ``structure_sidechain_lddt.csv`` and ``residue_sidechain_lddt.csv``: the all-atom lDDT (th_lddt_atoms) of
+every packed structure against its native, residues paired by chain and number, with the names of symmetric side-chain atoms
+resolved per residue.  The packer places bin centres and cannot tell the two namings of a ring or a carboxylate apart; the RMSD
+columns, which stay as they are, charge it for that, ``lddt_sidechain`` does not.  The columns are those of analyse_models.py
+--lddt_all_atom.  PARITY UNPINNED AGAINST OPENSTRUCTURE.
 """
 import argparse
 import csv
@@ -33,7 +39,7 @@ from pathlib import Path
 
 import numpy as np
 
-from timed_hip import batching, packer, pdbio, sidechains, structure
+from timed_hip import batching, lddt_atoms, packer, pdbio, sidechains, structure
 from timed_hip.pdbio import find_structures, stem_of
 
 STRUCTURE_COLUMNS = ["structure", "residues", "packed", "energy_initial", "energy_final", "sweeps", "moves", "converged", "status", "atoms_matched",
@@ -101,6 +107,11 @@ def main(args):
                          labels=labels, stats=stats)
     out = Path(args.path_to_output)
     write_outputs(out, labels, packed, suffix)
+    if getattr(args, "lddt", False):
+        scored = lddt_atoms.score_models([res.residues for res in packed], [res.built.to_model().residues for res in packed], device=args.device,
+                                         stats=stats)
+        lddt_atoms.write_csv(out / "structure_sidechain_lddt.csv", out / "residue_sidechain_lddt.csv",
+                             [(label, path, f"{stem_of(label)}_{suffix}.pdb") for label, path in found], scored)
     atoms = sum(int(res.built.n_matched.sum()) for res in packed)
     total = float(np.sqrt(sum(float(res.built.sum_sq.sum()) for res in packed) / atoms)) if atoms else float("nan")
     print(f"{len(found)} structures, {sum(int((res.cls >= 0).sum()) for res in packed)} side chains packed ({suffix}), energy "
@@ -128,6 +139,9 @@ CLI_FLAGS = (
     ("--clash_distance", dict(type=float, default=sidechains.CLASH_DISTANCE, help="two atoms of the result closer than this (Angstrom) are reported as a clash")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
     ("--workers", dict(type=int, default=8, help="host threads that read and parse the files (at most 16)")),
+    ("--lddt", dict(default=argparse.SUPPRESS, action="store_true",
+                    help="also write structure_sidechain_lddt.csv and residue_sidechain_lddt.csv: the all-atom lDDT of every packed structure "
+                         "against its native, symmetric side-chain names resolved.  PARITY UNPINNED AGAINST OPENSTRUCTURE")),
 )
 
 

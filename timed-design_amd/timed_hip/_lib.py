@@ -96,6 +96,7 @@ PROTOTYPES = {
     "th_pack_sidechains": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _vp, C.c_int32, C.c_int32, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "th_superpose": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _pd]),
     "th_lddt": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _pd]),
+    "th_lddt_atoms": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _d, _vp, _u, _vp, _vp, _vp, _pd]),
     "th_secondary_structure": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _pd]),
     "th_sasa": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _d, _vp, C.c_int32, _vp, _vp, _vp, _pd]),
     "th_sasa_sphere": (_i, [C.c_int32, _vp]),
