@@ -312,6 +312,9 @@ ConvFusion fuse_chain(const Planner& P, int i) {
             f.src = x;
         }
     }
+    // activation='softmax' runs as a step of its own after the layer (LayerPlan::split_softmax), in place on the layer's output:
+    // whatever follows it must read the probabilities, so no epilogue chain and no pool join the layer
+    if ((n.op == OP_CONV3D ? n.ip[13] : n.ip[3]) == ACT_SOFTMAX) return f;
     // epilogue: elementwise chain with single consumers
     int cur = i;
     int npost = (n.op == OP_CONV3D ? n.ip[13] : n.ip[3]) != ACT_LINEAR ? 1 : 0;
@@ -496,6 +499,18 @@ int build_epilogue(Planner& P, int i, LayerPlan& L) {
     return TH_OK;
 }
 
+// Dense node dn closes a GlobalAveragePooling3D -> Dense -> Softmax (the model output) tail within k_tail_dense's limits: F <= 2048 features
+// (the pooled vectors of a workgroup's four frames in LDS), O <= 512 outputs (eight rounds of 64 lanes), no activation of its own
+bool closes_dense_tail(const Planner& P, int dn) {
+    const std::vector<Node>& N = P.N;
+    const Node& d = N[dn];
+    if (d.op != OP_DENSE || d.C > 512 || d.ip[3] != ACT_LINEAR || dn == P.m->output_node || d.consumers.size() != 1) return false;
+    const Node& gp = N[d.in[0]];
+    if (gp.op != OP_GAP || gp.C > 2048 || gp.consumers.size() != 1) return false;
+    const Node& sm = N[d.consumers[0]];
+    return sm.op == OP_ACT && sm.ip[0] == ACT_SOFTMAX && d.consumers[0] == P.m->output_node;
+}
+
 // in this order: wino -> wfs -> wf -> first5 -> first -> pointwise -> gl -> n16 / mfma -> direct.  After the chunk-blocked pass: the
 // wfs and gl kernels read `blk`.
 int choose_kernel(Planner& P, int i, LayerPlan& L) {
@@ -505,7 +520,10 @@ int choose_kernel(Planner& P, int i, LayerPlan& L) {
     const Node& sn = P.N[L.f.src];
     if (n.op == OP_DENSE) {
         if (sn.cs != sn.C || sn.coff != 0 || sn.D * sn.H * sn.W != 1) TH_FAIL(TH_EUNSUP, "%s: Dense needs a contiguous vector input", n.name.c_str());
-        L.kind = P.kn.dense_gemm && dense_gemm_ok(sn.C, n.C, m->bufs[sn.buf].floats_per_frame) ? Kern::DenseGemm : Kern::Dense;
+        // TH_NO_TAIL_FUSE=1 is the A/B switch of k_tail_dense, which restates k_dense's fmaf chain: the tail's Dense stays on k_dense there,
+        // so the two plans agree bit for bit at every F (k_dense_gemm sums F in four quarters)
+        const bool tail_ab = P.kn.no_tail_fuse && closes_dense_tail(P, i);
+        L.kind = P.kn.dense_gemm && !tail_ab && dense_gemm_ok(sn.C, n.C, m->bufs[sn.buf].floats_per_frame) ? Kern::DenseGemm : Kern::Dense;
         return TH_OK;
     }
     const ConvGeom& g = L.g;
@@ -900,17 +918,16 @@ int try_dense_tail(Planner& P, int first, Step* st) {
     }
     const int gp = j;
     if (N[gp].op != OP_GAP || P.gap_done.count(gp) || N[gp].absorbed_by >= 0 || !N[gp].materialised || N[gp].consumers.size() != 1 ||
-        gp == M->output_node || N[gp].C > 2048)
+        gp == M->output_node)
         return 0;
     const int dn = N[gp].consumers[0];
-    if (N[dn].op != OP_DENSE || !P.layers.count(dn) || N[dn].C > 512 || N[dn].w[0] < 0) return 0;
-    const ConvFusion& f = P.layers.at(dn).f;
-    if (f.src != gp || !f.pre.empty() || !f.post.empty() || f.pool >= 0 || f.last != dn || !N[dn].materialised) return 0;
     // (Dense(activation='softmax') keeps its two steps: logits and probabilities share the node there, and a TH_PREDICT_LOGITS
     // call drops the in-place softmax step)
-    if (N[dn].ip[3] != ACT_LINEAR || dn == M->output_node || N[dn].consumers.size() != 1) return 0;
+    if (!closes_dense_tail(P, dn) || !P.layers.count(dn) || N[dn].w[0] < 0) return 0;
+    const ConvFusion& f = P.layers.at(dn).f;
+    if (f.src != gp || !f.pre.empty() || !f.post.empty() || f.pool >= 0 || f.last != dn || !N[dn].materialised) return 0;
     const int sm = N[dn].consumers[0];                  // node that holds the probabilities
-    if (!(N[sm].op == OP_ACT && N[sm].ip[0] == ACT_SOFTMAX && sm == M->output_node && N[sm].absorbed_by < 0 && N[sm].materialised)) return 0;
+    if (N[sm].absorbed_by >= 0 || !N[sm].materialised) return 0;
     const int src = N[chain.empty() ? gp : chain[0]].in[0];
     if (N[src].blk || !N[src].materialised || N[src].buf < 0) return 0;
     const Node& gn = N[gp];
