@@ -885,6 +885,66 @@ int th_cealign(int device, const double* ref_xyz, int64_t ref_total, const int64
                const int64_t* mob_offsets, int64_t n_pairs, double d0, double d1, int gap_max, int32_t* align_out, double* score_out,
                int64_t* count_out, double* transform_out, double* kernel_ms);
 
+/* ---- *** PARITY UNPINNED AGAINST PYMOL *** sequence alignment of models to their native: analyse_models.py --seqalign and
+ * --pair_by_seqalign — the pairing that survives renumbering, a missing loop and a purification tag together, and that exists for a
+ * misfolded model too.  The reference's scripts/analyse_af2.py calls PyMOL's cmd.align, a sequence alignment followed by a fit;
+ * th_superpose is the fit, this is the alignment.  cmd.align's own recurrences, end-gap treatment and tie handling are not available
+ * to pin against: the rule below is this project's own, a global alignment with affine gap costs (Gotoh's three tables) whose end
+ * gaps are free or charged, all in integers.  Here for a BATCH of (reference, model) pairs in one call, one wavefront per pair.
+ *
+ * All arrays are host memory.
+ *   ref_codes          uint8[ref_total]: the references, pair after pair.  A residue is one byte: 0..19 are the letters
+ *                      ACDEFGHIKLMNPQRSTVWY, 20 is anything else (the coding of th_seqset); a byte above 20 is refused, naming its index;
+ *   ref_offsets        int64[n_pairs + 1]: pair k owns residues ref_offsets[k] .. ref_offsets[k + 1]; from 0 to ref_total, never
+ *                      decreasing; a sequence may be empty and has at most TH_SEQALIGN_MAX_LENGTH residues;
+ *   mob_codes, mob_total, mob_offsets   the same for the models;
+ *   n_pairs            0 <= n_pairs <= 2^31 - 1, as are both totals;
+ *   matrix             int32[21][21]: the substitution table S, row = the reference's code, every entry within -127 .. 127 (the
+ *                      Python default is 2 x BLOSUM62 with -2 wherever either code is 20: cmd.align's documented gap = -10 and
+ *                      extend = -0.5 then are the integers gap_open = 20 and gap_extend = 1);
+ *   gap_open, gap_extend   0 <= gap_extend <= gap_open <= 32767: a run of k unpaired residues costs gap_open + (k - 1) gap_extend;
+ *   free_ends          1: unpaired residues before the first and after the last cell of the path cost nothing; 0: global;
+ *   align_out          int32[ref_total]: the index, local to the pair, of the model residue aligned to this reference residue, -1 if
+ *                      none (the convention of th_cealign);
+ *   count_out          int64[n_pairs][8]: n_ref, n_model, score, n_aligned, n_identical (aligned and the two bytes equal),
+ *                      n_positive (aligned with S > 0), n_gaps (runs of unpaired residues of either side strictly between the first
+ *                      and the last aligned pair; a run of each side between the same two pairs counts twice), n_gap_residues;
+ *   kernel_ms          NULL, or double[2]: the device time (events) of the fill and of the trace, in milliseconds.
+ * The rule, for one pair — reference a[1..n], model b[1..m] —, three values per cell, "minus infinity" = -2^30:
+ *   1. E[i][j] = max(H[i][j-1] - gap_open, E[i][j-1] - gap_extend): model residue j unpaired.  The cell's E is marked EXTENDED
+ *      only when the second term is strictly greater.
+ *   2. F[i][j] = max(H[i-1][j] - gap_open, F[i-1][j] - gap_extend): reference residue i unpaired; EXTENDED likewise.
+ *   3. H[i][j] starts as H[i-1][j-1] + S[a_i][b_j]; F[i][j] replaces it only if strictly greater; then E[i][j] replaces it only if
+ *      strictly greater.  The ORIGIN (diagonal / F / E) is recorded.
+ *   4. BORDERS.  free_ends = 1: H[i][0] = H[0][j] = 0, and E, F on the border are minus infinity.  free_ends = 0: H[0][0] = 0,
+ *      H[i][0] = F[i][0] = -(gap_open + (i - 1) gap_extend), H[0][j] = E[0][j] = -(gap_open + (j - 1) gap_extend); E[i][0] for i > 0
+ *      and F[0][j] for j > 0 are minus infinity.
+ *   5. END CELL.  Global: (n, m).  Free ends: the maximum of H over the last row and the last column, scanned (n, m) first, then
+ *      (n, j) for j = m - 1 .. 0, then (i, m) for i = n - 1 .. 0; a later cell wins only if strictly greater.  score = H there.
+ *   6. TRACE from the end cell in state H.  In state H read the origin: diagonal pairs a_i with b_j and moves to (i - 1, j - 1);
+ *      origin F or E enters that state.  In state F read the EXTENDED bit of F at (i, j), move to (i - 1, j), and stay in F if it
+ *      was set, else return to H; E is the same along j.  Stop when i = 0 or j = 0: whatever is left on a border is unpaired.
+ * The score is the sum of S over the aligned pairs minus the cost of every run on the path.  With free ends the path lies between
+ * the border cell where the trace stops and the end cell; a run of ONE side may precede its first pair or follow its last (two
+ * overhangs cannot both be skipped for nothing) and is charged, but is not among n_gaps.  An empty sequence aligns nothing and scores
+ * 0, or minus the border cost in global mode.
+ * k_seqalign_fill: lane l of the pair's wavefront owns a strip of 8 model columns and works on reference row t - l at step t; H and
+ * F of the strip stay in registers, the strip's right edge goes to lane l + 1 by a cross-lane move, the 8 scores of a step are one
+ * 8-byte LDS read, columns beyond 512 are further panels whose edge column is carried in memory, and the four trace bits of a cell
+ * are packed eight cells to a dword.  k_seqalign_trace: one thread per pair walks the bits back.  All integers, no atomics, no float
+ * arithmetic: a pair's bytes are the same wherever it sits in a batch.  Device memory per pair: the trace bits — 4 (n + s - 1) s
+ * bytes for the last panel of s = ceil(columns / 8) strips and 256 (n + 63) for every whole panel before it, 3.4 KB at 76 x 76 and
+ * 8.5 MB at 4096 x 4096 —, 17 bytes per reference residue, 5 per model residue, 120 per pair.  TH_EINVAL, before any device call:
+ * a negative or too large size, a NULL that is required (both offsets, matrix, count_out; with ref_total > 0 ref_codes and
+ * align_out, with mob_total > 0 mob_codes), offsets of either list that decrease, do not start at 0 or do not end at the list's
+ * total, a code above 20, gap_open < gap_extend, gap_extend < 0, gap_open > 32767, free_ends neither 0 nor 1, a table entry outside
+ * -127 .. 127, a sequence of more than TH_SEQALIGN_MAX_LENGTH residues (the score then stays below 2^28 and the trace bits below
+ * 8.5 MB).  n_pairs = 0 (with both totals 0) is success without a launch. */
+#define TH_SEQALIGN_MAX_LENGTH 4096   /* per sequence */
+int th_seqalign(int device, const uint8_t* ref_codes, int64_t ref_total, const int64_t* ref_offsets, const uint8_t* mob_codes,
+                int64_t mob_total, const int64_t* mob_offsets, int64_t n_pairs, const int32_t* matrix, int gap_open, int gap_extend,
+                int free_ends, int32_t* align_out, int64_t* count_out, double* kernel_ms);
+
 /* ---- *** PARITY UNPINNED AGAINST DSSP *** secondary structure of protein backbones: analyse_properties.py --secondary_structure and
  * analyse_models.py --secondary_structure — where the helices and strands are, by the DSSP rule (Kabsch & Sander 1983): backbone
  * hydrogen bonds by an electrostatic energy, then turns, helices, bridges, ladders and bends as patterns of those bonds.  What the

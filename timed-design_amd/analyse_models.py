@@ -19,7 +19,7 @@ PARITY UNPINNED AGAINST PYMOL: PyMOL is not available to pin this against.  The 
 behaviour of cmd.align (cycles 5, cutoff 2.0), written out in include/timed_hip.h and timed_hip/superpose.py: a least-squares fit
 with a proper rotation, then up to --cycles rounds that drop positions further than --cutoff x RMS and fit again.  Pairing is by
 position (file order; native and model must be equally long, as the reference asserts) or by number (chain, residue number and
-insertion code), NOT by a sequence alignment.  Out of scope: AlphaFold2 folder layouts and parsing FASTA or file names into model /
+insertion code), NOT by a sequence alignment unless --pair_by_seqalign asks for one (below).  Out of scope: AlphaFold2 folder layouts and parsing FASTA or file names into model /
 temperature / sample columns — the label is the model's path below --path_to_models, or the third CSV field.
 
 --lddt additionally writes ``model_lddt.csv``, one row per pair — label, reference, model, n_valid, n_included (ordered pairs of
@@ -70,6 +70,23 @@ class and the model's, both three-state letters, and the chain and number of the
 helices and strands?  Each distinct file is assigned once, from the structures already parsed for the superposition, so a native
 shared by a thousand models is one structure in the batch; the pairing is that of model_scores.csv (--pair_by, or --pair_by_cealign).
 
+--seqalign additionally writes ``model_seqalign.csv``, one row per pair — label, reference, model, n_ref, n_model (the residues of
+either structure that have a CA atom), score (in units of the table: twice BLOSUM62's), n_aligned, identity (n_identical / n_aligned),
+positives (aligned with a positive table entry, over n_aligned), n_gaps and n_gap_residues (runs of unpaired residues of either side
+between the first and the last aligned pair, and the residues in them), coverage_ref and coverage_model (n_aligned over either length),
+error — and ``residue_seqalign.csv`` — label, chain, number and residue of every residue of the reference, and the chain, number and
+residue of the model's residue aligned to it (empty if none).  This is the alignment step of cmd.align: the SEQUENCES of the two
+structures (chains concatenated in file order, residue names as one-letter codes, anything unknown as X) are aligned globally with
+affine gap costs — 2 x BLOSUM62, a run of k unpaired residues costs 2 x (--sa_gap_open + (k - 1) --sa_gap_extend), cmd.align's
+documented 10 and 0.5 — with free ends, or charged ends under --sa_global (th_seqalign, at most 4096 residues each).
+--pair_by_seqalign makes that alignment the pairing of model_scores.csv and of every optional score, in place of --pair_by: it
+survives renumbering, a missing loop and a purification tag together, and unlike --pair_by_cealign it exists for a misfolded model.
+It cannot be combined with --pair_by_cealign.
+
+PARITY UNPINNED AGAINST PYMOL: cmd.align's own recurrences, end-gap treatment and tie handling are not available to pin --seqalign
+against; the rule is this project's own, written out in include/timed_hip.h and timed_hip/seqalign.py.  Out of scope: local, profile
+and multiple alignment, banded or heuristic search.
+
 PARITY UNPINNED AGAINST DSSP (mkdssp, PyMOL's dss, STRIDE): none of them is available to pin this against.  The rule is this project's
 reading of the published definition (Kabsch & Sander 1983), written out in include/timed_hip.h and timed_hip/secstruct.py: every
 hydrogen bond below -0.5 kcal/mol counts, beta-bulges are not bridged over, priority H > E > B > G > I > T > S.
@@ -113,6 +130,7 @@ from timed_hip import lddt as lddt_module
 from timed_hip import lddt_atoms as lddt_atoms_module
 from timed_hip import sasa as sasa_module
 from timed_hip import secstruct as secstruct_module
+from timed_hip import seqalign as seqalign_module
 from timed_hip import superpose
 from timed_hip import tmscore as tmscore_module
 from timed_hip.pdbio import find_structures
@@ -126,6 +144,9 @@ LDDT_COLUMNS = ["label", "reference", "model", "n_valid", "n_included", "lddt", 
 RESIDUE_LDDT_COLUMNS = ["label", "chain", "number", "residue", "n_included", "lddt", "model_bfactor"]
 CEALIGN_COLUMNS = ["label", "reference", "model", "n_ref", "n_model", "n_starts", "n_afps", "n_aligned", "rmsd", "path_score", "error"]
 RESIDUE_CEALIGN_COLUMNS = ["label", "chain", "number", "residue", "model_chain", "model_number", "model_residue", "distance"]
+SEQALIGN_COLUMNS = ["label", "reference", "model", "n_ref", "n_model", "score", "n_aligned", "identity", "positives", "n_gaps", "n_gap_residues",
+                    "coverage_ref", "coverage_model", "error"]
+RESIDUE_SEQALIGN_COLUMNS = ["label", "chain", "number", "residue", "model_chain", "model_number", "model_residue"]
 TMSCORE_COLUMNS = ["label", "reference", "model", "n_valid", "norm_length", "d0", "tm_score", "tm_global_fit", "n_seeds", "n_fits", "error"]
 SECSTRUCT_COLUMNS = ["label", "reference", "model", "n_paired", "q8", "q3", "reference_helix_fraction", "reference_strand_fraction",
                      "model_helix_fraction", "model_strand_fraction", "reference_n_hbonds", "model_n_hbonds", "error"]
@@ -289,6 +310,36 @@ def write_cealign(out, todo, aligned):
                 wr.writerow([label, r.chain, r.number, r.name] + ([m.chain, m.number, m.name, _fmt(distance[k])] if m else ["", "", "", ""]))
 
 
+def write_seqalign(out, todo, aligned):
+    """model_seqalign.csv and residue_seqalign.csv; ``aligned``: what seqalign.align returned"""
+    with open(out / "model_seqalign.csv", "w", newline="") as fs, open(out / "residue_seqalign.csv", "w", newline="") as fr:
+        ws, wr = csv.writer(fs), csv.writer(fr)
+        ws.writerow(SEQALIGN_COLUMNS)
+        wr.writerow(RESIDUE_SEQALIGN_COLUMNS)
+        for (label, ref, model), res in zip(todo, aligned):
+            ws.writerow([label, str(ref), str(model), res.n_ref, res.n_model, res.score, res.n_aligned, _fmt(res.identity), _fmt(res.positives),
+                         res.n_gaps, res.n_gap_residues, _fmt(res.coverage_ref), _fmt(res.coverage_model), res.error or ""])
+            if res.error:
+                continue
+            partner = dict(zip(res.reference_index.tolist(), res.model_index.tolist()))
+            for k, r in enumerate(res.reference.residues):
+                m = res.model.residues[partner[k]] if k in partner else None
+                wr.writerow([label, r.chain, r.number, r.name] + ([m.chain, m.number, m.name] if m else ["", "", ""]))
+
+
+def seqalign_costs(args):
+    """(gap_open, gap_extend) of th_seqalign from --sa_gap_open and --sa_gap_extend: twice each, which must be integers"""
+    costs = []
+    for flag, default in (("sa_gap_open", 10.0), ("sa_gap_extend", 0.5)):
+        value = 2.0 * float(getattr(args, flag, default))
+        if not value == int(value) or not 0 <= value <= 32767:
+            sys.exit(f"--{flag} {getattr(args, flag, default)}: twice the cost must be an integer from 0 to 32767")
+        costs.append(int(value))
+    if costs[0] < costs[1]:
+        sys.exit(f"--sa_gap_open {costs[0] / 2} is below --sa_gap_extend {costs[1] / 2}")
+    return tuple(costs)
+
+
 def main(args):
     if args.pairs:
         if args.path_to_reference or args.path_to_models:
@@ -309,6 +360,12 @@ def main(args):
         sys.exit(f"--sasa_points {args.sasa_points} is outside 1 .. {sasa_module.MAX_POINTS}")
     if args.tmscore and args.tm_rounds < 0:
         sys.exit(f"--tm_rounds {args.tm_rounds} is negative")
+    by_sequence = getattr(args, "pair_by_seqalign", False)
+    if by_sequence and args.pair_by_cealign:
+        sys.exit("--pair_by_seqalign and --pair_by_cealign both replace --pair_by: give one of them")
+    sequence_aligning = getattr(args, "seqalign", False) or by_sequence
+    if sequence_aligning:
+        sa_gap_open, sa_gap_extend = seqalign_costs(args)
     aligning = args.cealign or args.pair_by_cealign
     if aligning and not (0 < args.ce_d0 < float("inf") and 0 < args.ce_d1 < float("inf")):
         sys.exit(f"--ce_d0 {args.ce_d0} and --ce_d1 {args.ce_d1} must be positive finite numbers")
@@ -320,7 +377,14 @@ def main(args):
     if aligning:
         aligned = cealign_module.cealign(pairs, "CA", args.ce_d0, args.ce_d1, args.ce_gap_max, args.device, True, args.workers, stats=stats)
         pairs = [(res.reference or ref, res.model or model) for (ref, model), res in zip(pairs, aligned)]        # parsed once for all scores
-    if args.pair_by_cealign:
+    sequence_aligned = None
+    if sequence_aligning:
+        sequence_aligned = seqalign_module.align(pairs, "CA", None, sa_gap_open, sa_gap_extend, not getattr(args, "sa_global", False), args.device,
+                                                 args.workers, stats=stats)
+        pairs = [(res.reference or ref, res.model or model) for (ref, model), res in zip(pairs, sequence_aligned)]
+    if by_sequence:
+        prepared = seqalign_module.prepare_aligned(pairs, results=sequence_aligned, stats=stats)
+    elif args.pair_by_cealign:
         prepared = cealign_module.prepare_aligned(pairs, results=aligned, stats=stats)
     else:
         prepared = superpose.prepare(pairs, args.pair_by, "CA", args.workers)     # read and paired once for both scores
@@ -329,6 +393,8 @@ def main(args):
     out.mkdir(parents=True, exist_ok=True)
     if args.cealign:
         write_cealign(out, todo, aligned)
+    if getattr(args, "seqalign", False):
+        write_seqalign(out, todo, sequence_aligned)
     if args.lddt:
         write_lddt(out, todo, lddt_module.lddt(prepared, radius=args.lddt_radius, device=args.device, stats=stats))
     if getattr(args, "lddt_all_atom", False):
@@ -368,7 +434,7 @@ CLI_FLAGS = (
     ("--cutoff", dict(type=float, default=2.0, help="a refinement cycle drops positions further than this many RMS (default 2.0, cmd.align's)")),
     ("--pair_by", dict(type=str, default="position", choices=list(superpose.PAIR_BY),
                        help="position: CA atoms in file order, equal length required (default); number: by chain, residue number and "
-                            "insertion code.  Never by a sequence alignment")),
+                            "insertion code.  Neither is a sequence alignment: that is --pair_by_seqalign")),
     ("--device", dict(type=int, default=0, help="HIP device index")),
     ("--workers", dict(type=int, default=8, help="host threads that read and parse the files (at most 16)")),
     ("--path_to_output", dict(type=str, default="model_scores", help="directory for model_scores.csv and residue_deviation.csv")),
@@ -411,12 +477,25 @@ CLI_FLAGS = (
                                   "side-chain parts.  PARITY UNPINNED AGAINST OPENSTRUCTURE")),
     ("--lddt_no_symmetry", dict(default=argparse.SUPPRESS, action="store_true",
                                 help="--lddt_all_atom: score the model as named, a flipped ring or carboxylate included")),
+    ("--seqalign", dict(default=argparse.SUPPRESS, action="store_true",
+                        help="also write model_seqalign.csv and residue_seqalign.csv: the sequence alignment of every model to its native "
+                             "(global, affine gaps, 2 x BLOSUM62, at most 4096 residues each), its score, identity, gaps and coverage.  "
+                             "PARITY UNPINNED AGAINST PYMOL")),
+    ("--pair_by_seqalign", dict(default=argparse.SUPPRESS, action="store_true",
+                                help="pair the positions of model_scores.csv and of every optional score by the alignment of --seqalign in "
+                                     "place of --pair_by: renumbering, a missing loop and a tag are then no error.  Not with --pair_by_cealign")),
+    ("--sa_gap_open", dict(default=argparse.SUPPRESS, type=float, help="--seqalign: the cost of a gap's first residue in BLOSUM62 units "
+                                                                       "(default 10, cmd.align's; twice it must be an integer)")),
+    ("--sa_gap_extend", dict(default=argparse.SUPPRESS, type=float, help="--seqalign: the cost of every further residue of a gap (default 0.5, "
+                                                                         "cmd.align's; twice it must be an integer)")),
+    ("--sa_global", dict(default=argparse.SUPPRESS, action="store_true",
+                         help="--seqalign: charge the unpaired residues at either end too (default: the ends are free)")),
 )
 
 
 def build_parser():
     parser = argparse.ArgumentParser(description="RMSD, GDT and per-residue deviation of models superposed on their native, batched on the "
-                                                 "GPU (MI355X).  PARITY UNPINNED AGAINST PYMOL; pairing by position or number, not by alignment",
+                                                 "GPU (MI355X).  PARITY UNPINNED AGAINST PYMOL; pairing by position or number, or by an alignment on request",
                                      epilog=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     for flag, keywords in CLI_FLAGS:
         parser.add_argument(flag, **keywords)

@@ -223,6 +223,21 @@ def calculate_cealign_RMSD(pdb_original_path, pdb_predicted_path, device: int = 
     return res.rmsd
 
 
+def align_sequences(a: str, b: str, device: int = 0) -> t.Tuple[str, str, int]:
+    """The sequence alignment of two strings of one-letter codes, ``a`` the reference: the two sequences written over one another
+    with ``-`` where a residue has no partner, and the score in units of the table — ``timed_hip.seqalign.align_strings`` with its
+    defaults (2 x BLOSUM62, a run of k unpaired residues costs 20 + (k - 1), free ends; halve the score for BLOSUM62 units).  This
+    is the alignment step of PyMOL's ``cmd.align``, which the reference's scripts/analyse_af2.py calls: PARITY UNPINNED AGAINST PYMOL,
+    the rule is this project's own (include/timed_hip.h, th_seqalign).  A sequence of more than 4096 residues raises ValueError.
+    For many pairs call ``align_strings`` itself: it batches them."""
+    from timed_hip import seqalign
+    (res,) = seqalign.align_strings([(a, b)], device=device)
+    if res.error:
+        raise ValueError(res.error)
+    top, bottom = seqalign.gapped(str(a), str(b), res)
+    return top, bottom, res.score
+
+
 def calculate_all_atom_lddt(pdb_original_path, pdb_predicted_path, device: int = 0) -> float:
     """The all-atom lDDT (Mariani et al. 2013) of a predicted structure against its original, over the heavy atoms of the residues
     paired by position, with the names of symmetric side-chain atoms resolved per residue: ``lddt`` of

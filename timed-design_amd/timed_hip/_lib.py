@@ -106,6 +106,7 @@ PROTOTYPES = {
     "th_tmscore": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _pd]),
     "th_tm_d0": (_d, [_i64]),
     "th_cealign": (_i, [_i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _d, _d, _i, _vp, _vp, _vp, _vp, _pd]),
+    "th_seqalign": (_i, [_i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _pd]),
     "th_h5_read_chunked": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i, _pi64, _pi64, _i, _i, _pi, _i]),
     "th_h5_read_chunked_as": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i, _pi64, _pi64, _i, _i, _pi, _i, _i]),
     "th_h5_read_contiguous_as": (_i, [_vp, _i64, _i64, _i64, _pi64, C.POINTER(_vp), _i64, _i, _i]),
